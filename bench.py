@@ -18,6 +18,12 @@ the device, sa_device.hip; the host sorter's time is reported beside it); the wh
 job through the one-call seam andi_hip_dist_matrix -- everything included, cold -- is
 reported under "end_to_end", never in "value".
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps,
+--dump-outputs DIR (the counts of the last timed step) and the result line.  What
+takes runs of its own -- the measured device-copy ceiling, the CPU baseline, the
+one-call seam end to end, the multi-GPU seam, the strong-scaling config and the
+secondary workloads ("extra") -- runs only with --full.
+
 N > 1 (one process per GPU, launched by torch.distributed.run): one G x G
 matrix with G ~ 29*sqrt(N) genomes, rows block-partitioned over the ranks, so
 per-GPU work stays that of one 29 x 29 set ("weak").  No data-path collective;
@@ -34,6 +40,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_MAX_BYTES = 64_000_000 - 4096  # --dump-outputs: everything written, at most (the .npy headers inside the margin)
 
 
 def parse():
@@ -55,8 +62,14 @@ def parse():
     ap.add_argument("--model", choices=("raw", "jc", "kimura"), default="jc", help="the estimator's model (andi -m): what the counts are made for")
     ap.add_argument("--contigs", type=int, default=0, help="every genome cut into that many contigs joined by '!' (andi --join, src/sequence.c:78-125: "
                                                            "what multi-contig assemblies like BASELINE's Maela set look like to the scan)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads (structured genomes, tree-structured set)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the device-copy ceiling, the CPU baseline, "
+                         "the one-call seam end to end, the multi-GPU seam and strong-scaling config, the secondary workloads")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the counts of the last timed step to DIR/counts.npy (float64; a fixed sample of rows, "
+                         "DIR/counts_rows.npy, when the matrix is larger than 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the seam end to end")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads (structured genomes, tree-structured set)")
     ap.add_argument("--seam-child", default="", help=argparse.SUPPRESS)  # internal: the multi-GPU seam in a process of its own
     ap.add_argument("--seed", type=int, default=1729)
     return ap.parse_args()
@@ -309,10 +322,27 @@ def seam_child(spec):
     print("SEAM " + json.dumps(out))
 
 
+def dump_outputs(path, full):
+    """--dump-outputs: the (rows, genomes, 17) counts of the last timed step as float64 (u32 counts are exact in it); beyond
+    DUMP_MAX_BYTES a fixed, seeded sample of rows, sorted, and their indices beside them"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    counts = np.asarray(full, dtype=np.uint32)
+    per_row = counts[0].size * 8 + 8
+    if counts.shape[0] * per_row > DUMP_MAX_BYTES:
+        k = max(1, DUMP_MAX_BYTES // per_row)
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(counts.shape[0], size=k, replace=False))
+        np.save(os.path.join(path, "counts_rows.npy"), rows.astype(np.float64))
+        counts = counts[rows]
+    np.save(os.path.join(path, "counts.npy"), counts.astype(np.float64))
+
+
 def main():
     args = parse()
     if args.seam_child:
         return seam_child(args.seam_child)
+    # a plain run measures the headline alone; what takes runs of its own is behind --full
+    cpu_base = args.full and not args.no_cpu_baseline
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -434,9 +464,9 @@ def main():
 
     # measured device-copy ceiling beside the nominal peak: 1 GiB D2D, read + write bytes
     # (the engine's own 16-byte streaming kernel, HIP events on its stream -- torch's int32 copy_ measured 4.75 TB/s where
-    # the guide's float4 copy does 6.29)
+    # the guide's float4 copy does 6.29); a run of its own: --full only
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             copy_gbps = lib.copy_ceiling(ctx, 1 << 30, 5)
         except Exception:
@@ -456,12 +486,14 @@ def main():
     out = None
     if rank == 0:
         full = gathered[0] if use_dist else shard.gather_matrix(block, G, rows=S)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, full)
         dmat = [andi_amd.estimate(full[0, j].astype(np.uint64) + full[j, 0], model) for j in range(1, min(S, 4))]
         out = {
             "metric": "genome-pairs/sec (ordered pairs, n^2-n) over the N x N anchor-distance loop",
             "value": value, "unit": "pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
+            "dtype": "u8", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": workload_name(args.set, G, S, args.length, args.dlo, args.dhi, args.seed, world, model) + (", every genome as %d contigs joined by '!' (--join)" % args.contigs if args.contigs > 1 else ""),
                        "genomes": G, "subjects": S, "length": args.length, "model": MODEL_NAMES[model], "pairs": pairs_total,
                        "segment": args.segment or ("auto (pass A routed per pair: by wavefronts on segments of 32768 ... 524288 symbols (shorter in small calls), by lanes on segments chosen per pair, 2048 ... 16384)" if tm["routed_calls"] else "auto (chosen per pair from its sampled match lengths: 2048 ... 16384)")},
@@ -469,7 +501,8 @@ def main():
                          "unit": "GB/s", "frac": frac, "traffic": traffic, "traffic_source": traffic_source,
                          "ranks": roofline_ranks,
                          "measured_copy_GBps": copy_gbps,
-                         "measured_copy_kernel": "andi_hip_copy_ceiling: 16 bytes per lane, non-temporal, 1 GiB, 5 passes, read + written bytes",
+                         "measured_copy_kernel": "andi_hip_copy_ceiling: 16 bytes per lane, non-temporal, 1 GiB, 5 passes, read + written bytes"
+                                                 if args.full else "not measured (--full)",
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": scan_ms,
                          "launches": int(tm["scan_launches"]),
                          "note": "the dominant kernel: pass A alone, HIP events around its launch(es) on the engine's streams; the sampling "
@@ -489,11 +522,11 @@ def main():
                            "pairs_per_s_incl_staging": (nsub * (G - 1)) / (t_stage + elapsed / args.steps)},
             "sample_distances": dmat,
         }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_base:
         Mcpu, base = cpu_baseline(seqs, p_value, model)
         out["cpu_baseline"] = base
         out["parity_vs_cpu_baseline"] = bool((Mcpu[:S] == full).all())
-    elif rank == 0 and not args.no_cpu_baseline:
+    elif rank == 0 and cpu_base:
         # N > 1: the baseline is carried forward on a bounded sample -- the first 29 genomes of the set, which ARE the
         # N = 1 workload (same seed, same base, same divergences: one 29 x 29 tile, what every GPU of the weak-scaling job does);
         # the other ranks wait at the barrier below.  Its counts check the gathered matrix's corner.
@@ -509,7 +542,7 @@ def main():
         e.close()
     Q.close()
     ctx.close()
-    if rank == 0 and world == 1 and S == G and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and S == G and cpu_base:
         # the whole job through the one-call seam (context, staging, suffix arrays, index builds, scans, D2H), cold
         t0 = time.time()
         M1 = andi_amd.dist_matrix(seqs, p_value=p_value, model=model)
@@ -586,9 +619,9 @@ def main():
             res = {"error": repr(e)}
         return res
 
-    if rank == 0 and world > 1:
+    if rank == 0 and world > 1 and args.full:
         out["end_to_end"]["seam_multi_gpu"] = seam_on_all_gpus(args.set, G, args.length, args.dlo, args.dhi, model, full)
-    strong = world > 1 or os.environ.get("ANDI_BENCH_C3_STRONG")  # (the variable: the code path on one GPU, for testing)
+    strong = args.full and (world > 1 or os.environ.get("ANDI_BENCH_C3_STRONG"))  # (the variable: the code path on one GPU, for testing)
     if strong and args.set == "star" and not args.subjects and not args.genomes:
         # BASELINE's configs[2] itself: the same 109-genome Kimura matrix on the N ranks, and through the seam's own tiler
         rec, c3_full, c3_spec = c3_strong(args, p_value, world, rank, local_rank, dist if use_dist else None, torch)
@@ -598,7 +631,7 @@ def main():
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()
-    if rank == 0 and world == 1 and not args.no_extra and args.set == "star" and not args.subjects and not args.contigs:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and args.set == "star" and not args.subjects and not args.contigs:
         out.setdefault("extra", {}).update({
             "realistic": secondary("realistic", args, model, p_value),
             "tree_structured": secondary("tree", args, model, p_value),

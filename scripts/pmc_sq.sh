@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; shift
-out=gpurun_out/pmc_$tag
+out=${OUT:-results}/pmc_$tag  # OUT: the folder for results
 mkdir -p $out
 i=0
 while read -r set; do

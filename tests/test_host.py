@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT, rand_dna
+from conftest import GOLDEN, ROOT, rand_dna
 
 
 def test_library_exports_every_declared_symbol():
@@ -216,18 +216,47 @@ void calculate_distances_stub(struct model *M, seq_t *sequences, size_t n) {
     assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
 
 
+def _patch_hunks(text):
+    """[{file, start, count, pre}] of a unified diff: pre = the lines the hunk expects at [start, start + count)"""
+    import re
+    out, path, cur, left = [], None, None, 0
+    for line in text.splitlines():
+        if left == 0 and line.startswith("+++ "):
+            path = line[4:].split("\t")[0].split("/", 1)[1]
+        elif left == 0 and line.startswith("@@"):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+", line)
+            cur = {"file": path, "start": int(m.group(1)), "count": int(m.group(2) or 1), "pre": []}
+            left = cur["count"]
+            out.append(cur)
+        elif left and line[:1] in (" ", "-"):
+            cur["pre"].append(line[1:] + "\n")
+            left -= 1
+    return out
+
+
 def test_integration_patch_applies_to_the_reference(tmp_path):
-    """the patch against the upstream tree, where that is mounted (this container; not the GPU box)"""
+    """the patch against the upstream tree (andi 1.15), held by tests/golden/integration_patch_targets.json: the SHA-256 of
+    the upstream lines every hunk expects at its place.  Every hunk's own lines hash to that, so the patch meets upstream
+    exactly where it says; then it is applied without fuzz or offset to stand-ins of the files (the recorded lines at their
+    places, filler elsewhere)."""
+    import hashlib
+    import json
     import shutil
     import subprocess
-    ref = "/root/reference"
-    if not os.path.exists(os.path.join(ref, "src", "process.c")) or not shutil.which("patch"):
-        pytest.skip("upstream tree not mounted")
-    os.makedirs(tmp_path / "src")
-    shutil.copy(os.path.join(ref, "src", "process.c"), tmp_path / "src" / "process.c")
-    shutil.copy(os.path.join(ref, "configure.ac"), tmp_path / "configure.ac")
-    r = subprocess.run(["patch", "-p1", "-i", os.path.join(ROOT, "integration", "andi-hip.patch")], cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    assert shutil.which("patch"), "patch(1) is needed"
+    rec = json.load(open(os.path.join(GOLDEN, "integration_patch_targets.json")))
+    hunks = _patch_hunks(_patch_text())
+    assert [(h["file"], h["start"], h["count"]) for h in hunks] == [(h["file"], h["start"], h["count"]) for h in rec["hunks"]]
+    files = {}
+    for h, want in zip(hunks, rec["hunks"]):
+        assert hashlib.sha256("".join(h["pre"]).encode()).hexdigest() == want["sha256"], (h["file"], h["start"])
+        lines = files.setdefault(h["file"], ["/* upstream line %d */\n" % (k + 1) for k in range(rec["files"][h["file"]]["lines"])])
+        lines[h["start"] - 1:h["start"] - 1 + h["count"]] = h["pre"]
+    for name, lines in files.items():
+        os.makedirs(os.path.dirname(str(tmp_path / name)), exist_ok=True)
+        (tmp_path / name).write_text("".join(lines))
+    r = subprocess.run(["patch", "-p1", "--fuzz=0", "-i", os.path.join(ROOT, "integration", "andi-hip.patch")], cwd=tmp_path, capture_output=True, text=True)
+    assert r.returncode == 0 and "offset" not in r.stdout and "fuzz" not in r.stdout, r.stdout + r.stderr
     text = (tmp_path / "src" / "process.c").read_text()
     assert "distMatrixHIP(M, sequences, n);" in text and "HAVE_ANDI_HIP" in (tmp_path / "configure.ac").read_text()
 
