@@ -1,25 +1,21 @@
-// api.hip — the C-ABI of libandihip.so (include/andi_hip.h): device objects,
-// staging, kernel orchestration and the one-call replacement of
-// distMatrix/distMatrixLM (src/dist_hack.h:34-96).
+// api.hip — the C-ABI of libandihip.so (include/andi_hip.h): contexts, subjects, queries and the small calls.  The scan
+// call is scan_call.hip, the one-call replacement of distMatrix/distMatrixLM (src/dist_hack.h:34-96) seam.hip.
 #include <hip/hip_runtime.h>
-#include <rccl/rccl.h> // types only: librccl is loaded on demand (dlopen), see rccl() below
-#include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <sys/mman.h>
 #include <vector>
 
+#include "api_internal.h"
 #include "andi_dev.h"
 #include "andi_hip.h"
 #include "bootstrap.h"
@@ -76,203 +72,10 @@ const char *andi_knob_value(AndiKnob k) {
 }
 
 
-// segment length when the caller passes 0: short enough that one scan launch has
-// several hundred thousand chains, long enough that stitching stays a few per cent
-#define ANDI_MIN_SEGMENT 4096u
-#define ANDI_MAX_SEGMENT 65536u
-#define ANDI_TARGET_CHAINS (1u << 22) /* at most about this many chains per call (308 bytes of scratch each) */
-#define ANDI_MIN_CHAINS (1u << 19)    /* and long segments only while the call keeps this many */
-// per-pair segment lengths: classes seg/2, seg, 2 seg, 4 seg of the call's length, as long as the scratch they
-// need (whole wavefronts per pair) stays a fraction of the device's memory
-#define ANDI_ADAPTIVE_MAX_PAIRS (1u << 22)
-#define ANDI_ROUTE_MIN_NT (1u << 18) /* query symbols x subjects from which pass A of a call is routed per pair */
-#define ANDI_ROUTE_TINY_NT (1u << 25) /* ... below which it is not routed but takes pass A by wavefronts for every pair */
-#define ANDI_ROUTE_SMALL_NT (1ull << 30) /* ... below which pass A by wavefronts takes a millisecond or less: a few pairs left to the lane scan would take longer (k_pair_route) */
-// scratch per (subject, segment): three states, two count vectors, the marks, the exit position, a list slot, a published anchor
-#define ANDI_SLOT_BYTES (3 * sizeof(ChainState) + 2 * 16 * sizeof(uint32_t) + ANDI_COLD_MARKS * sizeof(ColdMark) + 4 + 8 + 8)
-
 static_assert(sizeof(andi_hip_model) == 68, "struct model must be 17 x u32 (src/model.h:52-57)");
 static_assert(sizeof(andi_hip_interval) == 16, "lcp_inter_t is 4 x int32 (src/esa.h:25-34)");
 static_assert(sizeof(ChainState) == 32, "ChainState is padded to 32 bytes");
 static_assert(sizeof(ColdMark) == 112, "ColdMark is a state, 16 counts and the first anchor");
-
-struct EventPair {
-	hipEvent_t a, b;
-	int kind; // 0 build, 1 scan, 2 stitch
-};
-
-struct andi_hip_ctx {
-	int device = 0;
-	size_t queries_hint = 0; // andi_hip_ctx_expect_queries
-	hipStream_t stream = nullptr;
-	hipStream_t side_stream = nullptr; // pass A's second kernel runs beside the first
-	hipEvent_t side_fork = nullptr, side_join = nullptr;
-	std::string err;
-	// scan scratch
-	void *scratch = nullptr;
-	size_t scratch_bytes = 0;
-	// descriptor staging (pinned host + device), guarded by desc_done
-	void *desc_host = nullptr;
-	void *desc_dev = nullptr;
-	size_t desc_bytes = 0;
-	hipEvent_t desc_done = nullptr;
-	unsigned long long *d_fixups = nullptr;
-	// batched index builds: items (pinned host + device), guarded by ib_done
-	void *ib_host = nullptr, *ib_dev = nullptr;
-	size_t ib_cap = 0;
-	hipEvent_t ib_done = nullptr;
-	// index builds queued since the last scan looked at their flags (pinned host words the build kernels write)
-	hipEvent_t built = nullptr;
-	bool builds_pending = false;
-	// device suffix sorter: workspace, two pinned ints
-	void *sa_ws = nullptr;
-	size_t sa_ws_bytes = 0;
-	int32_t *sa_pinned = nullptr;
-	int stream_prio = 0; // of stream and side_stream (host_pool: they go back there)
-	uint32_t *h_quad_waves = nullptr; // pinned: the length of k_lane_quad's list of a scan call
-	hipStream_t coop_stream = nullptr; // routed scan calls: pass A by wavefronts runs beside the lane scan's kernels
-	hipEvent_t coop_fork = nullptr, coop_join = nullptr, l2_fork = nullptr, l2_join = nullptr;
-	uint32_t *h_any_left = nullptr;    // pinned: [0] the wavefront kernel handed some pair back, [1 + k] the layout's counter restitch_count[k] (ANDI_LANE_WAVES: wavefronts of the lane layout, ...)
-	void *pool_scratch = nullptr;      // pass A by wavefronts with pooled walks (coop_pool.h): a scratch per resident wavefront
-	size_t pool_bytes = 0;
-	uint32_t pool_waves = 0;
-	bool pool_failed = false;          // its allocation failed once: not tried again by this context
-	void *scratch2 = nullptr;          // the second lane layout (those pairs), grown on demand
-	size_t scratch2_bytes = 0;
-	unsigned long long *d_route = nullptr; // routed scan calls: query nucleotides whose pass A ran by wavefronts / by lanes, pairs handed back (read with the timings)
-	std::vector<EventPair> pending;
-	andi_hip_timings acc{};
-};
-
-struct andi_hip_esa {
-	uint8_t *S = nullptr;
-	int32_t *SA = nullptr, *LCP = nullptr, *CLD = nullptr;
-	uint8_t *FVC = nullptr;
-	int4 *tab = nullptr;
-	int32_t *min_scratch = nullptr;
-	uint2 *deep = nullptr;
-	uint8_t *Nraw = nullptr;              // 4-bit symbols for the lane scan: N0 and N1 with their padding
-	uint8_t *N0 = nullptr, *N1 = nullptr;
-	uint32_t *Praw = nullptr, *P = nullptr; // the text bit-sliced (EsaDev.P; packed from N0 when a scan call wants it), a block of padding in front
-	uint32_t *rec = nullptr;    // the suffixes' records in suffix-array order, left by the device sorter (sa_device.hip) for the index build
-	bool rec_valid = false;
-	uint16_t *rec2 = nullptr;   // ... and the symbols behind their first deepK (same validity)
-	int32_t *flags = nullptr;   // device, 4 ints
-	int32_t *h_flags = nullptr; // the same 4 ints as the host sees them (flags live in pinned host memory)
-	int32_t deepK = 0;
-	int32_t deepK_cap = 0; // the depth the table was allocated for
-	int32_t n = 0;
-	int32_t thr = 0;
-	size_t cap = 0;     // characters the buffers were sized for (>= n)
-	size_t ref_cap = 0; // same for the reference arrays
-	bool ref_built = false;   // LCP, CLD, FVC, tab valid
-	bool index_built = false; // deep, flags valid
-	int deep_ext = 0;         // the form of the table's entries of K-mers that occur once (andi_dev.h: 0 plain, 1 extended, 2 short extended)
-	size_t bytes = 0;
-};
-
-struct andi_hip_queries {
-	uint8_t *pool = nullptr;
-	uint8_t *nib = nullptr;       // the pool as 4-bit symbols
-	uint32_t *planes = nullptr;   // ... bit-sliced (EsaDev.P)
-	int32_t *h_foreign = nullptr; // pinned: set if the pool holds bytes outside the alphabet
-	uint64_t *d_off = nullptr;
-	uint32_t *d_len = nullptr;
-	uint32_t *d_sep = nullptr;    // contig separators of every sequence (k_sep_counts: for the routing of the scan)
-	std::vector<uint64_t> off;
-	std::vector<uint32_t> len;
-	size_t nq = 0;
-	uint64_t total_nt = 0;
-	// segmentation cache
-	uint32_t seg = 0;
-	uint32_t *d_qseg_start = nullptr;
-	uint32_t *d_seg2query = nullptr;
-	uint32_t total_segs = 0;
-	// a second one: the long segments of pass A by wavefronts (scan_coop.hip), kept beside the call's own so that a
-	// call that falls back to the lane scan does not cut the queries anew every time
-	uint32_t c_seg = 0;
-	uint32_t *c_qseg_start = nullptr;
-	uint32_t *c_seg2query = nullptr;
-	uint32_t c_total_segs = 0;
-};
-
-namespace {
-
-void set_err(char *buf, size_t len, const char *fmt, ...) {
-	if (!buf || !len) return;
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(buf, len, fmt, ap);
-	va_end(ap);
-}
-
-int fail(andi_hip_ctx *ctx, const char *what, hipError_t e) {
-	if (ctx) {
-		ctx->err = std::string(what) + ": " + hipGetErrorString(e);
-	}
-	return 1;
-}
-
-#define HIP_TRY(ctx, call)                                                                         \
-	do {                                                                                           \
-		hipError_t e__ = (call);                                                                   \
-		if (e__ != hipSuccess) return fail((ctx), #call, e__);                                     \
-	} while (0)
-
-template <typename T>
-hipError_t dmalloc(T **p, size_t count) {
-	return andi_arena::dev_malloc((void **)p, count * sizeof(T)); // (out of large chunks: dev_arena.h)
-}
-
-void resolve_events(andi_hip_ctx *ctx) {
-	for (auto &ev : ctx->pending) {
-		float ms = 0.f;
-		if (hipEventSynchronize(ev.b) == hipSuccess && hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
-			if (ev.kind == 0) {
-				ctx->acc.build_ms += ms;
-				ctx->acc.build_launches++;
-			} else if (ev.kind == 1) {
-				ctx->acc.scan_ms += ms;
-				ctx->acc.scan_launches++;
-			} else {
-				ctx->acc.stitch_ms += ms;
-				ctx->acc.stitch_launches++;
-			}
-		}
-		(void)hipEventDestroy(ev.a);
-		(void)hipEventDestroy(ev.b);
-	}
-	ctx->pending.clear();
-}
-
-struct Timed {
-	andi_hip_ctx *ctx;
-	EventPair ev;
-	bool ok;
-	Timed(andi_hip_ctx *c, int kind) : ctx(c), ok(false) {
-		ev.kind = kind;
-		if (hipEventCreate(&ev.a) != hipSuccess) return;
-		if (hipEventCreate(&ev.b) != hipSuccess) {
-			(void)hipEventDestroy(ev.a);
-			return;
-		}
-		ok = hipEventRecord(ev.a, c->stream) == hipSuccess;
-	}
-	void stop() {
-		if (!ok) return;
-		(void)hipEventRecord(ev.b, ctx->stream);
-		ctx->pending.push_back(ev);
-		ok = false;
-		if (ctx->pending.size() > 256) resolve_events(ctx);
-	}
-	~Timed() { // an error exit before stop(): the events go with the timer
-		if (!ok) return;
-		(void)hipEventDestroy(ev.a);
-		(void)hipEventDestroy(ev.b);
-	}
-	Timed(const Timed &) = delete;
-	Timed &operator=(const Timed &) = delete;
-};
 
 EsaDev esa_view(const andi_hip_esa *e, int mode) {
 	EsaDev v;
@@ -299,6 +102,8 @@ int pick_deep_k(size_t n, size_t queries) {
 	return K;
 }
 
+namespace {
+
 EsaBuildArgs build_args(const andi_hip_esa *e) {
 	EsaBuildArgs a;
 	a.S = e->S, a.SA = e->SA, a.LCP = e->LCP, a.CLD = e->CLD, a.FVC = e->FVC, a.tab = e->tab;
@@ -312,12 +117,6 @@ EsaBuildArgs build_args(const andi_hip_esa *e) {
 }
 
 } // namespace
-
-extern "C" {
-
-int andi_hip_abi_version(void) {
-	return ANDI_HIP_ABI_VERSION;
-}
 
 // Streams and the seam's pinned upload buffer are kept from one call to the next (like the arena's chunks: andi_hip_trim
 // gives them back): creating a stream takes 3 ms on this runtime -- nine per call of andi_hip_dist_matrix, 30 of a warm
@@ -356,7 +155,7 @@ static State &state() {
 }
 constexpr size_t PINNED_KEEP = (size_t)256 << 20; // bytes of pinned buffers kept at most
 
-static hipError_t stream_get(hipStream_t *out, int device, int prio) {
+hipError_t stream_get(hipStream_t *out, int device, int prio) {
 	{
 		std::lock_guard<std::mutex> lk(state().mu);
 		for (size_t i = 0; i < state().streams.size(); ++i)
@@ -368,12 +167,12 @@ static hipError_t stream_get(hipStream_t *out, int device, int prio) {
 	}
 	return hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio);
 }
-static void stream_put(hipStream_t s, int device, int prio) { // (idle: the caller has synchronised it)
+void stream_put(hipStream_t s, int device, int prio) { // (idle: the caller has synchronised it)
 	if (!s) return;
 	std::lock_guard<std::mutex> lk(state().mu);
 	state().streams.push_back({device, prio, s});
 }
-static hipError_t pinned_get(void **out, size_t bytes) {
+hipError_t pinned_get(void **out, size_t bytes) {
 	{
 		std::lock_guard<std::mutex> lk(state().mu);
 		size_t best = state().pinned.size();
@@ -387,7 +186,7 @@ static hipError_t pinned_get(void **out, size_t bytes) {
 	}
 	return hipHostMalloc(out, bytes, hipHostMallocDefault);
 }
-static void pinned_put(void *p, size_t bytes) {
+void pinned_put(void *p, size_t bytes) {
 	if (!p) return;
 	{
 		std::lock_guard<std::mutex> lk(state().mu);
@@ -401,7 +200,7 @@ static void pinned_put(void *p, size_t bytes) {
 	(void)hipHostFree(p);
 }
 constexpr size_t WORD_BYTES = 256, SLAB_BYTES = 65536;
-static void *word_get() { // 256 zeroed bytes of pinned host memory (device-visible: unified addressing), 256-byte aligned
+void *word_get() { // 256 zeroed bytes of pinned host memory (device-visible: unified addressing), 256-byte aligned
 	std::lock_guard<std::mutex> lk(state().mu);
 	State &S = state();
 	if (S.free_words.empty()) {
@@ -419,7 +218,7 @@ static void *word_get() { // 256 zeroed bytes of pinned host memory (device-visi
 	memset(p, 0, WORD_BYTES);
 	return p;
 }
-static void word_put(void *p) {
+void word_put(void *p) {
 	if (!p) return;
 	std::lock_guard<std::mutex> lk(state().mu);
 	state().free_words.push_back(p);
@@ -428,7 +227,7 @@ static void word_put(void *p) {
 
 // the pooled wavefront kernel's scratch: one per device is kept from context to context (a context of the seam lives for one
 // call: 0.8 GB of hipMalloc + hipFree per call and device otherwise); andi_hip_trim returns it
-static void *scratch_get(int device, size_t bytes) {
+void *scratch_get(int device, size_t bytes) {
 	{
 		std::lock_guard<std::mutex> lk(state().mu);
 		auto &v = state().scratch;
@@ -446,7 +245,7 @@ static void *scratch_get(int device, size_t bytes) {
 	}
 	return p;
 }
-static void scratch_put(int device, void *p, size_t bytes) { // (idle: the caller has waited for the kernels that used it)
+void scratch_put(int device, void *p, size_t bytes) { // (idle: the caller has waited for the kernels that used it)
 	if (!p) return;
 	{
 		std::lock_guard<std::mutex> lk(state().mu);
@@ -485,6 +284,10 @@ static size_t trim() { // (the caller restores the current device); returns the 
 	return freed;
 }
 } // namespace host_pool
+
+int andi_hip_abi_version(void) {
+	return ANDI_HIP_ABI_VERSION;
+}
 
 size_t andi_hip_trim(void) {
 	if (!andi_arena::any_chunks() && !host_pool::any()) return 0; // (a process that never used the library's device memory: no HIP call at all)
@@ -526,7 +329,7 @@ int andi_hip_device_count(void) {
 
 // high_priority: the context's streams are served before those of other contexts on the device (the staging stage of
 // andi_hip_dist_matrix: its short kernels must not queue behind the workgroups of a scan that fills the device)
-static int ctx_create(andi_hip_ctx **out, int device, char *errbuf, size_t errlen, bool high_priority) {
+int ctx_create(andi_hip_ctx **out, int device, char *errbuf, size_t errlen, bool high_priority) {
 	if (!out) return 1;
 	*out = nullptr;
 	int count = 0;
@@ -664,7 +467,7 @@ int andi_hip_copy_to_host(andi_hip_ctx *ctx, void *dst, const void *src, size_t 
 
 // ------------------------------------------------------------------ subjects
 // Allocate a subject slot able to hold an RS of up to `cap` characters.
-static int esa_reserve(andi_hip_ctx *ctx, size_t cap, andi_hip_esa **out) {
+int esa_reserve(andi_hip_ctx *ctx, size_t cap, andi_hip_esa **out) {
 	auto *e = new andi_hip_esa;
 	e->cap = cap;
 	hipError_t err = hipSuccess;
@@ -708,8 +511,8 @@ static int esa_reserve(andi_hip_ctx *ctx, size_t cap, andi_hip_esa **out) {
 
 // Put a (new) subject into a slot: uploads only.  The caller may release RS/SA
 // as soon as this returns.
-static int esa_upload(andi_hip_ctx *ctx, andi_hip_esa *e, const char *RS, const int32_t *SA, size_t n,
-					  size_t threshold, hipEvent_t done = nullptr) { // done: do not wait -- the event says when RS (and SA) may be reused
+int esa_upload(andi_hip_ctx *ctx, andi_hip_esa *e, const char *RS, const int32_t *SA, size_t n,
+					  size_t threshold, hipEvent_t done) {
 	if (n > e->cap) {
 		ctx->err = "subject does not fit its slot";
 		return 1;
@@ -734,7 +537,7 @@ static int esa_upload(andi_hip_ctx *ctx, andi_hip_esa *e, const char *RS, const 
 // seq_subject_init (src/sequence.c:210-219) for a sequence that is already resident as a query: RS is written into the slot
 // by a kernel from the query pool (esa_build.hip: k_rs_from_query) -- no host pass over the sequence, no upload.  The
 // threshold is the caller's (min_anchor_length on the host, from the device's G+C count: queries_gc_counts).
-static int esa_from_query(andi_hip_ctx *ctx, andi_hip_esa *e, const andi_hip_queries *Q, size_t i, size_t threshold) {
+int esa_from_query(andi_hip_ctx *ctx, andi_hip_esa *e, const andi_hip_queries *Q, size_t i, size_t threshold) {
 	const size_t len = Q->len[i], n = 2 * len + 1;
 	if (n > e->cap) {
 		ctx->err = "subject does not fit its slot";
@@ -753,7 +556,7 @@ static int esa_from_query(andi_hip_ctx *ctx, andi_hip_esa *e, const andi_hip_que
 }
 
 // calc_gc's numerators (src/sequence.c:197-208) of all staged sequences, counted where they lie
-static int queries_gc_counts(andi_hip_ctx *ctx, const andi_hip_queries *Q, std::vector<unsigned long long> &out) {
+int queries_gc_counts(andi_hip_ctx *ctx, const andi_hip_queries *Q, std::vector<unsigned long long> &out) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	unsigned long long *d = nullptr;
 	HIP_TRY(ctx, dmalloc(&d, Q->nq));
@@ -770,7 +573,7 @@ static int queries_gc_counts(andi_hip_ctx *ctx, const andi_hip_queries *Q, std::
 }
 
 // esa_init_SA (src/esa.c:294-304) on the device: the text is in the slot, the suffix array is built there
-static int esa_sort_suffixes(andi_hip_ctx *ctx, andi_hip_esa *e) {
+int esa_sort_suffixes(andi_hip_ctx *ctx, andi_hip_esa *e) {
 	const size_t need = andi_sa_device_workspace(e->n);
 	if (ctx->sa_ws_bytes < need) {
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1175,26 +978,8 @@ extern "C" int andi_hip_pack_symbols(const unsigned char *src, size_t len, unsig
 	return (bad & 0x80u) ? 1 : 0;
 }
 
-// The seam's queries, packed ONCE on the host (round 4): every device uploads the 4-bit pool -- a quarter of what the
-// byte pool and its packed copy were, from one host copy shared by the device threads -- and unpacks the bytes the rare
-// byte-wise paths read (k_unpack_symbols).  C4's 6.5 GB of queries took 0.35 s per device as bytes from pageable memory.
-struct PackedQueries {
-	std::vector<uint64_t> off;
-	std::vector<uint32_t> len;
-	uint64_t total_nt = 0;
-	size_t pool_bytes = 0;
-	uint8_t *nib = nullptr; // pool_bytes / 2 bytes: the pool as the device's pack kernel would leave it
-	int foreign = 0;        // a byte outside the alphabet (the scan refuses the queries then)
-	std::string err;
-	std::atomic<int> users{0}; // devices that have not staged yet: the last one lets the host copy go (gigabytes: not at the call's end)
-	void release() {
-		free(nib);
-		nib = nullptr;
-	}
-	~PackedQueries() { release(); }
-};
 
-static int pack_queries_host(const andi_hip_seq *seqs, size_t n, int threads, PackedQueries &P) {
+int pack_queries_host(const andi_hip_seq *seqs, size_t n, int threads, PackedQueries &P) {
 	if (!seqs || n == 0 || n >= (size_t)UINT32_MAX) {
 		P.err = "andi_hip_queries_stage: bad arguments";
 		return 1;
@@ -1245,7 +1030,7 @@ static int pack_queries_host(const andi_hip_seq *seqs, size_t n, int threads, Pa
 	return 0;
 }
 
-static int queries_stage_packed(andi_hip_ctx *ctx, const PackedQueries &P, andi_hip_queries **out) {
+int queries_stage_packed(andi_hip_ctx *ctx, const PackedQueries &P, andi_hip_queries **out) {
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	auto *q = new andi_hip_queries;
 	const size_t n = P.off.size();
@@ -1276,37 +1061,6 @@ static int queries_stage_packed(andi_hip_ctx *ctx, const PackedQueries &P, andi_
 	return 0;
 }
 
-static int ensure_segmentation(andi_hip_ctx *ctx, andi_hip_queries *q, uint32_t seg, bool coop = false) {
-	uint32_t &have = coop ? q->c_seg : q->seg, &total_out = coop ? q->c_total_segs : q->total_segs;
-	uint32_t *&d_start = coop ? q->c_qseg_start : q->d_qseg_start, *&d_s2q = coop ? q->c_seg2query : q->d_seg2query;
-	if (have == seg && d_start) return 0;
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-	(void)andi_arena::dev_free(d_start);
-	(void)andi_arena::dev_free(d_s2q);
-	d_start = d_s2q = nullptr;
-	std::vector<uint32_t> start(q->nq + 1);
-	uint64_t total = 0;
-	for (size_t i = 0; i < q->nq; ++i) {
-		start[i] = (uint32_t)total;
-		total += (q->len[i] + (uint64_t)seg - 1) / seg;
-		if (total >= UINT32_MAX) {
-			ctx->err = "too many scan segments; raise opts.segment";
-			return 1;
-		}
-	}
-	start[q->nq] = (uint32_t)total;
-	std::vector<uint32_t> s2q((size_t)total);
-	for (size_t i = 0; i < q->nq; ++i)
-		for (uint32_t w = start[i]; w < start[i + 1]; ++w) s2q[w] = (uint32_t)i;
-	HIP_TRY(ctx, dmalloc(&d_start, q->nq + 1));
-	HIP_TRY(ctx, dmalloc(&d_s2q, (size_t)total));
-	HIP_TRY(ctx, hipMemcpy(d_start, start.data(), (q->nq + 1) * 4, hipMemcpyHostToDevice));
-	HIP_TRY(ctx, hipMemcpy(d_s2q, s2q.data(), (size_t)total * 4, hipMemcpyHostToDevice));
-	have = seg;
-	total_out = (uint32_t)total;
-	return 0;
-}
-
 int andi_hip_match_positions(andi_hip_ctx *ctx, const andi_hip_esa *esa, const andi_hip_queries *q,
 							 size_t qidx, size_t first, size_t count, int cached,
 							 andi_hip_interval *out_host) {
@@ -1334,433 +1088,8 @@ int andi_hip_match_positions(andi_hip_ctx *ctx, const andi_hip_esa *esa, const a
 	return 0;
 }
 
-// ------------------------------------------------------------------ scan
-int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const int64_t *self,
-					   size_t nsub, const andi_hip_queries *q_const, int model, uint32_t segment,
-					   andi_hip_model *M_dev) {
-	if (!ctx || !subjects || !q_const || !M_dev || nsub == 0 || nsub > 65535) {
-		if (ctx) ctx->err = "andi_hip_scan_rows: bad arguments";
-		return 1;
-	}
-	if (model < ANDI_M_RAW || model > ANDI_M_ANI) {
-		ctx->err = "andi_hip_scan_rows: unknown model";
-		return 1;
-	}
-	auto *q = const_cast<andi_hip_queries *>(q_const);
-	if (*q->h_foreign) { // the reference's reader never produces that (src/sequence.c:260-282)
-		ctx->err = "andi_hip_scan_rows: a query holds a byte outside {A,C,G,T,!}";
-		return 1;
-	}
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// the streams only scans use (a context that stages or uploads never asks for them: a stream costs 3 ms to create)
-	if (!ctx->side_stream) HIP_TRY(ctx, host_pool::stream_get(&ctx->side_stream, ctx->device, ctx->stream_prio));
-	if (!ctx->coop_stream) HIP_TRY(ctx, host_pool::stream_get(&ctx->coop_stream, ctx->device, 0));
-	// segment == 0: the engine chooses.  With the lane scan and a moderate number of pairs
-	// the segment length is chosen per pair (scan_lane.hip: k_pair_estimate); otherwise one
-	// length for the call.
-	// Pass A with one wavefront per chain (scan_coop.hip) for the models that split an anchor's length evenly and
-	// thresholds a 32-symbol window can decide.  ANDI_COOP=n: the call's pass A, one (long) segment length for the call.
-	// Unset: large calls are ROUTED PER PAIR (scan.h) -- the pairs whose sampled matches suit that kernel take it, on a
-	// segmentation of its own; the others, and the pairs it hands back, take the lane scan; passes B and C run per layout.
-	const int coop_mode = andi_coop_enabled();
-	int coop_ok = coop_mode != 0 && !andi_knob(KNOB_FORCE_REFERENCE);
-	for (size_t s = 0; s < nsub && coop_ok; ++s)
-		if (!subjects[s] || subjects[s]->thr < 2 || subjects[s]->thr > 30) coop_ok = 0;
-	const uint64_t call_nt = q->total_nt * (uint64_t)nsub;
-	// TINY calls (less than two rounds of wavefronts on 2048-symbol segments): that kernel for every pair, without the
-	// sampling -- whatever a pair is like, a wavefront's chain over 2048 symbols is no longer than a lane's over 4096, and
-	// the device has the wavefronts to spare (structured genomes 3 x 1 Mbp ... 5 x 1.3 Mbp: 2.1 ... 3.3 ms by wavefronts,
-	// 2.65 ... 3.4 by lanes; clean ones 3 x 1 Mbp: 0.34 against 0.54 routed, 0.96 by lanes)
-	uint64_t tiny_nt = ANDI_ROUTE_TINY_NT;
-	if (const char *rt = andi_knob(KNOB_ROUTE_TINY)) // (tests, experiments: log2 of that size; 1: no call is tiny, small ones are routed)
-		if (atoi(rt) > 0 && atoi(rt) < 63) tiny_nt = 1ull << atoi(rt);
-	bool tiny = coop_ok && coop_mode < 0 && segment == 0 && call_nt >= ANDI_ROUTE_MIN_NT && call_nt < tiny_nt &&
-				!andi_knob(KNOB_UNIFORM_SEGMENTS) && !andi_knob(KNOB_FORCE_ADAPTIVE);
-	// A wavefront needs far fewer chains in flight than a lane, and every segment costs it a cold start of a dozen
-	// dependent round trips: segments as long as leave the device four rounds of wavefronts (24576), 32768 ... 524288
-	// symbols (measured: bench set 5.57 / 5.39 / 5.31 / 5.34 ms at 32768 / 65536 / 131072 / 262144, C4 shape 38.6 / 33.5 /
-	// 32.6 / 32.6 / 35.4 / 44.0 ms at 32768 / 131072 / 262144 / 524288 / 2^20 / 2^21 -- whole queries: pairs differ too much)
-	// Small calls: shorter segments still, as long as the device has one round of wavefronts (2048 symbols at least) --
-	// 3 x 1 Mbp (BASELINE's configs[0]): pass A 0.10 ms by wavefronts against 0.66 ms by lanes; 100 x 30 kbp 0.94 against
-	// 2.35 ms per call (profiles/r05_small_calls.txt).
-	uint32_t coop_seg = 524288;
-	while (coop_seg > 32768 && q->total_nt * (uint64_t)nsub / coop_seg < 24576) coop_seg /= 2;
-	while (coop_seg > 2048 && q->total_nt * (uint64_t)nsub / coop_seg < 12000u) coop_seg /= 2; // (8 x 1 Mbp: 0.38 ms at 4096 -- 15 600 wavefronts --, 0.46 at 2048; 12 x 1 Mbp: 0.65 at 8192 -- 17 600 --, 0.74 at 4096)
-	if (const char *cs = andi_knob(KNOB_COOP_SEG)) // experiments
-		if (atoi(cs) >= 64) coop_seg = (uint32_t)atoi(cs);
-	// (the smallest calls -- a few launches' worth of work -- keep the lane scan: routing costs them the sampling kernel
-	// and two looks of the host at the device)
-	bool routed = coop_ok && coop_mode < 0 && segment == 0 && call_nt >= ANDI_ROUTE_MIN_NT &&
-				  nsub * q->nq <= ANDI_ADAPTIVE_MAX_PAIRS && !andi_knob(KNOB_UNIFORM_SEGMENTS) && !andi_knob(KNOB_FORCE_ADAPTIVE);
-	if (routed || tiny) { // (queries shorter than the wavefront kernel takes -- k_pair_estimate -- are the lane scan's: where they are most of the call, all of it)
-		uint64_t cand_nt = 0;
-		for (size_t i = 0; i < q->nq; ++i)
-			if (q->len[i] >= std::min(coop_seg, ANDI_ROUTE_MIN_QLEN)) cand_nt += q->len[i];
-		if (2 * cand_nt < q->total_nt) routed = tiny = false;
-	}
-	if (tiny) routed = false;
-	const int coop = coop_ok && (coop_mode > 0 || tiny);
-	const bool want_adaptive = !coop && segment == 0 && nsub * q->nq <= ANDI_ADAPTIVE_MAX_PAIRS &&
-							   !andi_knob(KNOB_UNIFORM_SEGMENTS);
-	if (segment == 0 && coop) segment = coop_seg;
-	if (segment == 0) {
-		uint64_t nt = q->total_nt * (uint64_t)nsub;
-		segment = ANDI_MIN_SEGMENT;
-		while (segment < ANDI_MAX_SEGMENT && nt / segment > ANDI_TARGET_CHAINS) segment *= 2;
-	}
-	if (ensure_segmentation(ctx, q, segment)) return 1;
-
-	// descriptors: [EsaDev x nsub][int64 x nsub]
-	const size_t desc_need = nsub * (sizeof(EsaDev) + sizeof(int64_t));
-	if (ctx->desc_bytes < desc_need) {
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->desc_dev) (void)andi_arena::dev_free(ctx->desc_dev);
-		if (ctx->desc_host) host_pool::pinned_put(ctx->desc_host, ctx->desc_bytes);
-		ctx->desc_dev = ctx->desc_host = nullptr;
-		ctx->desc_bytes = 0;
-		const size_t desc_cap = std::max<size_t>(desc_need, 4096); // (one size for small calls: the pool of pinned buffers hands it back)
-		HIP_TRY(ctx, andi_arena::dev_malloc(&ctx->desc_dev, desc_cap));
-		HIP_TRY(ctx, host_pool::pinned_get(&ctx->desc_host, desc_cap));
-		ctx->desc_bytes = desc_cap;
-	} else {
-		HIP_TRY(ctx, hipEventSynchronize(ctx->desc_done)); // previous upload consumed
-	}
-	auto *h_esa = (EsaDev *)ctx->desc_host;
-	auto *h_self = (int64_t *)(h_esa + nsub);
-	uint64_t pairs = 0, nt = 0;
-	int any_reference = 0;
-	// the index builds must have finished: their flags decide which walk is exact.  (Only the builds this context
-	// has queued since its last scan are waited for -- not whatever else is on the stream; subjects built by another
-	// context are the caller's to have synchronised, as before.)
-	if (ctx->builds_pending) {
-		HIP_TRY(ctx, hipEventSynchronize(ctx->built));
-		ctx->builds_pending = false;
-	}
-	for (size_t s = 0; s < nsub; ++s) {
-		andi_hip_esa *e = subjects[s];
-		if (!e || (!e->index_built && !e->ref_built)) {
-			ctx->err = "andi_hip_scan_rows: subject index not built";
-			return 1;
-		}
-		int mode = ANDI_MODE_PROBE;
-		if (!e->index_built || e->h_flags[0] != 0 || andi_knob(KNOB_FORCE_REFERENCE)) {
-			// a 10-mer table entry may span a separator: only the reference's
-			// own walk reproduces get_match_cached there
-			mode = ANDI_MODE_REFERENCE;
-			if (!e->ref_built && andi_hip_esa_build(ctx, e)) return 1;
-			ctx->acc.reference_subjects++;
-			any_reference = 1;
-		}
-		if (e->index_built && e->h_flags[1]) {
-			ctx->err = "andi_hip_scan_rows: a subject holds a byte outside {A,C,G,T,!,;,#}";
-			return 1;
-		}
-		h_esa[s] = esa_view(e, mode);
-		h_self[s] = self ? self[s] : -1;
-		bool has_self = h_self[s] >= 0 && (size_t)h_self[s] < q->nq;
-		pairs += q->nq - (has_self ? 1 : 0);
-		nt += q->total_nt - (has_self ? q->len[(size_t)h_self[s]] : 0);
-	}
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->desc_dev, ctx->desc_host, desc_need, hipMemcpyHostToDevice,
-								ctx->stream));
-	HIP_TRY(ctx, hipEventRecord(ctx->desc_done, ctx->stream));
-
-	if (any_reference) routed = false;
-	// scratch: per (subject, segment) two states and two count vectors
-	bool adaptive = want_adaptive && !any_reference;
-	uint32_t seg0 = segment / 2; // classes: 1/2, 1, 2, 4 times the call's segment length
-	if (const char *e0 = andi_knob(KNOB_SEG0)) { // experiments: shortest segment of the adaptive classes
-		if (atoi(e0) >= 64) seg0 = (uint32_t)atoi(e0);
-	}
-	uint64_t max_waves = 0; // adaptive: wavefronts (64 segments of one pair) if every pair had the shortest segments
-	if (adaptive) {
-		for (size_t s = 0; s < nsub; ++s)
-			for (size_t i = 0; i < q->nq; ++i) {
-				if (h_self[s] == (int64_t)i) continue;
-				max_waves += ((q->len[i] + (uint64_t)seg0 - 1) / seg0 + 63) / 64;
-			}
-		// a pair occupies whole wavefronts: with queries of a few segments most lanes would idle, and the
-		// scratch must stay a fraction of the device's memory -- one segment length for the call then
-		uint64_t used = 0;
-		for (size_t i = 0; i < q->nq; ++i) used += (q->len[i] + (uint64_t)seg0 - 1) / seg0;
-		used *= nsub;
-		size_t free_b = 0, total_b = 0;
-		// (a routed call may need a second lane layout as large as the first for the pairs handed back: counted here, so that
-		// a call that fits keeps fitting when that happens)
-		const size_t want_b = (size_t)64 * max_waves * ANDI_SLOT_BYTES * (routed ? 2 : 1);
-		const bool fits = max_waves < (1u << 26) && // (the device is asked only when the scratch would have to grow)
-						  (want_b <= ctx->scratch_bytes || hipMemGetInfo(&free_b, &total_b) != hipSuccess || want_b < free_b / 2 + ctx->scratch_bytes);
-		if (!fits || (10 * used < 7 * 64 * max_waves && !andi_knob(KNOB_FORCE_ADAPTIVE))) adaptive = false, max_waves = 0;
-	}
-	const size_t pairs_all = nsub * q->nq;
-	if (routed && ensure_segmentation(ctx, q, coop_seg, true)) return 1;
-	const size_t slots = adaptive ? (size_t)64 * max_waves : nsub * (size_t)q->total_segs;
-	const size_t slots2 = routed ? nsub * (size_t)q->c_total_segs : 0; // (the wavefront kernel's layout, beside the lane scan's)
-	const size_t need = (slots + slots2) * ANDI_SLOT_BYTES + 256 +
-						(adaptive || routed ? pairs_all * 9 + 64 + (pairs_all / 1024 + 2) * 4 + 16 + nsub * 8 + 32 : 0);
-	if (ctx->scratch_bytes < need) {
-		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		if (ctx->scratch) (void)andi_arena::dev_free(ctx->scratch);
-		ctx->scratch = nullptr;
-		ctx->scratch_bytes = 0;
-		HIP_TRY(ctx, andi_arena::dev_malloc(&ctx->scratch, need));
-		ctx->scratch_bytes = need;
-	}
-
-	ScanArgs a;
-	a.subjects = (const EsaDev *)ctx->desc_dev;
-	a.self = (const int64_t *)((const EsaDev *)ctx->desc_dev + nsub);
-	a.nsub = (uint32_t)nsub;
-	a.qpool = q->pool, a.qnib = q->nib, a.qplanes = q->planes, a.qoff = q->d_off, a.qlen = q->d_len, a.qsep = q->d_sep, a.nq = (uint32_t)q->nq;
-	a.qseg_start = q->d_qseg_start, a.seg2query = q->d_seg2query;
-	a.total_segs = q->total_segs, a.seg = segment;
-	char *p = (char *)ctx->scratch;
-	auto carve = [&p](ScanArgs &x, size_t n) { // the per-slot arrays of a layout of n slots
-		x.cold_exit = (ChainState *)p;
-		p += n * sizeof(ChainState);
-		x.true_exit = (ChainState *)p;
-		p += n * sizeof(ChainState);
-		x.used_entry = (ChainState *)p;
-		p += n * sizeof(ChainState);
-		x.cold_counts = (uint32_t *)p;
-		p += n * 16 * sizeof(uint32_t);
-		x.owned = (uint32_t *)p;
-		p += n * 16 * sizeof(uint32_t);
-		x.marks = (ColdMark *)p;
-		p += n * ANDI_COLD_MARKS * sizeof(ColdMark);
-		x.exit_p = (uint32_t *)p;
-		p += n * sizeof(uint32_t);
-		p = (char *)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-		x.restitch_count = (uint32_t *)p;
-		x.restitch_round = 0;
-		x.defer_count = x.restitch_count + 8;
-		p += 64;
-		x.defer_list = (unsigned long long *)p;
-		p += n * sizeof(unsigned long long);
-		x.first_pub = (unsigned long long *)p; // (k_lane_quad, per-pair segment lengths only)
-		x.stretch_bad = (uint8_t *)p;          // (pass B: a byte per slot, while first_pub is idle)
-		p += n * sizeof(unsigned long long);
-	};
-	carve(a, slots);
-	a.adaptive = adaptive ? 1 : 0;
-	a.seg0 = seg0, a.max_waves = (uint32_t)max_waves;
-	a.max_class = 0; // long segments must not leave the device short of chains
-	while (a.max_class < 3 && nt / ((uint64_t)seg0 << (a.max_class + 1)) >= ANDI_MIN_CHAINS) a.max_class++;
-	a.pair_waves = (uint32_t *)p;
-	a.pair_wave0 = a.pair_waves + pairs_all;
-	a.pair_bsum = a.pair_wave0 + pairs_all + 1;
-	a.pair_class = (uint8_t *)(a.pair_bsum + pairs_all / 1024 + 2);
-	a.sub_cost = nullptr, a.sub_order = nullptr;
-	if (routed) { // (the order in which pass A by wavefronts takes the subjects: scan.h)
-		a.sub_cost = (float *)(((uintptr_t)(a.pair_class + pairs_all) + 15) & ~(uintptr_t)15);
-		a.sub_order = (uint32_t *)(a.sub_cost + nsub);
-	}
-	{
-		const char *f = andi_knob(KNOB_SEG_FACTOR);
-		a.seg_factor = f && atoi(f) > 0 ? (uint32_t)atoi(f) : 16u; // measured best of 8/16/32 with seg0 = 2048
-	}
-	a.M = M_dev;
-	a.fixups = ctx->d_fixups;
-	a.any_reference = any_reference;
-	{
-		const char *qm = andi_knob(KNOB_QUAD_MATCH); // experiments: mean match length from which a pair goes to k_lane_quad (0: all, -1: none)
-		a.quad_min_match = qm ? (uint32_t)atoi(qm) : 128u;
-		a.quad_listed = 0;
-		a.side_stream = ctx->side_stream, a.side_fork = ctx->side_fork, a.side_join = ctx->side_join;
-		a.h_quad_waves = ctx->h_quad_waves;
-		const char *kn = andi_knob(KNOB_KNOCK);
-		a.knock = kn ? (uint32_t)atoi(kn) : 0u;
-	}
-	a.coop = coop && !a.adaptive;
-	a.pool_scratch = nullptr, a.pool_ticket = nullptr, a.pool_waves = 0, a.pool_bytes = 0;
-	a.pool_maxchunks = a.pool_hc = 0, a.pool_first = 0, a.pool_use = 0;
-	{
-		const char *pm = andi_knob(KNOB_POOL_MATCH); // (experiments: mean sampled match from which a routed pair's wavefront kernel is k_pool_cold)
-		a.pool_match = pm && atoi(pm) >= 0 ? (uint32_t)atoi(pm) : 48u;
-	}
-	// Pooled walks (k_pool_cold): the scratch of the resident wavefronts -- 0.8 GB on a 256-CU part, a mapping of its own -- is
-	// taken only by a call that is going to run that kernel (andi_coop_wants_pool: known behind the look at the layout in a
-	// routed call), from the device's idle one if a destroyed context left it (host_pool), once per context; a context whose
-	// attempt failed does not try again (the windows then stay in LDS: k_coop_cold).
-	auto give_pool_scratch = [&](ScanArgs &x) {
-		if (!andi_coop_wants_pool(x)) return;
-		if (!ctx->pool_scratch && !ctx->pool_failed) {
-			uint32_t waves = 0;
-			const size_t bytes = andi_pool_scratch_bytes(ctx->device, &waves);
-			if (bytes && (ctx->pool_scratch = host_pool::scratch_get(ctx->device, bytes)))
-				ctx->pool_waves = waves, ctx->pool_bytes = bytes - 4096;
-			else
-				ctx->pool_failed = true;
-		}
-		if (!ctx->pool_scratch) return;
-		x.pool_ticket = (uint32_t *)ctx->pool_scratch, x.pool_scratch = (char *)ctx->pool_scratch + 4096, x.pool_waves = ctx->pool_waves, x.pool_bytes = ctx->pool_bytes;
-	};
-	a.route = routed ? ANDI_LAYOUT_LANES : 0, a.route_seg = coop_seg, a.route_nt = ctx->d_route;
-	uint32_t longest_q = 0;
-	for (size_t i = 0; i < q->nq; ++i) longest_q = std::max(longest_q, (uint32_t)q->len[i]);
-	a.reduce_threads = (longest_q + (a.adaptive ? seg0 : segment) - 1) / (a.adaptive ? seg0 : segment) <= 64 ? 64u : 0u;
-	{
-		const char *rs = andi_knob(KNOB_ROUTE_SMALL); // (experiments: log2 of the size below which a call is small)
-		const uint64_t small_nt = rs && atoi(rs) > 0 && atoi(rs) < 63 ? 1ull << atoi(rs) : ANDI_ROUTE_SMALL_NT;
-		a.route_all_few = q->total_nt * (uint64_t)nsub < small_nt ? 1u : 0u;
-	}
-	{
-		const char *gu = andi_knob(KNOB_COOP_GIVEUP); // (tests: hand pairs back early, so that the second lane layout runs)
-		a.route_giveup = gu && atoi(gu) > 0 ? (uint32_t)atoi(gu) : a.route_all_few ? 256u : 1024u; // (small calls route pairs the sampling cannot judge: a lower limit)
-		const char *sm = andi_knob(KNOB_ROUTE_SOFT); // (experiments)
-		a.route_soft_match = sm && atoi(sm) > 0 ? (uint32_t)atoi(sm) : 512u; // (128 = k_lane_quad's class: tree-structured set 38.1 -> 39.4 % of the roofline at 512, C3-like 45.6 -> 48.1 %, C4 shape the same)
-	}
-	a.exact_equal = (model == ANDI_M_LOGDET || model == ANDI_M_ANI) ? 1 : 0; // src/model.c:247
-
-	if (routed) {
-		// The call's pairs are routed (scan.h): the wavefront kernel's layout b beside the lane scan's a.  The pairs are
-		// sampled and routed; pass A by wavefronts (on a stream of its own) runs beside the lane scan's kernels; the pairs
-		// it handed back -- rare: the host looks -- get a second lane layout a2; passes B and C once per layout.
-		ScanArgs b = a;
-		b.adaptive = 0, b.coop = 1, b.route = ANDI_LAYOUT_COOP;
-		b.qseg_start = q->c_qseg_start, b.seg2query = q->c_seg2query, b.total_segs = q->c_total_segs, b.seg = coop_seg;
-		b.reduce_threads = (longest_q + coop_seg - 1) / coop_seg <= 64 ? 64u : 0u;
-		p = (char *)(a.sub_order + nsub);
-		p = (char *)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-		carve(b, slots2);
-		hipError_t e;
-		// every error exit below first waits for the streams this branch forks work onto: their kernels read the scratch
-		// the next call may regrow, and the context's teardown waits for ctx->stream only
-		auto bail = [&](const char *what, hipError_t err) {
-			(void)hipStreamSynchronize(ctx->coop_stream);
-			(void)hipStreamSynchronize(ctx->side_stream);
-			(void)hipStreamSynchronize(ctx->stream);
-			return fail(ctx, what, err);
-		};
-		{
-			Timed t(ctx, 2);
-			e = hipMemsetAsync(b.restitch_count, 0, 16 * sizeof(uint32_t), ctx->stream);
-			if (e == hipSuccess) e = andi_launch_pair_layout(a, ctx->stream);
-			t.stop();
-			if (e != hipSuccess) return bail("scan layout", e);
-		}
-		if (andi_knob(KNOB_DEBUG_STITCH)) { // diagnostics: how the pairs were routed
-			std::vector<uint8_t> cls(pairs_all);
-			(void)hipStreamSynchronize(ctx->stream);
-			(void)hipMemcpy(cls.data(), a.pair_class, pairs_all, hipMemcpyDeviceToHost);
-			size_t n_coop = 0, n_quad = 0, n_other = 0;
-			for (size_t i = 0; i < pairs_all; ++i)
-				if (h_self[i / q->nq] != (int64_t)(i % q->nq)) (cls[i] & ANDI_ROUTE_COOP ? n_coop : cls[i] & 0x80u ? n_quad : n_other)++;
-			fprintf(stderr, "route: %zu pairs by wavefronts, %zu k_lane_quad's class, %zu other lanes (unrelated stretches suspected / short query / many pairs far apart)\n", n_coop, n_quad, n_other);
-		}
-		bool any_left = false;
-		{
-			Timed t(ctx, 1);
-			// Which of the two goes first: the lane scan's kernels where its pairs are few -- behind the wavefront kernel a
-			// handful of lane blocks (four wavefronts and their LDS on one CU at once) found no place until that kernel's
-			// tail and ended 0.2 ms after everything else --, the wavefront kernel where they are many (the tree-structured
-			// set, the C4 shape: 0.4 and 1.5 ms the other way round).  The host looks at the layout (one word).
-			// (Small calls do not look: the wavefront kernel first, the lane layout's passes whether it has pairs or not --
-			// a look costs them 40 us of their few hundred.)
-			const bool look = !a.route_all_few;
-			for (int k = 0; k < 16; ++k) ctx->h_any_left[1 + k] = 0;
-			ctx->h_any_left[1 + ANDI_LANE_WAVES] = 1;
-			e = hipSuccess;
-			if (look) e = hipMemcpyAsync(ctx->h_any_left + 1, a.restitch_count, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-			if (look && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			const bool lanes_first = look && e == hipSuccess && (uint64_t)ctx->h_any_left[1 + ANDI_LANE_WAVES] * 20 < ctx->h_any_left[1 + ANDI_ALL_WAVES];
-			// which wavefront kernel: the pooled one where the pairs that suit it hold at least half of the segments (scan.h)
-			b.pool_use = look && e == hipSuccess && 2 * (uint64_t)ctx->h_any_left[1 + ANDI_POOL_SEGS] >= ctx->h_any_left[1 + ANDI_COOP_SEGS] && ctx->h_any_left[1 + ANDI_COOP_SEGS] != 0;
-			give_pool_scratch(b);
-			if (e == hipSuccess) e = hipEventRecord(ctx->coop_fork, ctx->stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(ctx->coop_stream, ctx->coop_fork, 0);
-			if (e == hipSuccess && lanes_first) e = andi_launch_scan_cold(a, ctx->stream);
-			if (e == hipSuccess) e = andi_launch_coop_cold(b, ctx->coop_stream);
-			if (andi_coop_will_pool(b)) ctx->acc.pool_calls++;
-			if (e == hipSuccess) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
-			if (e == hipSuccess && !lanes_first) e = andi_launch_scan_cold(a, ctx->stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
-			if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_any_left, b.restitch_count + ANDI_ROUTE_ANY_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-			if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-			if (e != hipSuccess) return bail("scan pass A", e);
-			any_left = ctx->h_any_left[0] != 0;
-			const bool any_lanes = ctx->h_any_left[1 + ANDI_LANE_WAVES] != 0; // (no pair in the lane layout: its passes B and C have nothing to do)
-			ScanArgs a2 = a;
-			if (any_left) { // the pairs handed back: a lane layout of their own (as large as the first at most)
-				const size_t need2 = slots * ANDI_SLOT_BYTES + 256 + pairs_all * 9 + 64 + (pairs_all / 1024 + 2) * 4 + 16;
-				if (ctx->scratch2_bytes < need2) {
-					if (ctx->scratch2) (void)andi_arena::dev_free(ctx->scratch2);
-					ctx->scratch2 = nullptr, ctx->scratch2_bytes = 0;
-					e = andi_arena::dev_malloc(&ctx->scratch2, need2);
-					if (e != hipSuccess) return bail("scratch of the second lane layout", e);
-					ctx->scratch2_bytes = need2;
-				}
-				p = (char *)ctx->scratch2;
-				carve(a2, slots);
-				a2.route = ANDI_LAYOUT_LANES2;
-				a2.pair_waves = (uint32_t *)p;
-				a2.pair_wave0 = a2.pair_waves + pairs_all;
-				a2.pair_bsum = a2.pair_wave0 + pairs_all + 1;
-				a2.side_stream = nullptr; // (its own kernels one after the other: it runs on the side stream itself, below)
-			}
-			t.stop();
-			// Passes B and C once per layout, side by side (each is a chain of small launches); the pairs handed back take
-			// their pass A at the head of their chain.
-			Timed t2(ctx, 2);
-			e = hipEventRecord(ctx->l2_fork, ctx->stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(ctx->coop_stream, ctx->l2_fork, 0);
-			if (e == hipSuccess) e = andi_launch_scan_stitch(b, ctx->coop_stream);
-			if (e == hipSuccess) e = andi_launch_scan_reduce(b, ctx->coop_stream);
-			if (e == hipSuccess) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
-			if (e == hipSuccess && any_left) {
-				e = hipStreamWaitEvent(ctx->side_stream, ctx->l2_fork, 0);
-				if (e == hipSuccess) e = andi_launch_pair_leftover(a2, ctx->side_stream);
-				if (e == hipSuccess) e = andi_launch_scan_cold(a2, ctx->side_stream);
-				if (e == hipSuccess) e = andi_launch_scan_stitch(a2, ctx->side_stream);
-				if (e == hipSuccess) e = andi_launch_scan_reduce(a2, ctx->side_stream);
-				if (e == hipSuccess) e = hipEventRecord(ctx->l2_join, ctx->side_stream);
-			}
-			if (e == hipSuccess && any_lanes) e = andi_launch_scan_stitch(a, ctx->stream);
-			if (e == hipSuccess && any_lanes) e = andi_launch_scan_reduce(a, ctx->stream);
-			if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
-			if (e == hipSuccess && any_left) e = hipStreamWaitEvent(ctx->stream, ctx->l2_join, 0);
-			if (e == hipSuccess) e = andi_launch_route_count(a, ctx->stream);
-			t2.stop();
-			if (e != hipSuccess) return bail("scan passes B/C", e);
-		}
-		ctx->acc.coop_calls++;
-		ctx->acc.routed_calls++;
-	} else {
-		if (a.adaptive) {
-			Timed t(ctx, 2);
-			hipError_t e = andi_launch_pair_layout(a, ctx->stream);
-			t.stop();
-			if (e != hipSuccess) return fail(ctx, "scan layout", e);
-		}
-		give_pool_scratch(a); // (a call whose pass A is the wavefront kernel's for every pair: ANDI_COOP=n, tiny calls)
-		{
-			Timed t(ctx, 1);
-			hipError_t e = andi_launch_scan_cold(a, ctx->stream);
-			t.stop();
-			if (e != hipSuccess) return fail(ctx, "scan pass A", e);
-			if (a.coop) ctx->acc.coop_calls++;
-			if (a.coop && andi_coop_will_pool(a)) ctx->acc.pool_calls++;
-		}
-		Timed t(ctx, 2);
-		hipError_t e = andi_launch_scan_stitch(a, ctx->stream);
-		if (e == hipSuccess) e = andi_launch_scan_reduce(a, ctx->stream);
-		t.stop();
-		if (e != hipSuccess) return fail(ctx, "scan passes B/C", e);
-	}
-	if (andi_knob(KNOB_DEBUG_STITCH)) { // diagnostics: segments stitched again per round, length of the last stage's list
-		uint32_t h[16];
-		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipMemcpy(h, a.restitch_count, sizeof h, hipMemcpyDeviceToHost);
-		fprintf(stderr, "stitch: %zu slots; true chains that left on their own %u; stitched again in rounds: %u %u %u; last list %u\n", slots,
-				h[ANDI_RESTITCH_ROUNDS], h[0], h[1], h[2], h[8]);
-	}
-	(adaptive ? ctx->acc.adaptive_calls : ctx->acc.uniform_calls)++;
-	ctx->acc.scan_pairs += pairs;
-	ctx->acc.scan_query_nt += nt;
-	return 0;
-}
-
 // ------------------------------------------------------------------ the measured copy ceiling (bench.py: roofline.measured_copy_GBps)
+extern "C" { // (the kernel's host stub keeps the name it always had)
 namespace {
 __global__ __launch_bounds__(256) void k_stream_copy(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n16) {
 	const size_t stride = (size_t)gridDim.x * 256;
@@ -1773,6 +1102,7 @@ __global__ __launch_bounds__(256) void k_stream_copy(const uint4 *__restrict__ s
 	}
 }
 } // namespace
+} // extern "C"
 
 int andi_hip_copy_ceiling(andi_hip_ctx *ctx, size_t bytes, int reps, double *gbps) {
 	if (!ctx || !gbps || bytes < 4096 || reps < 1) {
@@ -1857,699 +1187,3 @@ void andi_hip_timings_reset(andi_hip_ctx *ctx) {
 	ctx->acc = andi_hip_timings{};
 }
 
-} // extern "C"
-
-// ------------------------------------------------------------------ the seam
-// distMatrix / distMatrixLM, src/dist_hack.h:34-96: for every subject build the
-// index and compare every other sequence against it.
-//
-// The rows of the matrix (one subject against every query) are independent given
-// the subject's index.  Every device of the call owns a contiguous block of rows
-// (block sizes differ by at most one) and is driven by one host thread with its own
-// context: all queries staged once, a set of subject slots reused batch after batch,
-// its rows kept in HBM.  A pool of host threads shared by all devices prepares RS and
-// the suffix array (seq_subject_init + esa_init_SA) in the order the devices will
-// ask for them.  The one exchange of the job is the gather of the row blocks on the
-// first device -- RCCL send/recv over xGMI, every peer on its own link -- followed by
-// one copy of the matrix to the host.  (One device, several contexts on one device,
-// or no usable RCCL: every block is copied to the host matrix directly.)
-namespace {
-struct Prepared {
-	size_t idx = 0;
-	char *RS = nullptr;
-	size_t n = 0, thr = 0;
-	std::vector<int32_t> SA;
-	int rc = 0;
-};
-
-// librccl is loaded when a call first spans several devices: single-device users (and processes
-// that carry another copy of RCCL, like PyTorch's) never touch it
-struct Rccl {
-	void *lib = nullptr;
-	ncclResult_t (*CommInitAll)(ncclComm_t *, int, const int *) = nullptr;
-	ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-	ncclResult_t (*GroupStart)() = nullptr;
-	ncclResult_t (*GroupEnd)() = nullptr;
-	ncclResult_t (*Send)(const void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-	ncclResult_t (*Recv)(void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-	const char *(*GetErrorString)(ncclResult_t) = nullptr;
-	bool ok = false;
-};
-
-Rccl &rccl() {
-	static Rccl r;
-	static std::once_flag once;
-	std::call_once(once, [] {
-		const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"};
-		for (const char *nm : names)
-			if ((r.lib = dlopen(nm, RTLD_NOW | RTLD_LOCAL))) break;
-		if (!r.lib) return;
-		r.CommInitAll = (decltype(r.CommInitAll))dlsym(r.lib, "ncclCommInitAll");
-		r.CommDestroy = (decltype(r.CommDestroy))dlsym(r.lib, "ncclCommDestroy");
-		r.GroupStart = (decltype(r.GroupStart))dlsym(r.lib, "ncclGroupStart");
-		r.GroupEnd = (decltype(r.GroupEnd))dlsym(r.lib, "ncclGroupEnd");
-		r.Send = (decltype(r.Send))dlsym(r.lib, "ncclSend");
-		r.Recv = (decltype(r.Recv))dlsym(r.lib, "ncclRecv");
-		r.GetErrorString = (decltype(r.GetErrorString))dlsym(r.lib, "ncclGetErrorString");
-		r.ok = r.CommInitAll && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv && r.GetErrorString;
-	});
-	return r;
-}
-
-thread_local char g_last_gather[200] = "none"; // how the calling thread's last andi_hip_dist_matrix call collected its rows (diagnostic)
-
-void row_block(size_t total, size_t parts, size_t k, size_t &first, size_t &last) { // as andi_amd/shard.py: row_block
-	const size_t base = total / parts, extra = total % parts;
-	first = k * base + std::min(k, extra);
-	last = first + base + (k < extra ? 1 : 0);
-}
-} // namespace
-
-extern "C" {
-
-const char *andi_hip_last_gather(void) {
-	return g_last_gather;
-}
-
-void andi_hip_row_block(size_t total, size_t parts, size_t k, size_t *first, size_t *last) {
-	size_t f = 0, l = 0;
-	if (parts && k < parts) row_block(total, parts, k, f, l);
-	if (first) *first = f;
-	if (last) *last = l;
-}
-
-int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
-						 const andi_hip_opts *opts_in, char *errbuf, size_t errlen) {
-	if (!M || !seqs || n == 0) {
-		set_err(errbuf, errlen, "andi_hip_dist_matrix: bad arguments");
-		return 1;
-	}
-	andi_hip_opts o;
-	if (opts_in) {
-		o = *opts_in;
-	} else {
-		andi_hip_default_opts(&o);
-	}
-	for (size_t i = 0; i < n; ++i) {
-		if (!seqs[i].seq || seqs[i].len == 0) {
-			set_err(errbuf, errlen, "sequence %zu is empty", i); // src/andi.c:302-304
-			return 1;
-		}
-		if (seqs[i].len > (size_t)(INT32_MAX - 1) / 2) { // src/andi.c:296-300
-			set_err(errbuf, errlen, "sequence %zu is too long. The technical limit is %zu.", i,
-					(size_t)(INT32_MAX - 1) / 2);
-			return 1;
-		}
-	}
-
-	// ---- the devices of the call
-	std::vector<int> devs;
-	{
-		int visible = 0;
-		hipError_t e = hipGetDeviceCount(&visible);
-		if (e != hipSuccess || visible <= 0) {
-			set_err(errbuf, errlen, "no HIP device available (%s); the anchor-distance engine has no CPU path",
-					e != hipSuccess ? hipGetErrorString(e) : "device count 0");
-			return 1;
-		}
-		if (o.devices && o.num_gpus > 0) {
-			devs.assign(o.devices, o.devices + o.num_gpus);
-		} else {
-			const int want = o.num_gpus < 0 ? visible - o.device : (o.num_gpus == 0 ? 1 : o.num_gpus);
-			for (int k = 0; k < want; ++k) devs.push_back(o.device + k);
-		}
-		for (int d : devs)
-			if (d < 0 || d >= visible) {
-				set_err(errbuf, errlen, "HIP device %d out of range (have %d)", d, visible);
-				return 1;
-			}
-		if (devs.empty()) {
-			set_err(errbuf, errlen, "andi_hip_dist_matrix: no device selected");
-			return 1;
-		}
-		if (devs.size() > n) devs.resize(n); // at least one row each
-	}
-	const size_t ndev = devs.size();
-	bool distinct = true;
-	for (size_t a = 0; a < ndev; ++a)
-		for (size_t b = a + 1; b < ndev; ++b) distinct = distinct && devs[a] != devs[b];
-	const char *gather_env = andi_knob(KNOB_GATHER);
-	// RCCL gather: several distinct devices (or forced, to exercise the path on the devices there are -- with contexts that
-	// share a device the communicators cannot be made: the route's fallback, every block copied from HBM directly, runs),
-	// and the matrix fits next to the rest
-	bool use_rccl = (ndev > 1 && distinct && !(gather_env && !strcmp(gather_env, "direct"))) ||
-					(gather_env && !strcmp(gather_env, "rccl"));
-	if (use_rccl && n * n * sizeof(andi_hip_model) > ((size_t)32 << 30)) use_rccl = false;
-	if (use_rccl && !rccl().ok) use_rccl = false;
-
-	// ---- shared host pool: subject preparation + suffix sorting (the role of the OpenMP
-	// subject loop, src/dist_hack.h:46-52), in the order the devices consume, bounded look-ahead
-	size_t longest = 0;
-	for (size_t i = 0; i < n; ++i) longest = std::max(longest, seqs[i].len);
-	const size_t rs_cap = 2 * longest + 1;
-	std::vector<size_t> first(ndev), last(ndev);
-	size_t max_rows = 0;
-	for (size_t d = 0; d < ndev; ++d) {
-		row_block(n, ndev, d, first[d], last[d]);
-		max_rows = std::max(max_rows, last[d] - first[d]);
-	}
-	std::vector<size_t> order; // subjects in the order they are needed
-	order.reserve(n);
-	for (size_t k = 0; k < max_rows; ++k)
-		for (size_t d = 0; d < ndev; ++d)
-			if (first[d] + k < last[d]) order.push_back(first[d] + k);
-
-	int threads = o.host_threads > 0 ? o.host_threads : (int)std::thread::hardware_concurrency();
-	if (threads < 1) threads = 1;
-	if ((size_t)threads > n) threads = (int)n;
-	// Every subject is also a query, and the queries are staged in HBM before the first batch: unless the suffix arrays are
-	// the host's (sa_on_host: the sorter needs RS where it runs), a device writes RS = revcomp(S) '#' S into the subject's
-	// slot itself from its query pool (esa_from_query) and the host computes only min_anchor_length from the device's G+C
-	// counts -- no host pass over the sequences, no second upload of what is already resident (round 5's trace of the bench
-	// set's warm call: host pool 5.5 ms + subject uploads 12.9 ms of 54).
-	const bool dev_prep = !o.sa_on_host;
-	const size_t batch_max = o.low_memory ? 1 : 8;
-	const size_t window = (size_t)threads + ndev * batch_max + 1;
-
-	std::mutex mu;
-	std::condition_variable cv;
-	std::deque<Prepared *> ready; // any order
-	std::atomic<size_t> next{0};
-	size_t consumed = 0; // subjects taken by the devices, guarded by mu
-	bool abort_flag = false;
-	std::string first_error;
-	size_t rows_done = 0; // guarded by mu (progress)
-
-	auto fail_all = [&](const std::string &msg) {
-		std::lock_guard<std::mutex> lk(mu);
-		if (!abort_flag) first_error = msg;
-		abort_flag = true;
-		cv.notify_all();
-	};
-
-	auto worker = [&]() {
-		for (;;) {
-			const size_t pos = next.fetch_add(1);
-			if (pos >= n) return;
-			{
-				std::unique_lock<std::mutex> lk(mu);
-				cv.wait(lk, [&] { return abort_flag || pos < consumed + window; });
-				if (abort_flag) return;
-			}
-			const size_t i = order[pos];
-			Prepared *p = nullptr;
-			try {
-				p = new Prepared;
-				p->idx = i;
-				double gc;
-				p->rc = andi_hip_subject_prepare(seqs[i].seq, seqs[i].len, o.p_value, &p->RS, &p->n, &gc, &p->thr);
-				if (!p->rc && o.sa_on_host) {
-					p->SA.resize(p->n);
-					p->rc = andi_hip_suffix_array((const unsigned char *)p->RS, p->SA.data(), (int32_t)p->n);
-				}
-			} catch (...) { // out of memory: report it as the reference does (src/dist_hack.h:53)
-				if (p) {
-					andi_hip_free(p->RS);
-					delete p;
-				}
-				char msg[96];
-				snprintf(msg, sizeof msg, "Failed to create index for sequence %zu.", i);
-				fail_all(msg);
-				return;
-			}
-			{
-				std::lock_guard<std::mutex> lk(mu);
-				ready.push_back(p);
-			}
-			cv.notify_all();
-		}
-	};
-
-	auto take = [&](size_t i) -> Prepared * { // blocks until subject i is prepared; null if the call was aborted
-		std::unique_lock<std::mutex> lk(mu);
-		Prepared *p = nullptr;
-		cv.wait(lk, [&] {
-			if (abort_flag) return true;
-			for (auto *c : ready)
-				if (c->idx == i) return true;
-			return false;
-		});
-		if (abort_flag) return nullptr;
-		for (auto it = ready.begin(); it != ready.end(); ++it)
-			if ((*it)->idx == i) {
-				p = *it;
-				ready.erase(it);
-				break;
-			}
-		return p;
-	};
-
-	// ---- one driver per device.  Two stages, two contexts (streams) and two sets of subject slots per device: while the
-	// scan of one batch of subjects runs, a second thread stages the next -- upload, suffix arrays, index builds -- as
-	// the reference's threads build one subject's index while others scan (src/dist_hack.h:46-52).
-	struct Dev {
-		andi_hip_ctx *ctx = nullptr;  // scans, row copies
-		andi_hip_ctx *prep = nullptr; // suffix arrays, index builds
-		andi_hip_ctx *up = nullptr;   // uploads (a thread and a stream of their own: the copies of batch k + 1 run beside the sorts of batch k)
-		std::vector<andi_hip_ctx *> sorters; // suffix sorts of a batch's subjects side by side (streams and workspaces of their own)
-		andi_hip_queries *Q = nullptr;
-		andi_hip_model *d_rows = nullptr; // rccl: the whole row block; direct: one batch of rows
-		size_t pinned_bytes = 0;
-		char *pinned = nullptr;           // staging buffers for RS (two: one is filled while the other's copy runs): uploads from pinned memory go through the DMA engines, beside a scan
-		hipEvent_t pinned_free[2] = {nullptr, nullptr};
-		std::vector<andi_hip_esa *> slots; // sets x batch
-	};
-	std::vector<Dev> dv(ndev);
-
-	const bool trace = andi_knob(KNOB_E2E_TRACE) != nullptr; // diagnostics: where the call's wall time goes (device 0's driver)
-	auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-	const double t_call = now_ms();
-	// the queries as 4-bit symbols, packed once for all devices while their contexts come up (ANDI_QUERIES_BYTES: every
-	// device uploads the bytes and packs them itself, as up to round 3)
-	// One device: the bytes as they lie (measured on one GPU, same box: C4's queries 0.51 s as bytes, 0.10 s packed -- but the
-	// pack's pass over the host's memory and the release of its copy gave the 0.3 s back; C5 was slower packed).
-	const bool pack_on_host = andi_knob(KNOB_QUERIES_BYTES) == nullptr && (ndev > 1 || andi_knob(KNOB_QUERIES_PACKED) != nullptr);
-	PackedQueries PQ;
-	PQ.users.store((int)ndev);
-	std::mutex pq_mu;
-	std::condition_variable pq_cv;
-	bool pq_done = false;
-	int pq_rc = 0;
-	std::thread packer;
-	if (pack_on_host)
-		packer = std::thread([&] {
-			const int rc = pack_queries_host(seqs, n, threads, PQ);
-			std::lock_guard<std::mutex> lk(pq_mu);
-			pq_rc = rc, pq_done = true;
-			pq_cv.notify_all();
-		});
-	auto drive = [&](size_t d) {
-		Dev &D = dv[d];
-		char eb[256] = "";
-		double t_last = now_ms(), acc_wait = 0, acc_scan = 0, acc_copy = 0;
-		auto lap = [&](double &acc) {
-			const double t = now_ms();
-			acc += t - t_last, t_last = t;
-		};
-		double t_ctx = 0, t_queries = 0, t_slots = 0;
-		auto bail = [&](const char *what, andi_hip_ctx *cx) {
-			char msg[512];
-			snprintf(msg, sizeof msg, "%s (device %d): %s", what, devs[d], cx ? andi_hip_last_error(cx) : eb);
-			fail_all(msg);
-		};
-		if (andi_hip_ctx_create(&D.ctx, devs[d], eb, sizeof eb)) return bail("creating a context", nullptr);
-		if (ctx_create(&D.prep, devs[d], eb, sizeof eb, true)) return bail("creating a context", nullptr);
-		if (!dev_prep) {
-			if (ctx_create(&D.up, devs[d], eb, sizeof eb, true)) return bail("creating a context", nullptr);
-			andi_hip_ctx_expect_queries(D.up, n - 1);
-		}
-		// A suffix sort is two dozen launches with two or three host round trips between them (sa_device.hip): 0.73 ms per
-		// 9.8 M characters of which the device is busy half.  The subjects of a batch are sorted by up to four host threads,
-		// each with a stream and a workspace of its own, so one subject's small launches and waits hide behind another's
-		// radix passes.
-		size_t sort_width = dev_prep && !o.low_memory ? std::min<size_t>(4, std::min(batch_max, last[d] - first[d])) : 1;
-		if (const char *sw = andi_knob(KNOB_SORT_WIDTH)) // (experiments)
-			if (atoi(sw) >= 1 && atoi(sw) <= 8) sort_width = std::min<size_t>((size_t)atoi(sw), std::min(batch_max, last[d] - first[d]));
-		// (a workspace of 45 bytes per character each: together at most one chunk of the arena -- eight of them for 9.8 M characters pushed a
-		// 29-genome call past the 8 GiB the arena keeps from call to call, and every call paid the driver for its chunks again: 37 -> 177 ms;
-		// two sorters measured like four, profiles/r07_seam/)
-		while (sort_width > 1 && andi_sa_device_workspace((int32_t)rs_cap) * sort_width > ((size_t)2 << 30)) --sort_width;
-		for (size_t w = 1; w < sort_width; ++w) {
-			andi_hip_ctx *cx = nullptr;
-			if (ctx_create(&cx, devs[d], eb, sizeof eb, true)) return bail("creating a context", nullptr);
-			andi_hip_ctx_expect_queries(cx, n - 1);
-			D.sorters.push_back(cx);
-		}
-		andi_hip_ctx_expect_queries(D.ctx, n - 1);
-		andi_hip_ctx_expect_queries(D.prep, n - 1);
-		lap(t_ctx);
-		const size_t rows = last[d] - first[d];
-		// Subject slots: device buffers sized for the longest genome, reused batch after batch (no
-		// allocation inside the loop).  Several subjects per scan call keep the GPU filled; low_memory
-		// keeps one index resident at a time, which is what distMatrixLM trades (src/dist_hack.h:14-16).
-		size_t batch = batch_max < rows ? batch_max : rows;
-		auto sets_for = [&](size_t bt) { // (low_memory: one index resident at a time)
-			const size_t nb = (rows + bt - 1) / bt;
-			return o.low_memory ? (size_t)1 : (nb > 2 && !dev_prep ? (size_t)3 : (nb > 1 ? (size_t)2 : (size_t)1)); // (the third set is the uploads')
-		};
-		{
-			size_t free_b = 0, total_b = 0;
-			if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-				// a slot: text + padding, suffix array, the records of the device sorter, the packed text twice, the probe table
-				const size_t per_slot = 14 * rs_cap + ((size_t)8 << (2 * pick_deep_k(rs_cap, D.ctx->queries_hint))) + (1 << 20);
-				while (batch > 1 && sets_for(batch) * batch * per_slot > free_b / (2 * ndev)) batch /= 2; // (as many sets as the batches will really have)
-			}
-		}
-		const size_t nbatches = (rows + batch - 1) / batch;
-		// Three sets of slots: while batch k is scanned, batch k + 2 is uploaded (no compute units needed) and batch k + 1
-		// is ready; the device's COMPUTE alternates strictly -- suffix sorts and index builds of batch k + 1, then the scan
-		// of batch k -- because side by side the staging kernels starve behind the workgroups of a scan that fills the
-		// device (sorts of 8 subjects: 6 ms alone, 38 ms beside a scan, on a high-priority stream as on a plain one).
-		const size_t sets = sets_for(batch);
-		D.slots.assign(sets * batch, nullptr);
-		if (pack_on_host) {
-			{
-				std::unique_lock<std::mutex> lk(pq_mu);
-				pq_cv.wait(lk, [&] { return pq_done; });
-			}
-			if (pq_rc) {
-				snprintf(eb, sizeof eb, "%s", PQ.err.c_str());
-				return bail("staging queries", nullptr);
-			}
-			const int rc = queries_stage_packed(D.ctx, PQ, &D.Q);
-			if (PQ.users.fetch_sub(1) == 1) PQ.release(); // (every device has its copy)
-			if (rc) return bail("staging queries", D.ctx);
-		} else if (andi_hip_queries_stage(D.ctx, seqs, n, &D.Q)) {
-			return bail("staging queries", D.ctx);
-		}
-		std::vector<unsigned long long> gcs; // G+C of every sequence (calc_gc, src/sequence.c:197-208)
-		if (dev_prep && queries_gc_counts(D.ctx, D.Q, gcs)) return bail("staging queries", D.ctx);
-		lap(t_queries);
-		for (size_t b = 0; b < sets * batch; ++b)
-			if (esa_reserve(D.prep, rs_cap, &D.slots[b])) return bail("allocating subject slots", D.prep);
-		if (andi_hip_sync(D.prep)) return bail("allocating subject slots", D.prep);
-		double t_reserve = 0, t_pinned = 0;
-		lap(t_reserve);
-		D.pinned_bytes = 2 * (rs_cap + 64);
-		if (dev_prep || host_pool::pinned_get((void **)&D.pinned, D.pinned_bytes) != hipSuccess) D.pinned = nullptr; // (then from where RS lies)
-		if (D.pinned && (hipEventCreateWithFlags(&D.pinned_free[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&D.pinned_free[1], hipEventDisableTiming) != hipSuccess)) {
-			host_pool::pinned_put(D.pinned, D.pinned_bytes);
-			D.pinned = nullptr;
-		}
-		lap(t_pinned);
-		if (andi_hip_dev_alloc(D.ctx, (use_rccl ? rows : batch) * n * sizeof(andi_hip_model), (void **)&D.d_rows)) return bail("row buffer", D.ctx);
-		lap(t_slots);
-		t_slots += t_reserve + t_pinned;
-		if (trace && d == 0) fprintf(stderr, "andi_hip_dist_matrix trace: slots = device buffers of %zu slots %.1f ms + pinned upload buffer %.1f ms + row buffer %.1f ms\n", sets * batch, t_reserve, t_pinned, t_slots - t_reserve - t_pinned);
-
-		// hand-over between the two stages
-		std::mutex pm;
-		std::condition_variable pcv;
-		size_t prepared = 0, scanned = 0; // batches staged / scanned so far
-		bool prep_failed = false;
-		double p_take = 0, p_upload = 0, p_sort = 0, p_build = 0;
-
-		size_t uploaded = dev_prep ? nbatches : 0; // batches whose texts are on the device (written there by the staging thread itself: all of them)
-		// the device's compute alternates between the stages where a slot set is free for it: stage k + 1, then scan k
-		const bool alternate = sets >= (dev_prep ? (size_t)2 : (size_t)3);
-		auto give_up = [&]() {
-			std::lock_guard<std::mutex> lk(pm);
-			prep_failed = true;
-			pcv.notify_all();
-		};
-		auto upload = [&]() { // the upload thread of this device: texts from the host pool into the slot sets, a batch ahead of the sorts
-			(void)hipSetDevice(devs[d]);
-			double tl = now_ms();
-			auto plap = [&](double &acc) {
-				const double t = now_ms();
-				acc += t - tl, tl = t;
-			};
-			size_t nup = 0; // texts uploaded so far
-			for (size_t k = 0; k < nbatches; ++k) {
-				{
-					std::unique_lock<std::mutex> lk(pm);
-					pcv.wait(lk, [&] { return k < scanned + sets || prep_failed; }); // its set of slots is free again
-					if (prep_failed) return;
-				}
-				tl = now_ms();
-				const size_t i0 = first[d] + k * batch, nb = std::min(batch, last[d] - i0);
-				andi_hip_esa **set = D.slots.data() + (k % sets) * batch;
-				for (size_t b = 0; b < nb; ++b) { // uploads: beside whatever the device computes
-					Prepared *p = take(i0 + b);
-					if (!p) return give_up();
-					plap(p_take);
-					bool ok = true;
-					if (p->rc) {
-						char msg[96];
-						snprintf(msg, sizeof msg, "Failed to create index for sequence %zu.", i0 + b); // src/dist_hack.h:53
-						fail_all(msg);
-						ok = false;
-					}
-					// through one of two pinned buffers: the next text is copied into the other while this one's transfer runs
-					const bool two = D.pinned && !o.sa_on_host; // (a suffix array from the host is pageable memory: that copy waits anyway)
-					const size_t pb = nup++ & 1;
-					char *pin = D.pinned ? D.pinned + pb * (rs_cap + 64) : nullptr;
-					if (ok && two && nup > 2 && hipEventSynchronize(D.pinned_free[pb]) != hipSuccess) bail("staging subject", D.up), ok = false;
-					const char *src = p->RS;
-					if (ok && pin) memcpy(pin, p->RS, p->n), src = pin;
-					if (ok && esa_upload(D.up, set[b], src, o.sa_on_host ? p->SA.data() : nullptr, p->n, p->thr, two ? D.pinned_free[pb] : nullptr)) bail("staging subject", D.up), ok = false;
-					plap(p_upload);
-					andi_hip_free(p->RS);
-					delete p;
-					{
-						std::lock_guard<std::mutex> lk(mu);
-						++consumed;
-					}
-					cv.notify_all();
-					if (!ok) return give_up();
-				}
-				if (andi_hip_sync(D.up)) { // (the batch's transfers)
-					bail("staging subject", D.up);
-					return give_up();
-				}
-				plap(p_upload);
-				{
-					std::lock_guard<std::mutex> lk(pm);
-					uploaded = k + 1;
-				}
-				pcv.notify_all();
-			}
-		};
-		auto stage = [&]() { // the staging thread of this device: suffix sorts and index builds
-			(void)hipSetDevice(devs[d]);
-			double tl = now_ms();
-			auto plap = [&](double &acc) {
-				const double t = now_ms();
-				acc += t - tl, tl = t;
-			};
-			for (size_t k = 0; k < nbatches; ++k) {
-				{ // the batch's texts are there; with three sets the device's compute is this batch's once the scan of batch k - 2 is done
-					std::unique_lock<std::mutex> lk(pm);
-					pcv.wait(lk, [&] { return (uploaded > k && (dev_prep ? k < scanned + sets : (sets < 3 || k < scanned + 2))) || prep_failed; });
-					if (prep_failed) return;
-				}
-				tl = now_ms();
-				const size_t i0 = first[d] + k * batch, nb = std::min(batch, last[d] - i0);
-				andi_hip_esa **set = D.slots.data() + (k % sets) * batch;
-				// RS from the resident sequence (the threshold on the host, same libm: src/sequence.c:210-219), then its suffix array
-				auto text_and_sort = [&](andi_hip_ctx *cx, size_t b) -> const char * {
-					const size_t i = i0 + b, len = seqs[i].len;
-					const size_t thr = andi_hip_min_anchor_length(o.p_value, (double)gcs[i] / len, 2 * len + 1);
-					if (esa_from_query(cx, set[b], D.Q, i, thr)) return "staging subject";
-					if (esa_sort_suffixes(cx, set[b])) return "suffix array";
-					return nullptr;
-				};
-				if (dev_prep) {
-					const size_t width = std::min(nb, D.sorters.size() + 1);
-					std::atomic<size_t> next_b{0};
-					std::mutex em;
-					const char *what = nullptr;
-					andi_hip_ctx *where = nullptr;
-					auto sort_some = [&](andi_hip_ctx *cx) {
-						(void)hipSetDevice(devs[d]);
-						for (;;) {
-							const size_t b = next_b.fetch_add(1);
-							if (b >= nb) break;
-							const char *w = text_and_sort(cx, b);
-							if (w) {
-								std::lock_guard<std::mutex> lk(em);
-								if (!what) what = w, where = cx;
-								next_b.store(nb);
-								break;
-							}
-						}
-						if (andi_hip_sync(cx)) {
-							std::lock_guard<std::mutex> lk(em);
-							if (!what) what = "suffix array", where = cx;
-						}
-					};
-					std::vector<std::thread> helpers;
-					for (size_t w = 1; w < width; ++w) helpers.emplace_back(sort_some, D.sorters[w - 1]);
-					sort_some(D.prep);
-					for (auto &t : helpers) t.join();
-					if (what) {
-						bail(what, where);
-						return give_up();
-					}
-					plap(p_sort);
-				}
-				if (andi_hip_esa_build_index_batch(D.prep, set, nb) || andi_hip_sync(D.prep)) {
-					bail("index build", D.prep);
-					return give_up();
-				}
-				plap(p_build);
-				{
-					std::lock_guard<std::mutex> lk(pm);
-					prepared = k + 1;
-				}
-				pcv.notify_all();
-			}
-		};
-		std::thread uploader;
-		if (!dev_prep) uploader = std::thread(upload);
-		std::thread stager(stage);
-
-		std::vector<int64_t> self(batch);
-		bool failed = false;
-		t_last = now_ms();
-		for (size_t k = 0; k < nbatches && !failed; ++k) {
-			{
-				std::unique_lock<std::mutex> lk(pm);
-				pcv.wait(lk, [&] { return (prepared > k && (!alternate || prepared > k + 1 || prepared == nbatches)) || prep_failed; });
-				if (prepared <= k) break; // (the staging thread has reported why)
-			}
-			lap(acc_wait);
-			const size_t i0 = first[d] + k * batch, nb = std::min(batch, last[d] - i0);
-			andi_hip_esa **set = D.slots.data() + (k % sets) * batch;
-			for (size_t b = 0; b < nb; ++b) self[b] = (int64_t)(i0 + b);
-			andi_hip_model *dst = use_rccl ? D.d_rows + (i0 - first[d]) * n : D.d_rows;
-			if (andi_hip_scan_rows(D.ctx, set, self.data(), nb, D.Q, o.model, o.segment, dst)) bail("scan", D.ctx), failed = true;
-			if (!failed && trace) (void)andi_hip_sync(D.ctx);
-			lap(acc_scan);
-			if (!failed && !use_rccl && andi_hip_copy_to_host(D.ctx, M + i0 * n, dst, nb * n * sizeof(andi_hip_model))) bail("row copy", D.ctx), failed = true;
-			if (!failed && use_rccl && andi_hip_sync(D.ctx)) bail("scan", D.ctx), failed = true; // the slots are reused
-			lap(acc_copy);
-			{
-				std::lock_guard<std::mutex> lk(pm);
-				scanned = k + 1;
-				if (failed) prep_failed = true;
-			}
-			pcv.notify_all();
-			if (!failed && o.progress) {
-				std::lock_guard<std::mutex> lk(mu);
-				rows_done += nb;
-				o.progress(rows_done * (n - 1), n * n - n, o.ud);
-			}
-		}
-		{
-			std::lock_guard<std::mutex> lk(pm);
-			if (scanned < nbatches) prep_failed = true; // (release the staging thread)
-		}
-		pcv.notify_all();
-		stager.join();
-		if (uploader.joinable()) uploader.join();
-		if (trace && d == 0)
-			fprintf(stderr, "andi_hip_dist_matrix trace (ms): contexts %.1f, queries %.1f, slots %.1f | staging thread: waiting for the host pool %.1f, subject %s %.1f, suffix arrays %.1f, index builds %.1f | scan thread: waiting for staged subjects %.1f, scans %.1f, row copies %.1f; driver total %.1f (%zu batches of %zu, %zu slot sets)\n",
-					t_ctx, t_queries, t_slots, p_take, dev_prep ? "texts written on the device" : "uploads", p_upload, p_sort, p_build, acc_wait, acc_scan, acc_copy, now_ms() - t_call, nbatches, batch, sets);
-	};
-
-	std::vector<std::thread> pool, drivers;
-	for (int t = 0; t < threads && !dev_prep; ++t) pool.emplace_back(worker);
-	if (ndev == 1) {
-		drive(0); // the calling thread, as before
-	} else {
-		for (size_t d = 0; d < ndev; ++d) drivers.emplace_back(drive, d);
-		for (auto &t : drivers) t.join();
-	}
-	{
-		std::lock_guard<std::mutex> lk(mu);
-		consumed = n; // release any waiting worker
-		if (abort_flag) next.store(n);
-	}
-	cv.notify_all();
-	for (auto &t : pool) t.join();
-	if (packer.joinable()) packer.join();
-	for (auto *p : ready) {
-		andi_hip_free(p->RS);
-		delete p;
-	}
-	int rc = abort_flag ? 1 : 0;
-	const double t_drivers_done = now_ms();
-
-	// ---- the gather: row blocks to the first device over RCCL, one copy to the host
-	snprintf(g_last_gather, sizeof g_last_gather, "%s", use_rccl ? "rccl" : "direct");
-	if (!rc && use_rccl) {
-		Rccl &R = rccl();
-		std::vector<ncclComm_t> comms(ndev, nullptr);
-		andi_hip_model *d_full = nullptr;
-		std::string err;
-		auto nccl_ok = [&](ncclResult_t r, const char *what) {
-			if (r == ncclSuccess) return true;
-			if (err.empty()) err = std::string(what) + ": " + R.GetErrorString(r);
-			return false;
-		};
-		// one process, one node: the communicators bootstrap over the loopback interface unless the caller chose one;
-		// the caller's environment is put back as it was (a later multi-node initialisation in this process must not
-		// inherit the loopback)
-		// (RCCL takes the interface from the process environment and from nowhere else: two of this library's calls are
-		// kept apart by a lock; a caller whose OTHER threads read or write the environment meanwhile sets
-		// NCCL_SOCKET_IFNAME itself before its first call -- the library then leaves the environment alone, andi_hip.h)
-		static std::mutex env_lock;
-		bool ok;
-		{
-			std::lock_guard<std::mutex> guard(env_lock);
-			const bool had_ifname = getenv("NCCL_SOCKET_IFNAME") != nullptr;
-			if (!had_ifname) setenv("NCCL_SOCKET_IFNAME", "lo", 0);
-			ok = nccl_ok(R.CommInitAll(comms.data(), (int)ndev, devs.data()), "ncclCommInitAll");
-			if (!had_ifname) unsetenv("NCCL_SOCKET_IFNAME");
-		}
-		if (ok && hipSetDevice(devs[0]) != hipSuccess) ok = false, err = "hipSetDevice";
-		if (ok && hipMalloc((void **)&d_full, n * n * sizeof(andi_hip_model)) != hipSuccess) ok = false, err = "allocating the gathered matrix";
-		if (ok) {
-			ok = nccl_ok(R.GroupStart(), "ncclGroupStart");
-			for (size_t d = 1; d < ndev && ok; ++d) {
-				const size_t bytes = (last[d] - first[d]) * n * sizeof(andi_hip_model);
-				// (every call with the device of its communicator current)
-				ok = hipSetDevice(devs[d]) == hipSuccess &&
-					 nccl_ok(R.Send(dv[d].d_rows, bytes, ncclUint8, 0, comms[d], dv[d].ctx->stream), "ncclSend") &&
-					 hipSetDevice(devs[0]) == hipSuccess &&
-					 nccl_ok(R.Recv(d_full + first[d] * n, bytes, ncclUint8, (int)d, comms[0], dv[0].ctx->stream), "ncclRecv");
-			}
-			if (!nccl_ok(R.GroupEnd(), "ncclGroupEnd")) ok = false;
-		}
-		if (ok) { // the first device's own block, then everything to the host
-			hipError_t e = hipSetDevice(devs[0]);
-			if (e == hipSuccess)
-				e = hipMemcpyAsync(d_full + first[0] * n, dv[0].d_rows, (last[0] - first[0]) * n * sizeof(andi_hip_model),
-								   hipMemcpyDeviceToDevice, dv[0].ctx->stream);
-			for (size_t d = 1; d < ndev && e == hipSuccess; ++d) {
-				e = hipSetDevice(devs[d]);
-				if (e == hipSuccess) e = hipStreamSynchronize(dv[d].ctx->stream);
-			}
-			if (e == hipSuccess) e = hipSetDevice(devs[0]);
-			if (e == hipSuccess) e = hipStreamSynchronize(dv[0].ctx->stream);
-			if (e == hipSuccess) e = hipMemcpy(M, d_full, n * n * sizeof(andi_hip_model), hipMemcpyDeviceToHost);
-			if (e != hipSuccess) ok = false, err = std::string("gathering the matrix: ") + hipGetErrorString(e);
-		}
-		for (auto cm : comms)
-			if (cm) (void)R.CommDestroy(cm);
-		if (d_full) {
-			(void)hipSetDevice(devs[0]);
-			(void)andi_arena::dev_free(d_full);
-		}
-		if (!ok) { // RCCL unusable on this box: the rows are still in HBM -- copy every block to the host directly
-			snprintf(g_last_gather, sizeof g_last_gather, "direct (rccl: %.160s)", err.c_str());
-			for (size_t d = 0; d < ndev && !rc; ++d)
-				if (andi_hip_copy_to_host(dv[d].ctx, M + first[d] * n, dv[d].d_rows, (last[d] - first[d]) * n * sizeof(andi_hip_model))) {
-					first_error = std::string("row copy: ") + andi_hip_last_error(dv[d].ctx);
-					rc = 1;
-				}
-		}
-	}
-	if (rc) set_err(errbuf, errlen, "%s", first_error.empty() ? "andi_hip_dist_matrix failed" : first_error.c_str());
-	const double t_gathered = now_ms();
-
-	for (auto &D : dv) {
-		if (!D.ctx) {
-			for (auto *cx : D.sorters) andi_hip_ctx_destroy(cx);
-			if (D.prep) andi_hip_ctx_destroy(D.prep);
-			if (D.up) andi_hip_ctx_destroy(D.up);
-			continue;
-		}
-		for (auto *cx : D.sorters) andi_hip_ctx_destroy(cx);
-		for (auto *e : D.slots)
-			if (e) andi_hip_esa_free(D.ctx, e);
-		if (D.d_rows) andi_hip_dev_free(D.ctx, D.d_rows);
-		if (D.Q) andi_hip_queries_free(D.ctx, D.Q);
-		if (D.pinned) host_pool::pinned_put(D.pinned, D.pinned_bytes);
-		for (hipEvent_t ev : D.pinned_free)
-			if (ev) (void)hipEventDestroy(ev);
-		if (D.prep) andi_hip_ctx_destroy(D.prep);
-		if (D.up) andi_hip_ctx_destroy(D.up);
-		andi_hip_ctx_destroy(D.ctx);
-	}
-	if (trace) fprintf(stderr, "andi_hip_dist_matrix trace: call total %.1f ms (gather %.1f, slots, queries and contexts released %.1f)\n", now_ms() - t_call, t_gathered - t_drivers_done, now_ms() - t_gathered);
-	return rc;
-}
-
-} // extern "C"

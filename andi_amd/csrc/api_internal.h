@@ -1,0 +1,252 @@
+// api_internal.h — what the library's host translation units share (api.hip, scan_call.hip, seam.hip): the objects
+// behind the C-ABI's handles, the error helpers, and the helpers the scan call and the seam take from api.hip.
+// Private: no kernel code, nothing of it is exported (the functions declared here are hidden).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "andi_dev.h"
+#include "andi_hip.h"
+#include "dev_arena.h"
+#include "esa_build.h"
+#include "knobs.h"
+#include "scan.h"
+
+// scratch per (subject, segment): three states, two count vectors, the marks, the exit position, a list slot, a published anchor
+#define ANDI_SLOT_BYTES (3 * sizeof(ChainState) + 2 * 16 * sizeof(uint32_t) + ANDI_COLD_MARKS * sizeof(ColdMark) + 4 + 8 + 8)
+
+struct EventPair {
+	hipEvent_t a, b;
+	int kind; // 0 build, 1 scan, 2 stitch
+};
+
+struct andi_hip_ctx {
+	int device = 0;
+	size_t queries_hint = 0; // andi_hip_ctx_expect_queries
+	hipStream_t stream = nullptr;
+	hipStream_t side_stream = nullptr; // pass A's second kernel runs beside the first
+	hipEvent_t side_fork = nullptr, side_join = nullptr;
+	std::string err;
+	// scan scratch
+	void *scratch = nullptr;
+	size_t scratch_bytes = 0;
+	// descriptor staging (pinned host + device), guarded by desc_done
+	void *desc_host = nullptr;
+	void *desc_dev = nullptr;
+	size_t desc_bytes = 0;
+	hipEvent_t desc_done = nullptr;
+	unsigned long long *d_fixups = nullptr;
+	// batched index builds: items (pinned host + device), guarded by ib_done
+	void *ib_host = nullptr, *ib_dev = nullptr;
+	size_t ib_cap = 0;
+	hipEvent_t ib_done = nullptr;
+	// index builds queued since the last scan looked at their flags (pinned host words the build kernels write)
+	hipEvent_t built = nullptr;
+	bool builds_pending = false;
+	// device suffix sorter: workspace, two pinned ints
+	void *sa_ws = nullptr;
+	size_t sa_ws_bytes = 0;
+	int32_t *sa_pinned = nullptr;
+	int stream_prio = 0; // of stream and side_stream (host_pool: they go back there)
+	uint32_t *h_quad_waves = nullptr; // pinned: the length of k_lane_quad's list of a scan call
+	hipStream_t coop_stream = nullptr; // routed scan calls: pass A by wavefronts runs beside the lane scan's kernels
+	hipEvent_t coop_fork = nullptr, coop_join = nullptr, l2_fork = nullptr, l2_join = nullptr;
+	uint32_t *h_any_left = nullptr;    // pinned: [0] the wavefront kernel handed some pair back, [1 + k] the layout's counter restitch_count[k] (ANDI_LANE_WAVES: wavefronts of the lane layout, ...)
+	void *pool_scratch = nullptr;      // pass A by wavefronts with pooled walks (coop_pool.h): a scratch per resident wavefront
+	size_t pool_bytes = 0;
+	uint32_t pool_waves = 0;
+	bool pool_failed = false;          // its allocation failed once: not tried again by this context
+	void *scratch2 = nullptr;          // the second lane layout (those pairs), grown on demand
+	size_t scratch2_bytes = 0;
+	unsigned long long *d_route = nullptr; // routed scan calls: query nucleotides whose pass A ran by wavefronts / by lanes, pairs handed back (read with the timings)
+	std::vector<EventPair> pending;
+	andi_hip_timings acc{};
+};
+
+struct andi_hip_esa {
+	uint8_t *S = nullptr;
+	int32_t *SA = nullptr, *LCP = nullptr, *CLD = nullptr;
+	uint8_t *FVC = nullptr;
+	int4 *tab = nullptr;
+	int32_t *min_scratch = nullptr;
+	uint2 *deep = nullptr;
+	uint8_t *Nraw = nullptr;              // 4-bit symbols for the lane scan: N0 and N1 with their padding
+	uint8_t *N0 = nullptr, *N1 = nullptr;
+	uint32_t *Praw = nullptr, *P = nullptr; // the text bit-sliced (EsaDev.P; packed from N0 when a scan call wants it), a block of padding in front
+	uint32_t *rec = nullptr;    // the suffixes' records in suffix-array order, left by the device sorter (sa_device.hip) for the index build
+	bool rec_valid = false;
+	uint16_t *rec2 = nullptr;   // ... and the symbols behind their first deepK (same validity)
+	int32_t *flags = nullptr;   // device, 4 ints
+	int32_t *h_flags = nullptr; // the same 4 ints as the host sees them (flags live in pinned host memory)
+	int32_t deepK = 0;
+	int32_t deepK_cap = 0; // the depth the table was allocated for
+	int32_t n = 0;
+	int32_t thr = 0;
+	size_t cap = 0;     // characters the buffers were sized for (>= n)
+	size_t ref_cap = 0; // same for the reference arrays
+	bool ref_built = false;   // LCP, CLD, FVC, tab valid
+	bool index_built = false; // deep, flags valid
+	int deep_ext = 0;         // the form of the table's entries of K-mers that occur once (andi_dev.h: 0 plain, 1 extended, 2 short extended)
+	size_t bytes = 0;
+};
+
+struct andi_hip_queries {
+	uint8_t *pool = nullptr;
+	uint8_t *nib = nullptr;       // the pool as 4-bit symbols
+	uint32_t *planes = nullptr;   // ... bit-sliced (EsaDev.P)
+	int32_t *h_foreign = nullptr; // pinned: set if the pool holds bytes outside the alphabet
+	uint64_t *d_off = nullptr;
+	uint32_t *d_len = nullptr;
+	uint32_t *d_sep = nullptr;    // contig separators of every sequence (k_sep_counts: for the routing of the scan)
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> len;
+	size_t nq = 0;
+	uint64_t total_nt = 0;
+	// segmentation cache
+	uint32_t seg = 0;
+	uint32_t *d_qseg_start = nullptr;
+	uint32_t *d_seg2query = nullptr;
+	uint32_t total_segs = 0;
+	// a second one: the long segments of pass A by wavefronts (scan_coop.hip), kept beside the call's own so that a
+	// call that falls back to the lane scan does not cut the queries anew every time
+	uint32_t c_seg = 0;
+	uint32_t *c_qseg_start = nullptr;
+	uint32_t *c_seg2query = nullptr;
+	uint32_t c_total_segs = 0;
+};
+
+namespace {
+
+void set_err(char *buf, size_t len, const char *fmt, ...) {
+	if (!buf || !len) return;
+	va_list ap;
+	va_start(ap, fmt);
+	vsnprintf(buf, len, fmt, ap);
+	va_end(ap);
+}
+
+int fail(andi_hip_ctx *ctx, const char *what, hipError_t e) {
+	if (ctx) {
+		ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+	}
+	return 1;
+}
+
+#define HIP_TRY(ctx, call)                                                                         \
+	do {                                                                                           \
+		hipError_t e__ = (call);                                                                   \
+		if (e__ != hipSuccess) return fail((ctx), #call, e__);                                     \
+	} while (0)
+
+template <typename T>
+hipError_t dmalloc(T **p, size_t count) {
+	return andi_arena::dev_malloc((void **)p, count * sizeof(T)); // (out of large chunks: dev_arena.h)
+}
+
+void resolve_events(andi_hip_ctx *ctx) {
+	for (auto &ev : ctx->pending) {
+		float ms = 0.f;
+		if (hipEventSynchronize(ev.b) == hipSuccess && hipEventElapsedTime(&ms, ev.a, ev.b) == hipSuccess) {
+			if (ev.kind == 0) {
+				ctx->acc.build_ms += ms;
+				ctx->acc.build_launches++;
+			} else if (ev.kind == 1) {
+				ctx->acc.scan_ms += ms;
+				ctx->acc.scan_launches++;
+			} else {
+				ctx->acc.stitch_ms += ms;
+				ctx->acc.stitch_launches++;
+			}
+		}
+		(void)hipEventDestroy(ev.a);
+		(void)hipEventDestroy(ev.b);
+	}
+	ctx->pending.clear();
+}
+
+struct Timed {
+	andi_hip_ctx *ctx;
+	EventPair ev;
+	bool ok;
+	Timed(andi_hip_ctx *c, int kind) : ctx(c), ok(false) {
+		ev.kind = kind;
+		if (hipEventCreate(&ev.a) != hipSuccess) return;
+		if (hipEventCreate(&ev.b) != hipSuccess) {
+			(void)hipEventDestroy(ev.a);
+			return;
+		}
+		ok = hipEventRecord(ev.a, c->stream) == hipSuccess;
+	}
+	void stop() {
+		if (!ok) return;
+		(void)hipEventRecord(ev.b, ctx->stream);
+		ctx->pending.push_back(ev);
+		ok = false;
+		if (ctx->pending.size() > 256) resolve_events(ctx);
+	}
+	~Timed() { // an error exit before stop(): the events go with the timer
+		if (!ok) return;
+		(void)hipEventDestroy(ev.a);
+		(void)hipEventDestroy(ev.b);
+	}
+	Timed(const Timed &) = delete;
+	Timed &operator=(const Timed &) = delete;
+};
+
+} // namespace
+
+// The seam's queries, packed ONCE on the host (round 4): every device uploads the 4-bit pool -- a quarter of what the
+// byte pool and its packed copy were, from one host copy shared by the device threads -- and unpacks the bytes the rare
+// byte-wise paths read (k_unpack_symbols).  C4's 6.5 GB of queries took 0.35 s per device as bytes from pageable memory.
+struct PackedQueries {
+	std::vector<uint64_t> off;
+	std::vector<uint32_t> len;
+	uint64_t total_nt = 0;
+	size_t pool_bytes = 0;
+	uint8_t *nib = nullptr; // pool_bytes / 2 bytes: the pool as the device's pack kernel would leave it
+	int foreign = 0;        // a byte outside the alphabet (the scan refuses the queries then)
+	std::string err;
+	std::atomic<int> users{0}; // devices that have not staged yet: the last one lets the host copy go (gigabytes: not at the call's end)
+	void release() {
+		free(nib);
+		nib = nullptr;
+	}
+	~PackedQueries() { release(); }
+};
+
+#pragma GCC visibility push(hidden)
+
+// api.hip
+EsaDev esa_view(const andi_hip_esa *e, int mode);
+int pick_deep_k(size_t n, size_t queries);
+int ctx_create(andi_hip_ctx **out, int device, char *errbuf, size_t errlen, bool high_priority);
+int esa_reserve(andi_hip_ctx *ctx, size_t cap, andi_hip_esa **out);
+int esa_upload(andi_hip_ctx *ctx, andi_hip_esa *e, const char *RS, const int32_t *SA, size_t n,
+			   size_t threshold, hipEvent_t done = nullptr); // done: do not wait -- the event says when RS (and SA) may be reused
+int esa_from_query(andi_hip_ctx *ctx, andi_hip_esa *e, const andi_hip_queries *Q, size_t i, size_t threshold);
+int queries_gc_counts(andi_hip_ctx *ctx, const andi_hip_queries *Q, std::vector<unsigned long long> &out);
+int esa_sort_suffixes(andi_hip_ctx *ctx, andi_hip_esa *e);
+
+int pack_queries_host(const andi_hip_seq *seqs, size_t n, int threads, PackedQueries &P);
+int queries_stage_packed(andi_hip_ctx *ctx, const PackedQueries &P, andi_hip_queries **out);
+
+// Streams, pinned buffers and the pooled kernel's scratch kept from one call to the next (api.hip: ONE pool per process)
+namespace host_pool {
+hipError_t stream_get(hipStream_t *out, int device, int prio);
+void stream_put(hipStream_t s, int device, int prio);
+hipError_t pinned_get(void **out, size_t bytes);
+void pinned_put(void *p, size_t bytes);
+void *word_get();
+void word_put(void *p);
+void *scratch_get(int device, size_t bytes);
+void scratch_put(int device, void *p, size_t bytes);
+} // namespace host_pool
+
+#pragma GCC visibility pop

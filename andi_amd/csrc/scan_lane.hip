@@ -1297,16 +1297,15 @@ static hipError_t lane_cold(const ScanArgs &a, dim3 grid, hipStream_t st) {
 			default: k_lane_cold<EXACT, 8, false><<<grid, BLOCK, 0, st>>>(a); break;
 		}
 	}
-	if (counted) {
+	hipError_t e = hipSuccess;
+	if (counted) { // (an error here still joins the side stream: what it runs reads the call's scratch)
 		(void)hipMemcpyAsync(a.h_quad_waves, a.restitch_count + ANDI_QUAD_WAVES, sizeof(uint32_t), hipMemcpyDeviceToHost, a.side_stream);
-		hipError_t e = hipStreamSynchronize(a.side_stream);
-		if (e != hipSuccess) return e;
-		e = andi_launch_lane_quad_small(a, *a.h_quad_waves, a.side_stream);
-		if (e != hipSuccess) return e;
+		e = hipStreamSynchronize(a.side_stream);
+		if (e == hipSuccess) e = andi_launch_lane_quad_small(a, *a.h_quad_waves, a.side_stream);
 		(void)hipEventRecord(a.side_join, a.side_stream);
 	}
 	if (side) (void)hipStreamWaitEvent(st, a.side_join, 0);
-	return hipGetLastError();
+	return e != hipSuccess ? e : hipGetLastError();
 }
 
 static hipError_t pair_offsets(const ScanArgs &a, hipStream_t st) {

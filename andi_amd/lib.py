@@ -471,7 +471,7 @@ def last_gather():
 
 
 def row_block(total, parts, k):
-    """the seam's own tiling of the subject rows over `parts` devices (api.hip: row_block): [first, last) of part k"""
+    """the seam's own tiling of the subject rows over `parts` devices (seam.hip: row_block): [first, last) of part k"""
     f, l = C.c_size_t(0), C.c_size_t(0)
     load().andi_hip_row_block(total, parts, k, C.byref(f), C.byref(l))
     return int(f.value), int(l.value)

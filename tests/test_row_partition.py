@@ -1,4 +1,4 @@
-"""The seam's tiling of the subject rows over the GPUs of a node (api.hip: row_block, the parallel loop of
+"""The seam's tiling of the subject rows over the GPUs of a node (seam.hip: row_block, the parallel loop of
 src/dist_hack.h:46-47) against the one the one-process-per-GPU entry uses (andi_amd/shard.py): the same contiguous blocks for
 every n = 1 ... 3085 (BASELINE's config 3) and 1 ... 8 parts -- through the C-ABI (andi_hip_row_block), no GPU touched."""
 import ctypes as C
