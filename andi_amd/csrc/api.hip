@@ -921,10 +921,34 @@ void andi_hip_queries_free(andi_hip_ctx *ctx, andi_hip_queries *q) {
 	if (!q) return;
 	if (ctx) (void)hipSetDevice(ctx->device);
 	(void)hipDeviceSynchronize();
-	void *bufs[] = {q->pool, q->nib, q->planes, q->d_off, q->d_len, q->d_sep, q->d_qseg_start, q->d_seg2query, q->c_qseg_start, q->c_seg2query};
-	for (void *b : bufs) (void)andi_arena::dev_free(b, false);
-	host_pool::word_put(q->h_foreign);
+	void *own[] = {q->d_qseg_start, q->d_seg2query, q->c_qseg_start, q->c_seg2query}; // (every set's, a view's too)
+	for (void *b : own) (void)andi_arena::dev_free(b, false);
+	if (q->owns_pool) {
+		void *bufs[] = {q->pool, q->nib, q->planes, q->d_off, q->d_len, q->d_sep};
+		for (void *b : bufs) (void)andi_arena::dev_free(b, false);
+		host_pool::word_put(q->h_foreign);
+	}
 	delete q;
+}
+
+// Queries [first, first + count) of a staged set, on the parent's device buffers: the scan reaches a query's symbols only
+// through qoff[] (scan_dev.h), so a view's offsets are the parent's own, and the pool stays where it is.  Nothing is
+// copied or uploaded; the view cuts its own segments (ensure_segmentation) when a scan first asks for them.
+int andi_hip_queries_view(andi_hip_ctx *ctx, const andi_hip_queries *q, size_t first, size_t count, andi_hip_queries **out) {
+	if (!ctx || !q || !out || count == 0 || first > q->nq || count > q->nq - first) {
+		if (ctx) ctx->err = "andi_hip_queries_view: bad arguments";
+		return 1;
+	}
+	auto *v = new andi_hip_queries;
+	v->owns_pool = false;
+	v->pool = q->pool, v->nib = q->nib, v->planes = q->planes, v->h_foreign = q->h_foreign;
+	v->d_off = q->d_off + first, v->d_len = q->d_len + first, v->d_sep = q->d_sep ? q->d_sep + first : nullptr;
+	v->off.assign(q->off.begin() + first, q->off.begin() + first + count);
+	v->len.assign(q->len.begin() + first, q->len.begin() + first + count);
+	v->nq = count;
+	for (uint32_t l : v->len) v->total_nt += l;
+	*out = v;
+	return 0;
 }
 
 // 4-bit symbols of a byte string, as the device's pack kernel makes them (scan_lane.hip: symbol_of, in_alphabet): byte j of

@@ -98,6 +98,9 @@ struct andi_hip_esa {
 };
 
 struct andi_hip_queries {
+	// a view (andi_hip_queries_view) shares its parent's pool, nib, planes and h_foreign, and its d_off, d_len and d_sep point
+	// into the parent's arrays; it owns only its segmentation caches
+	bool owns_pool = true;
 	uint8_t *pool = nullptr;
 	uint8_t *nib = nullptr;       // the pool as 4-bit symbols
 	uint32_t *planes = nullptr;   // ... bit-sliced (EsaDev.P)

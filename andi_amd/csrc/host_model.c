@@ -288,3 +288,59 @@ size_t andi_hip_format_distances(const andi_hip_model *M, const char *const *nam
 	if (warn_flags) *warn_flags = flags;
 	return o.len;
 }
+
+/* The query-versus-reference table (andi_hip_dist_rect's two cross blocks, include/andi_hip.h): query q is row nr + q of
+ * refs ++ queries, reference r is column r, so a cell is what fmt_rows computes for that pair of the union --
+ * model_average(M[i][j], M[j][i]) with M[i][j] = MQR[q][r], M[j][i] = MRQ[r][q] (extra_verbose: MQR[q][r] alone) -- and the
+ * low-coverage check is the union's for i = r < j = nr + q.  One thread: the table is nq x nr, not n x n. */
+size_t andi_hip_format_distances_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR,
+									  const char *const *ref_names, size_t nr, const char *const *query_names, size_t nq,
+									  int model, int extra_verbose, int truncate_names, int warnings,
+									  char *out, size_t cap, char *warnbuf, size_t warncap, int *warn_flags) {
+	double *D = malloc((nq && nr ? nq * nr : 1) * sizeof *D);
+	if (!D) return 0;
+	sink o = {out, cap, 0}, w = {warnbuf, warncap, 0};
+	int flags = 0, scientific = 0;
+	for (size_t q = 0; q < nq; q++)
+		for (size_t r = 0; r < nr; r++) {
+			const andi_hip_model *qr = &MQR[q * nr + r], *rq = &MRQ[r * nq + q];
+			andi_hip_model datum = extra_verbose ? *qr : andi_hip_model_average(qr, rq);
+			const double d = D[q * nr + r] = andi_hip_estimate(&datum, model);
+			if (d > 0 && d < 0.001) scientific = 1;
+			if (!warnings) continue;
+			if (isnan(d)) {
+				flags |= 1;
+				put(&w,
+					"For the two sequences '%s' and '%s' the distance computation failed and "
+					"is reported as nan. Please refer to the documentation for further "
+					"details.\n",
+					query_names[q], ref_names[r]);
+			}
+			andi_hip_model upper = extra_verbose ? *rq : datum; /* (the union's row r, column nr + q) */
+			if (!isnan(andi_hip_estimate(&upper, model))) {
+				const double c1 = andi_hip_model_coverage(rq), c2 = andi_hip_model_coverage(qr);
+				if (c1 < 0.2 || c2 < 0.2) {
+					flags |= 2;
+					put(&w,
+						"For the two sequences '%s' and '%s' very little homology was found "
+						"(%f and %f, respectively).\n",
+						ref_names[r], query_names[q], c1, c2);
+				}
+			}
+		}
+	put(&o, "%zu %zu\n", nq, nr);
+	put(&o, "%10s", "");
+	for (size_t r = 0; r < nr; r++) put(&o, truncate_names ? " %.10s" : " %s", ref_names[r]);
+	put(&o, "\n");
+	const char *f = scientific ? " %1.4e" : " %1.4f";
+	for (size_t q = 0; q < nq; q++) {
+		put(&o, truncate_names ? "%-10.10s" : "%-10s", query_names[q]);
+		for (size_t r = 0; r < nr; r++) put(&o, f, D[q * nr + r]);
+		put(&o, "\n");
+	}
+	free(D);
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
+	if (warnbuf && warncap) warnbuf[w.len < warncap ? w.len : warncap - 1] = '\0';
+	if (warn_flags) *warn_flags = flags;
+	return o.len;
+}

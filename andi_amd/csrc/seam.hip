@@ -1,5 +1,6 @@
 // seam.hip — andi_hip_dist_matrix (include/andi_hip.h), the one-call replacement of distMatrix/distMatrixLM
-// (src/dist_hack.h:34-96), with its row partition and gather.
+// (src/dist_hack.h:34-96), with its row partition and gather; andi_hip_dist_rect, the cross blocks of that matrix for a
+// set of references and a set of queries, on the same loop.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h> // types only: librccl is loaded on demand (dlopen), see rccl() below
 #include <dlfcn.h>
@@ -35,6 +36,11 @@
 // first device -- RCCL send/recv over xGMI, every peer on its own link -- followed by
 // one copy of the matrix to the host.  (One device, several contexts on one device,
 // or no usable RCCL: every block is copied to the host matrix directly.)
+//
+// Both calls are one loop over ROW GROUPS: a group's subjects, staged sequences s0 ... s0 + rows - 1, are each scanned
+// against one column view of the staged set (andi_hip_queries_view).  The square call has one group, every sequence
+// against all of them (its own column the diagonal); andi_hip_dist_rect stages refs ++ queries and has two -- the
+// references against view(nr, nq), the queries against view(0, nr) -- with no diagonal in either.
 namespace {
 struct Prepared {
 	size_t idx = 0;
@@ -112,7 +118,7 @@ struct SubjectPool {
 	size_t consumed = 0; // subjects taken by the devices, guarded by mu
 	bool abort_flag = false;
 	std::string first_error;
-	size_t rows_done = 0; // guarded by mu (progress)
+	size_t pairs_done = 0; // guarded by mu (progress)
 	std::vector<std::thread> workers;
 
 	SubjectPool(const andi_hip_seq *s, const andi_hip_opts &opts, std::vector<size_t> ord, size_t win) : seqs(s), o(opts), order(std::move(ord)), window(win) {}
@@ -231,14 +237,28 @@ struct QueryPacker {
 	~QueryPacker() { join(); }
 };
 
+// a block of rows of one call: subjects s0 ... s0 + rows - 1 of the staged set, each against the queries v0 ... v0 + vn - 1
+// of it, row s0 + r to out + r * vn.  diagonal: the view is the whole set and subject i is query i (self = i: the square
+// call); otherwise no subject meets itself (self = -1).  hint: andi_hip_ctx_expect_queries for its subjects.
+struct RowGroup {
+	size_t s0, rows, v0, vn;
+	andi_hip_model *out;
+	bool diagonal;
+	size_t hint;
+	std::vector<size_t> first, last; // the devices' row blocks (staged-set indices)
+};
+
 // what every device's driver of one call shares
 struct SeamCall {
-	andi_hip_model *M;
-	const andi_hip_seq *seqs;
+	const char *name;         // the entry point (error messages, trace lines)
+	const andi_hip_seq *seqs; // the staged set
 	size_t n;
 	andi_hip_opts o;
+	std::vector<RowGroup> groups;
+	size_t width = 0, hint_max = 0; // the widest group's vn, the largest hint
+	size_t pairs_total = 0;         // (progress)
+	bool allow_rccl = false;        // (the square call's gather)
 	std::vector<int> devs;
-	std::vector<size_t> first, last; // the devices' row blocks
 	size_t rs_cap;                   // the longest subject's RS
 	bool dev_prep;                   // RS and suffix arrays made on the device (not sa_on_host)
 	size_t batch_max;
@@ -260,6 +280,7 @@ struct Driver {
 	andi_hip_ctx *up = nullptr;   // uploads (a thread and a stream of their own: the copies of batch k + 1 run beside the sorts of batch k)
 	std::vector<andi_hip_ctx *> sorters; // suffix sorts of a batch's subjects side by side (streams and workspaces of their own)
 	andi_hip_queries *Q = nullptr;
+	std::vector<andi_hip_queries *> views; // per group: its column view of Q (null: Q whole)
 	andi_hip_model *d_rows = nullptr; // rccl: the whole row block; direct: one batch of rows
 	size_t pinned_bytes = 0;
 	char *pinned = nullptr;           // staging buffers for RS (two: one is filled while the other's copy runs): uploads from pinned memory go through the DMA engines, beside a scan
@@ -267,6 +288,10 @@ struct Driver {
 	std::vector<andi_hip_esa *> slots; // sets x batch
 	std::vector<unsigned long long> gcs; // G+C of every sequence (calc_gc, src/sequence.c:197-208)
 	size_t rows = 0, batch = 0, nbatches = 0, sets = 0;
+	struct Batch {
+		size_t g, i0, nb; // its group, first subject, size
+	};
+	std::vector<Batch> batches; // (no batch spans two groups: one scan call has one view)
 	char eb[256] = "";
 	// hand-over between the stages
 	std::mutex pm;
@@ -277,7 +302,9 @@ struct Driver {
 	// the trace (device 0)
 	double t_ctx = 0, t_queries = 0, t_slots = 0, p_take = 0, p_upload = 0, p_sort = 0, p_build = 0, acc_wait = 0, acc_scan = 0, acc_copy = 0;
 
-	Driver(const SeamCall &call, size_t k) : C(call), d(k), dev(call.devs[k]), rows(call.last[k] - call.first[k]) {}
+	Driver(const SeamCall &call, size_t k) : C(call), d(k), dev(call.devs[k]) {
+		for (const RowGroup &G : C.groups) rows += G.last[d] - G.first[d];
+	}
 
 	void bail(const char *what, andi_hip_ctx *cx) {
 		char msg[512];
@@ -296,10 +323,11 @@ struct Driver {
 		}
 		pcv.notify_all();
 	}
-	// batch k: its first subject, its size, its set of slots
-	size_t batch_first(size_t k) const { return C.first[d] + k * batch; }
-	size_t batch_size(size_t k) const { return std::min(batch, C.last[d] - batch_first(k)); }
+	// batch k: its first subject, its size, its set of slots, its group
+	size_t batch_first(size_t k) const { return batches[k].i0; }
+	size_t batch_size(size_t k) const { return batches[k].nb; }
 	andi_hip_esa **batch_set(size_t k) { return slots.data() + (k % sets) * batch; }
+	const RowGroup &batch_group(size_t k) const { return C.groups[batches[k].g]; }
 	size_t sets_for(size_t bt) const { // (low_memory: one index resident at a time)
 		const size_t nb = (rows + bt - 1) / bt;
 		return C.o.low_memory ? (size_t)1 : (nb > 2 && !C.dev_prep ? (size_t)3 : (nb > 1 ? (size_t)2 : (size_t)1)); // (the third set is the uploads')
@@ -321,7 +349,7 @@ bool Driver::open() {
 	if (ctx_create(&prep, dev, eb, sizeof eb, true)) return bail("creating a context", nullptr), false;
 	if (!C.dev_prep) {
 		if (ctx_create(&up, dev, eb, sizeof eb, true)) return bail("creating a context", nullptr), false;
-		andi_hip_ctx_expect_queries(up, n - 1);
+		andi_hip_ctx_expect_queries(up, C.hint_max);
 	}
 	// A suffix sort is two dozen launches with two or three host round trips between them (sa_device.hip): 0.73 ms per
 	// 9.8 M characters of which the device is busy half.  The subjects of a batch are sorted by up to four host threads,
@@ -337,11 +365,12 @@ bool Driver::open() {
 	for (size_t w = 1; w < sort_width; ++w) {
 		andi_hip_ctx *cx = nullptr;
 		if (ctx_create(&cx, dev, eb, sizeof eb, true)) return bail("creating a context", nullptr), false;
-		andi_hip_ctx_expect_queries(cx, n - 1);
+		andi_hip_ctx_expect_queries(cx, C.hint_max);
 		sorters.push_back(cx);
 	}
-	andi_hip_ctx_expect_queries(ctx, n - 1);
-	andi_hip_ctx_expect_queries(prep, n - 1);
+	// (the slots are sized for the largest hint; every batch is staged with its group's: upload_loop, stage_loop)
+	andi_hip_ctx_expect_queries(ctx, C.hint_max);
+	andi_hip_ctx_expect_queries(prep, C.hint_max);
 	lap(t_ctx);
 	// Subject slots: device buffers sized for the longest genome, reused batch after batch (no
 	// allocation inside the loop).  Several subjects per scan call keep the GPU filled; low_memory
@@ -355,7 +384,9 @@ bool Driver::open() {
 			while (batch > 1 && sets_for(batch) * batch * per_slot > free_b / (2 * C.devs.size())) batch /= 2; // (as many sets as the batches will really have)
 		}
 	}
-	nbatches = (rows + batch - 1) / batch;
+	for (size_t g = 0; g < C.groups.size(); ++g)
+		for (size_t i = C.groups[g].first[d]; i < C.groups[g].last[d]; i += batch) batches.push_back({g, i, std::min(batch, C.groups[g].last[d] - i)});
+	nbatches = batches.size();
 	// Three sets of slots: while batch k is scanned, batch k + 2 is uploaded (no compute units needed) and batch k + 1
 	// is ready; the device's COMPUTE alternates strictly -- suffix sorts and index builds of batch k + 1, then the scan
 	// of batch k -- because side by side the staging kernels starve behind the workgroups of a scan that fills the
@@ -373,6 +404,11 @@ bool Driver::open() {
 	} else if (andi_hip_queries_stage(ctx, C.seqs, n, &Q)) {
 		return bail("staging queries", ctx), false;
 	}
+	for (const RowGroup &G : C.groups) {
+		andi_hip_queries *v = nullptr;
+		if (!(G.v0 == 0 && G.vn == n) && andi_hip_queries_view(ctx, Q, G.v0, G.vn, &v)) return bail("staging queries", ctx), false;
+		views.push_back(v);
+	}
 	if (C.dev_prep && queries_gc_counts(ctx, Q, gcs)) return bail("staging queries", ctx), false;
 	lap(t_queries);
 	for (size_t b = 0; b < sets * batch; ++b)
@@ -387,10 +423,10 @@ bool Driver::open() {
 		pinned = nullptr;
 	}
 	lap(t_pinned);
-	if (andi_hip_dev_alloc(ctx, (C.use_rccl ? rows : batch) * n * sizeof(andi_hip_model), (void **)&d_rows)) return bail("row buffer", ctx), false;
+	if (andi_hip_dev_alloc(ctx, (C.use_rccl ? rows : batch) * C.width * sizeof(andi_hip_model), (void **)&d_rows)) return bail("row buffer", ctx), false;
 	lap(t_slots);
 	t_slots += t_reserve + t_pinned;
-	if (C.trace && d == 0) fprintf(stderr, "andi_hip_dist_matrix trace: slots = device buffers of %zu slots %.1f ms + pinned upload buffer %.1f ms + row buffer %.1f ms\n", sets * batch, t_reserve, t_pinned, t_slots - t_reserve - t_pinned);
+	if (C.trace && d == 0) fprintf(stderr, "%s trace: slots = device buffers of %zu slots %.1f ms + pinned upload buffer %.1f ms + row buffer %.1f ms\n", C.name, sets * batch, t_reserve, t_pinned, t_slots - t_reserve - t_pinned);
 	return true;
 }
 
@@ -408,6 +444,7 @@ void Driver::upload_loop() {
 		plap.t = now_ms();
 		const size_t i0 = batch_first(k), nb = batch_size(k);
 		andi_hip_esa **set = batch_set(k);
+		andi_hip_ctx_expect_queries(up, batch_group(k).hint);
 		for (size_t b = 0; b < nb; ++b) { // uploads: beside whatever the device computes
 			Prepared *p = C.pool->take(i0 + b);
 			if (!p) return give_up();
@@ -455,6 +492,8 @@ void Driver::stage_loop() {
 		plap.t = now_ms();
 		const size_t i0 = batch_first(k), nb = batch_size(k);
 		andi_hip_esa **set = batch_set(k);
+		andi_hip_ctx_expect_queries(prep, batch_group(k).hint);
+		for (andi_hip_ctx *cx : sorters) andi_hip_ctx_expect_queries(cx, batch_group(k).hint);
 		// RS from the resident sequence (the threshold on the host, same libm: src/sequence.c:210-219), then its suffix array
 		auto text_and_sort = [&](andi_hip_ctx *cx, size_t b) -> const char * {
 			const size_t i = i0 + b, len = C.seqs[i].len;
@@ -508,7 +547,6 @@ void Driver::stage_loop() {
 
 // the scan thread (the driver's own): every batch once it is staged, its rows to the host or into the row block
 void Driver::scan_loop() {
-	const size_t n = C.n;
 	// the device's compute alternates between the stages where a slot set is free for it: stage k + 1, then scan k
 	const bool alternate = sets >= (C.dev_prep ? (size_t)2 : (size_t)3);
 	std::vector<int64_t> self(batch);
@@ -523,12 +561,14 @@ void Driver::scan_loop() {
 		lap(acc_wait);
 		const size_t i0 = batch_first(k), nb = batch_size(k);
 		andi_hip_esa **set = batch_set(k);
-		for (size_t b = 0; b < nb; ++b) self[b] = (int64_t)(i0 + b);
-		andi_hip_model *dst = C.use_rccl ? d_rows + (i0 - C.first[d]) * n : d_rows;
-		if (andi_hip_scan_rows(ctx, set, self.data(), nb, Q, C.o.model, C.o.segment, dst)) bail("scan", ctx), failed = true;
+		const RowGroup &G = batch_group(k);
+		const andi_hip_queries *view = views[batches[k].g] ? views[batches[k].g] : Q;
+		for (size_t b = 0; b < nb; ++b) self[b] = G.diagonal ? (int64_t)(i0 + b) : -1;
+		andi_hip_model *dst = C.use_rccl ? d_rows + (i0 - G.first[d]) * G.vn : d_rows;
+		if (andi_hip_scan_rows(ctx, set, self.data(), nb, view, C.o.model, C.o.segment, dst)) bail("scan", ctx), failed = true;
 		if (!failed && C.trace) (void)andi_hip_sync(ctx);
 		lap(acc_scan);
-		if (!failed && !C.use_rccl && andi_hip_copy_to_host(ctx, C.M + i0 * n, dst, nb * n * sizeof(andi_hip_model))) bail("row copy", ctx), failed = true;
+		if (!failed && !C.use_rccl && andi_hip_copy_to_host(ctx, G.out + (i0 - G.s0) * G.vn, dst, nb * G.vn * sizeof(andi_hip_model))) bail("row copy", ctx), failed = true;
 		if (!failed && C.use_rccl && andi_hip_sync(ctx)) bail("scan", ctx), failed = true; // the slots are reused
 		lap(acc_copy);
 		{
@@ -539,8 +579,8 @@ void Driver::scan_loop() {
 		pcv.notify_all();
 		if (!failed && C.o.progress) {
 			std::lock_guard<std::mutex> lk(C.pool->mu);
-			C.pool->rows_done += nb;
-			C.o.progress(C.pool->rows_done * (n - 1), n * n - n, C.o.ud);
+			C.pool->pairs_done += nb * (G.diagonal ? G.vn - 1 : G.vn);
+			C.o.progress(C.pool->pairs_done, C.pairs_total, C.o.ud);
 		}
 	}
 	{
@@ -560,7 +600,7 @@ void Driver::run() {
 	stager.join();
 	if (uploader.joinable()) uploader.join();
 	if (C.trace && d == 0)
-		fprintf(stderr, "andi_hip_dist_matrix trace (ms): contexts %.1f, queries %.1f, slots %.1f | staging thread: waiting for the host pool %.1f, subject %s %.1f, suffix arrays %.1f, index builds %.1f | scan thread: waiting for staged subjects %.1f, scans %.1f, row copies %.1f; driver total %.1f (%zu batches of %zu, %zu slot sets)\n",
+		fprintf(stderr, "%s trace (ms): contexts %.1f, queries %.1f, slots %.1f | staging thread: waiting for the host pool %.1f, subject %s %.1f, suffix arrays %.1f, index builds %.1f | scan thread: waiting for staged subjects %.1f, scans %.1f, row copies %.1f; driver total %.1f (%zu batches of %zu, %zu slot sets)\n", C.name,
 				t_ctx, t_queries, t_slots, p_take, C.dev_prep ? "texts written on the device" : "uploads", p_upload, p_sort, p_build, acc_wait, acc_scan, acc_copy, now_ms() - C.t_call, nbatches, batch, sets);
 }
 
@@ -570,6 +610,8 @@ void Driver::close() {
 	for (auto *e : slots)
 		if (e) andi_hip_esa_free(ctx, e);
 	if (d_rows) andi_hip_dev_free(ctx, d_rows);
+	for (auto *v : views)
+		if (v) andi_hip_queries_free(ctx, v);
 	if (Q) andi_hip_queries_free(ctx, Q);
 	if (pinned) host_pool::pinned_put(pinned, pinned_bytes);
 	for (hipEvent_t ev : pinned_free)
@@ -583,6 +625,8 @@ void Driver::close() {
 // still in HBM -- every block is copied to the host directly.  Returns nonzero (err set) if that fails too.
 int gather_rccl(const SeamCall &C, const std::vector<std::unique_ptr<Driver>> &dv, std::string &first_error) {
 	const size_t n = C.n, ndev = dv.size();
+	const std::vector<size_t> &first = C.groups[0].first, &last = C.groups[0].last; // (the square call's one group)
+	andi_hip_model *const M = C.groups[0].out;
 	const std::vector<int> &devs = C.devs;
 	Rccl &R = rccl();
 	std::vector<ncclComm_t> comms(ndev, nullptr);
@@ -613,19 +657,19 @@ int gather_rccl(const SeamCall &C, const std::vector<std::unique_ptr<Driver>> &d
 	if (ok) {
 		ok = nccl_ok(R.GroupStart(), "ncclGroupStart");
 		for (size_t d = 1; d < ndev && ok; ++d) {
-			const size_t bytes = (C.last[d] - C.first[d]) * n * sizeof(andi_hip_model);
+			const size_t bytes = (last[d] - first[d]) * n * sizeof(andi_hip_model);
 			// (every call with the device of its communicator current)
 			ok = hipSetDevice(devs[d]) == hipSuccess &&
 				 nccl_ok(R.Send(dv[d]->d_rows, bytes, ncclUint8, 0, comms[d], dv[d]->ctx->stream), "ncclSend") &&
 				 hipSetDevice(devs[0]) == hipSuccess &&
-				 nccl_ok(R.Recv(d_full + C.first[d] * n, bytes, ncclUint8, (int)d, comms[0], dv[0]->ctx->stream), "ncclRecv");
+				 nccl_ok(R.Recv(d_full + first[d] * n, bytes, ncclUint8, (int)d, comms[0], dv[0]->ctx->stream), "ncclRecv");
 		}
 		if (!nccl_ok(R.GroupEnd(), "ncclGroupEnd")) ok = false;
 	}
 	if (ok) { // the first device's own block, then everything to the host
 		hipError_t e = hipSetDevice(devs[0]);
 		if (e == hipSuccess)
-			e = hipMemcpyAsync(d_full + C.first[0] * n, dv[0]->d_rows, (C.last[0] - C.first[0]) * n * sizeof(andi_hip_model),
+			e = hipMemcpyAsync(d_full + first[0] * n, dv[0]->d_rows, (last[0] - first[0]) * n * sizeof(andi_hip_model),
 							   hipMemcpyDeviceToDevice, dv[0]->ctx->stream);
 		for (size_t d = 1; d < ndev && e == hipSuccess; ++d) {
 			e = hipSetDevice(devs[d]);
@@ -633,7 +677,7 @@ int gather_rccl(const SeamCall &C, const std::vector<std::unique_ptr<Driver>> &d
 		}
 		if (e == hipSuccess) e = hipSetDevice(devs[0]);
 		if (e == hipSuccess) e = hipStreamSynchronize(dv[0]->ctx->stream);
-		if (e == hipSuccess) e = hipMemcpy(C.M, d_full, n * n * sizeof(andi_hip_model), hipMemcpyDeviceToHost);
+		if (e == hipSuccess) e = hipMemcpy(M, d_full, n * n * sizeof(andi_hip_model), hipMemcpyDeviceToHost);
 		if (e != hipSuccess) ok = false, err = std::string("gathering the matrix: ") + hipGetErrorString(e);
 	}
 	for (auto cm : comms)
@@ -645,7 +689,7 @@ int gather_rccl(const SeamCall &C, const std::vector<std::unique_ptr<Driver>> &d
 	if (ok) return 0;
 	snprintf(g_last_gather, sizeof g_last_gather, "direct (rccl: %.160s)", err.c_str());
 	for (size_t d = 0; d < ndev; ++d)
-		if (andi_hip_copy_to_host(dv[d]->ctx, C.M + C.first[d] * n, dv[d]->d_rows, (C.last[d] - C.first[d]) * n * sizeof(andi_hip_model))) {
+		if (andi_hip_copy_to_host(dv[d]->ctx, M + first[d] * n, dv[d]->d_rows, (last[d] - first[d]) * n * sizeof(andi_hip_model))) {
 			first_error = std::string("row copy: ") + andi_hip_last_error(dv[d]->ctx);
 			return 1;
 		}
@@ -653,7 +697,7 @@ int gather_rccl(const SeamCall &C, const std::vector<std::unique_ptr<Driver>> &d
 }
 
 // the devices of the call (0, error text set: none usable)
-int pick_devices(const andi_hip_opts &o, size_t n, std::vector<int> &devs, char *errbuf, size_t errlen) {
+int pick_devices(const char *name, const andi_hip_opts &o, size_t n, std::vector<int> &devs, char *errbuf, size_t errlen) {
 	int visible = 0;
 	hipError_t e = hipGetDeviceCount(&visible);
 	if (e != hipSuccess || visible <= 0) {
@@ -673,7 +717,7 @@ int pick_devices(const andi_hip_opts &o, size_t n, std::vector<int> &devs, char 
 			return 1;
 		}
 	if (devs.empty()) {
-		set_err(errbuf, errlen, "andi_hip_dist_matrix: no device selected");
+		set_err(errbuf, errlen, "%s: no device selected", name);
 		return 1;
 	}
 	if (devs.size() > n) devs.resize(n); // at least one row each
@@ -695,64 +739,52 @@ bool want_rccl(const std::vector<int> &devs, size_t n) {
 	if (use_rccl && !rccl().ok) use_rccl = false;
 	return use_rccl;
 }
-} // namespace
-
-extern "C" {
-
-const char *andi_hip_last_gather(void) {
-	return g_last_gather;
-}
-
-void andi_hip_row_block(size_t total, size_t parts, size_t k, size_t *first, size_t *last) {
-	size_t f = 0, l = 0;
-	if (parts && k < parts) row_block(total, parts, k, f, l);
-	if (first) *first = f;
-	if (last) *last = l;
-}
-
-int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
-						 const andi_hip_opts *opts_in, char *errbuf, size_t errlen) {
-	if (!M || !seqs || n == 0) {
-		set_err(errbuf, errlen, "andi_hip_dist_matrix: bad arguments");
-		return 1;
-	}
-	SeamCall C;
-	C.M = M, C.seqs = seqs, C.n = n;
-	if (opts_in) {
-		C.o = *opts_in;
-	} else {
-		andi_hip_default_opts(&C.o);
-	}
-	const andi_hip_opts &o = C.o;
+// sequence checks of both calls (src/andi.c:296-304), before any HIP call; `what` names the set in the message
+bool check_seqs(const andi_hip_seq *seqs, size_t n, const char *what, char *errbuf, size_t errlen) {
 	for (size_t i = 0; i < n; ++i) {
 		if (!seqs[i].seq || seqs[i].len == 0) {
-			set_err(errbuf, errlen, "sequence %zu is empty", i); // src/andi.c:302-304
-			return 1;
+			set_err(errbuf, errlen, "%s %zu is empty", what, i); // src/andi.c:302-304
+			return false;
 		}
 		if (seqs[i].len > (size_t)(INT32_MAX - 1) / 2) { // src/andi.c:296-300
-			set_err(errbuf, errlen, "sequence %zu is too long. The technical limit is %zu.", i,
-					(size_t)(INT32_MAX - 1) / 2);
-			return 1;
+			set_err(errbuf, errlen, "%s %zu is too long. The technical limit is %zu.", what, i, (size_t)(INT32_MAX - 1) / 2);
+			return false;
 		}
 	}
-	if (pick_devices(o, n, C.devs, errbuf, errlen)) return 1;
+	return true;
+}
+
+// The call once its groups are set: devices, every group's tiling, the host pool, one driver per device, the gather.
+// dev_rows: the most devices the call can give a row each.
+int run_seam(SeamCall &C, size_t dev_rows, char *errbuf, size_t errlen) {
+	const andi_hip_opts &o = C.o;
+	const andi_hip_seq *seqs = C.seqs;
+	const size_t n = C.n;
+	if (pick_devices(C.name, o, dev_rows, C.devs, errbuf, errlen)) return 1;
 	const size_t ndev = C.devs.size();
-	C.use_rccl = want_rccl(C.devs, n);
+	C.use_rccl = C.allow_rccl && want_rccl(C.devs, n);
 
 	size_t longest = 0;
 	for (size_t i = 0; i < n; ++i) longest = std::max(longest, seqs[i].len);
 	C.rs_cap = 2 * longest + 1;
-	C.first.resize(ndev), C.last.resize(ndev);
-	size_t max_rows = 0;
-	for (size_t d = 0; d < ndev; ++d) {
-		row_block(n, ndev, d, C.first[d], C.last[d]);
-		max_rows = std::max(max_rows, C.last[d] - C.first[d]);
+	std::vector<std::vector<size_t>> mine(ndev); // every device's subjects in the order it stages them
+	for (RowGroup &G : C.groups) {
+		G.first.resize(ndev), G.last.resize(ndev);
+		for (size_t d = 0; d < ndev; ++d) {
+			row_block(G.rows, ndev, d, G.first[d], G.last[d]);
+			G.first[d] += G.s0, G.last[d] += G.s0;
+			for (size_t i = G.first[d]; i < G.last[d]; ++i) mine[d].push_back(i);
+		}
+		C.width = std::max(C.width, G.vn);
+		C.hint_max = std::max(C.hint_max, G.hint);
 	}
+	size_t max_rows = 0;
+	for (auto &m : mine) max_rows = std::max(max_rows, m.size());
 	std::vector<size_t> order; // subjects in the order they are needed
 	order.reserve(n);
 	for (size_t k = 0; k < max_rows; ++k)
 		for (size_t d = 0; d < ndev; ++d)
-			if (C.first[d] + k < C.last[d]) order.push_back(C.first[d] + k);
+			if (k < mine[d].size()) order.push_back(mine[d][k]);
 	int threads = o.host_threads > 0 ? o.host_threads : (int)std::thread::hardware_concurrency();
 	if (threads < 1) threads = 1;
 	if ((size_t)threads > n) threads = (int)n;
@@ -762,7 +794,12 @@ int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
 	// counts -- no host pass over the sequences, no second upload of what is already resident (round 5's trace of the bench
 	// set's warm call: host pool 5.5 ms + subject uploads 12.9 ms of 54).
 	C.dev_prep = !o.sa_on_host;
-	C.batch_max = o.low_memory ? 1 : 8;
+	// Calls without a diagonal (andi_hip_dist_rect) take 32 subjects per scan call: with one or a few queries per reference
+	// row a batch of 8 is a scan call of a few launches' latency (3085 references x 1 query of 2.1 Mbp: scans 235 -> 90 ms,
+	// the call 1.19 -> 0.96 s; the bench set's 28 + 1: 23.4 -> 21.7 ms; profiles/rect_c4.json, rect_bench_batches.json)
+	C.batch_max = o.low_memory ? 1 : (C.groups[0].diagonal ? 8 : 32);
+	if (const char *rb = andi_knob(KNOB_RECT_BATCH)) // (experiments: subjects per scan call of a call without a diagonal)
+		if (!o.low_memory && !C.groups[0].diagonal && atoi(rb) >= 1 && atoi(rb) <= 64) C.batch_max = (size_t)atoi(rb);
 	SubjectPool pool(seqs, C.o, std::move(order), (size_t)threads + ndev * C.batch_max + 1);
 	C.pool = &pool;
 
@@ -794,12 +831,74 @@ int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
 
 	snprintf(g_last_gather, sizeof g_last_gather, "%s", C.use_rccl ? "rccl" : "direct");
 	if (!rc && C.use_rccl) rc = gather_rccl(C, dv, pool.first_error);
-	if (rc) set_err(errbuf, errlen, "%s", pool.first_error.empty() ? "andi_hip_dist_matrix failed" : pool.first_error.c_str());
+	if (rc) set_err(errbuf, errlen, "%s", pool.first_error.empty() ? (std::string(C.name) + " failed").c_str() : pool.first_error.c_str());
 	const double t_gathered = now_ms();
 
 	for (auto &D : dv) D->close();
-	if (C.trace) fprintf(stderr, "andi_hip_dist_matrix trace: call total %.1f ms (gather %.1f, slots, queries and contexts released %.1f)\n", now_ms() - C.t_call, t_gathered - t_drivers_done, now_ms() - t_gathered);
+	if (C.trace) fprintf(stderr, "%s trace: call total %.1f ms (gather %.1f, slots, queries and contexts released %.1f)\n", C.name, now_ms() - C.t_call, t_gathered - t_drivers_done, now_ms() - t_gathered);
 	return rc;
+}
+} // namespace
+
+extern "C" {
+
+const char *andi_hip_last_gather(void) {
+	return g_last_gather;
+}
+
+void andi_hip_row_block(size_t total, size_t parts, size_t k, size_t *first, size_t *last) {
+	size_t f = 0, l = 0;
+	if (parts && k < parts) row_block(total, parts, k, f, l);
+	if (first) *first = f;
+	if (last) *last = l;
+}
+
+int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
+						 const andi_hip_opts *opts_in, char *errbuf, size_t errlen) {
+	if (!M || !seqs || n == 0) {
+		set_err(errbuf, errlen, "andi_hip_dist_matrix: bad arguments");
+		return 1;
+	}
+	SeamCall C;
+	C.name = "andi_hip_dist_matrix";
+	C.seqs = seqs, C.n = n;
+	if (opts_in) {
+		C.o = *opts_in;
+	} else {
+		andi_hip_default_opts(&C.o);
+	}
+	if (!check_seqs(seqs, n, "sequence", errbuf, errlen)) return 1;
+	// one group: every sequence against all of them (distMatrix compares every sequence with every other, n - 1 queries
+	// per subject: src/dist_hack.h:59-68)
+	C.groups.push_back({0, n, 0, n, M, true, n - 1, {}, {}});
+	C.pairs_total = n * n - n;
+	C.allow_rccl = true;
+	return run_seam(C, n, errbuf, errlen);
+}
+
+int andi_hip_dist_rect(andi_hip_model *MRQ, andi_hip_model *MQR, const andi_hip_seq *refs, size_t nr,
+					   const andi_hip_seq *queries, size_t nq, const andi_hip_opts *opts_in, char *errbuf, size_t errlen) {
+	if (!MRQ || !MQR || !refs || !queries || nr == 0 || nq == 0) {
+		set_err(errbuf, errlen, "andi_hip_dist_rect: bad arguments");
+		return 1;
+	}
+	if (!check_seqs(refs, nr, "reference", errbuf, errlen) || !check_seqs(queries, nq, "query", errbuf, errlen)) return 1;
+	SeamCall C;
+	C.name = "andi_hip_dist_rect";
+	if (opts_in) {
+		C.o = *opts_in;
+	} else {
+		andi_hip_default_opts(&C.o);
+	}
+	// the staged set is refs ++ queries (what the square call over that set would stage); its two cross blocks are two groups
+	std::vector<andi_hip_seq> all(refs, refs + nr);
+	all.insert(all.end(), queries, queries + nq);
+	C.seqs = all.data(), C.n = nr + nq;
+	C.groups.push_back({0, nr, nr, nq, MRQ, false, nq, {}, {}});  // references against the queries
+	C.groups.push_back({nr, nq, 0, nr, MQR, false, nr, {}, {}});  // queries against the references
+	C.pairs_total = 2 * nr * nq;
+	C.allow_rccl = false; // (rows go to MRQ and MQR directly)
+	return run_seam(C, std::max(nr, nq), errbuf, errlen);
 }
 
 } // extern "C"

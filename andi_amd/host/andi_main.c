@@ -360,6 +360,9 @@ static void usage(int status) {
 		"default: JC\n"
 		"  -p FLOAT             Significance of an anchor; default: 0.025\n"
 		"      --progress=WHEN  Print a progress bar 'always', 'never', or 'auto'; default: auto\n"
+		"      --reference=FILE  Compare FILES... against the sequences of FILE only (repeatable); prints one row\n"
+		"                       per query, one column per reference\n"
+		"      --reference-list=FILE  Read reference filenames from FILE; one per line\n"
 		"  -t, --threads=INT    Set the number of host threads; by default, all processors are used\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
@@ -411,11 +414,105 @@ static void print_matrix(const andi_hip_model *M, const genome *g, size_t n, int
 	free(names);
 }
 
+/* the query-versus-reference table (--reference): one row per query, one column per reference */
+static void print_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR, const genome *r, size_t nr, const genome *q,
+					   size_t nq, int model, int vv, int truncate) {
+	const char **rn = xmalloc(nr * sizeof *rn), **qn = xmalloc(nq * sizeof *qn);
+	for (size_t i = 0; i < nr; i++) rn[i] = r[i].name;
+	for (size_t i = 0; i < nq; i++) qn[i] = q[i].name;
+	size_t cap = 64, wcap = (size_t)1 << 16;
+	for (size_t i = 0; i < nr; i++) cap += strlen(rn[i]) + 1;
+	cap += nq * (300 + 16 * nr);
+	char *out = xmalloc(cap), *wbuf = xmalloc(wcap);
+	int flags = 0;
+	for (;;) {
+		const size_t need = andi_hip_format_distances_rect(MRQ, MQR, rn, nr, qn, nq, model, vv, truncate, 1, out, cap, wbuf, wcap, &flags);
+		const int out_short = need >= cap, warn_short = strlen(wbuf) + 1 >= wcap;
+		if (!out_short && !warn_short) break;
+		if (out_short) free(out), cap = need + 1, out = xmalloc(cap);
+		if (warn_short) free(wbuf), wcap *= 4, wbuf = xmalloc(wcap);
+	}
+	for (char *line = strtok(wbuf, "\n"); line; line = strtok(NULL, "\n")) soft_warnx("%s", line);
+	fputs(out, stdout);
+	free(out);
+	free(wbuf);
+	free(rn);
+	free(qn);
+}
+
+/* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
+static int check_genomes(const genome_list *l, int truncate) {
+	int any_short = 0;
+	const size_t limit = (INT_MAX - 1) / 2;
+	for (size_t i = 0; i < l->n; i++) {
+		const genome *g = &l->v[i];
+		if (truncate && strlen(g->name) > 10)
+			warnx("The sequence name '%s' is longer than ten characters. It will be truncated in the output "
+				  "to '%.10s'.", g->name, g->name);
+		if (g->len > limit) errx(1, "The sequence %s is too long. The technical limit is %zu.", g->name, limit);
+		if (g->len == 0) errx(1, "The sequence %s is empty.", g->name);
+		if (g->len < 1000) any_short = 1;
+	}
+	return any_short;
+}
+
+static andi_hip_seq *seq_array(const genome_list *l) {
+	andi_hip_seq *in = xmalloc(l->n * sizeof *in);
+	for (size_t i = 0; i < l->n; i++) in[i].seq = l->v[i].seq, in[i].len = l->v[i].len;
+	return in;
+}
+
+/* --reference: the queries (the FILES) against the references, the two cross blocks of the square run over both sets */
+static int run_rect(char **ref_files, size_t nref_files, char **files, size_t nfiles, int join, int verbose, int truncate,
+					int show_progress, andi_hip_opts *opts) {
+	genome_list refs = {0}, qs = {0};
+	read_all_files(ref_files, nref_files, join, opts->host_threads, &refs);
+	read_all_files(files, nfiles, join, opts->host_threads, &qs);
+	if (refs.n == 0) errx(1, "No reference sequences given: --reference and --reference-list name no readable sequence.");
+	if (qs.n == 0) errx(1, "No query sequences given: name at least one FASTA file besides the references.");
+	if (saw_non_acgt)
+		warnx("The input sequences contained characters other than acgtACGT. These were automatically "
+			  "stripped to ensure correct results.");
+	int any_short = check_genomes(&refs, truncate);
+	any_short |= check_genomes(&qs, truncate);
+	if (any_short)
+		soft_warnx("One of the given input sequences is shorter than a thousand nucleotides. This may result "
+				   "in inaccurate distances. Try an alignment instead.");
+	const size_t nr = refs.n, nq = qs.n;
+	if (show_progress) {
+		progress_n = nr + nq;
+		opts->progress = progress_cb;
+		progress_cb(0, 2 * nr * nq, NULL);
+	}
+	if (SIZE_MAX / sizeof(andi_hip_model) / nr < nq) errx(1, "Comparison is limited to fewer sequences (%zu given).", nr + nq);
+	andi_hip_model *MRQ = malloc(nr * nq * sizeof *MRQ), *MQR = malloc(nr * nq * sizeof *MQR);
+	if (!MRQ || !MQR) err(errno, "Could not allocate enough memory for the comparison matrix. Try using --join or --low-memory.");
+	andi_hip_seq *rin = seq_array(&refs), *qin = seq_array(&qs);
+	char msg[512];
+	if (andi_hip_dist_rect(MRQ, MQR, rin, nr, qin, nq, opts, msg, sizeof msg)) errx(1, "%s", msg);
+	if (show_progress) fprintf(stderr, ", done.\n");
+	print_rect(MRQ, MQR, refs.v, nr, qs.v, nq, opts->model, verbose >= 2, truncate);
+	if (verbose) { /* print_coverages, src/io.c:329-338, of the query rows */
+		printf("\nCoverage:\n");
+		for (size_t q = 0; q < nq; q++) {
+			for (size_t r = 0; r < nr; r++) printf("%1.4e ", andi_hip_model_coverage(&MQR[q * nr + r]));
+			printf("\n");
+		}
+	}
+	free(MRQ);
+	free(MQR);
+	free(rin);
+	free(qin);
+	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
 int main(int argc, char *argv[]) {
 	static const struct option long_options[] = {{"version", no_argument, NULL, 0},
 												 {"truncate-names", no_argument, NULL, 0},
 												 {"file-of-filenames", required_argument, NULL, 0},
 												 {"progress", optional_argument, NULL, 0},
+												 {"reference", required_argument, NULL, 0},
+												 {"reference-list", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -440,6 +537,9 @@ int main(int argc, char *argv[]) {
 	enum { P_AUTO, P_NEVER, P_ALWAYS } progress = P_AUTO;
 	char **files = NULL;
 	size_t nfiles = 0, files_cap = 0;
+	char **ref_files = NULL; /* --reference, --reference-list: the query-versus-reference mode */
+	size_t nref_files = 0, ref_cap = 0;
+	int rect = 0, bootstrap_given = 0;
 
 	for (;;) {
 		int idx = 0;
@@ -451,6 +551,16 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "version")) version();
 				if (!strcmp(o, "truncate-names")) truncate = 1;
 				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files, &nfiles, &files_cap);
+				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
+				if (!strcmp(o, "reference")) {
+					rect = 1;
+					if (nref_files == ref_cap) {
+						ref_cap = ref_cap ? ref_cap * 2 : 16;
+						ref_files = realloc(ref_files, ref_cap * sizeof *ref_files);
+						if (!ref_files) err(errno, "Out of memory");
+					}
+					ref_files[nref_files++] = strdup(optarg);
+				}
 				if (!strcmp(o, "progress")) {
 					if (!optarg || !strcasecmp(optarg, "always")) progress = P_ALWAYS;
 					else if (!strcasecmp(optarg, "auto")) progress = P_AUTO;
@@ -503,6 +613,7 @@ int main(int argc, char *argv[]) {
 							   "argument.", optarg);
 				} else {
 					bootstrap = b - 1; /* -b N prints N matrices in total, src/andi.c:198 */
+					bootstrap_given = 1;
 				}
 				break;
 			}
@@ -525,14 +636,17 @@ int main(int argc, char *argv[]) {
 		}
 		files[nfiles++] = strdup(argv[i]);
 	}
+	if (rect && bootstrap_given) errx(1, "Bootstrapping (-b) is not available together with --reference or --reference-list.");
 	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
-	if (nfiles < (size_t)(join ? 2 : 1)) {
+	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
 		if (isatty(STDIN_FILENO)) usage(EXIT_FAILURE);
 		files = realloc(files, (nfiles + 1) * sizeof *files);
 		files[nfiles++] = strdup("-");
 	}
 
 	/* ANDI_HIP_CLI_TRACE=1: where the wall time goes -- reading the input, the matrix, printing it (stderr; scripts/full_size.py --cli) */
+	if (progress == P_AUTO && rect) progress = isatty(STDERR_FILENO) ? P_ALWAYS : P_NEVER;
+	if (rect) return run_rect(ref_files, nref_files, files, nfiles, join, verbose, truncate, progress == P_ALWAYS, &opts);
 	const int cli_trace = getenv("ANDI_HIP_CLI_TRACE") != NULL;
 	struct timespec ts0, ts1, ts2, ts3;
 	clock_gettime(CLOCK_MONOTONIC, &ts0);

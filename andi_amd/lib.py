@@ -85,6 +85,8 @@ SYMBOLS = {
     "andi_hip_trim": (C.c_size_t, []),
     "andi_hip_pack_symbols": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p]),
     "andi_hip_dist_matrix": (C.c_int, [_P, C.POINTER(Seq), C.c_size_t, C.POINTER(Opts), C.c_char_p, C.c_size_t]),
+    "andi_hip_dist_rect": (C.c_int, [_P, _P, C.POINTER(Seq), C.c_size_t, C.POINTER(Seq), C.c_size_t, C.POINTER(Opts),
+                                     C.c_char_p, C.c_size_t]),
     "andi_hip_last_gather": (C.c_char_p, []),
     "andi_hip_row_block": (None, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "andi_hip_copy_ceiling": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(C.c_double)]),
@@ -102,6 +104,9 @@ SYMBOLS = {
     "andi_hip_format_distances": (C.c_size_t, [_P, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, C.c_int,
                                                C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_size_t,
                                                C.POINTER(C.c_int)]),
+    "andi_hip_format_distances_rect": (C.c_size_t, [_P, _P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_char_p),
+                                                    C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P,
+                                                    C.c_size_t, C.POINTER(C.c_int)]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -123,6 +128,7 @@ SYMBOLS = {
     "andi_hip_esa_bytes": (C.c_size_t, [_P]),
     "andi_hip_queries_stage": (C.c_int, [_P, C.POINTER(Seq), C.c_size_t, C.POINTER(_P)]),
     "andi_hip_queries_free": (None, [_P, _P]),
+    "andi_hip_queries_view": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.POINTER(_P)]),
     "andi_hip_match_positions": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, _P]),
     "andi_hip_scan_rows": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.c_size_t, _P, C.c_int,
                                      C.c_uint32, _P]),
@@ -227,6 +233,34 @@ def format_distances(M, names, model=M_JC, extra_verbose=False, truncate_names=F
         need = L.andi_hip_format_distances(M.ctypes.data, cnames, n, model, int(extra_verbose), int(truncate_names),
                                            int(warnings), C.cast(out, _P), cap, C.cast(warn, _P), len(warn),
                                            C.byref(flags))
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode(), warn.value.decode(), flags.value
+
+
+def _names(names):
+    return (C.c_char_p * len(names))(*[s.encode() if isinstance(s, str) else s for s in names])
+
+
+def format_distances_rect(MRQ, MQR, ref_names, query_names, model=M_JC, extra_verbose=False, truncate_names=False,
+                          warnings=True):
+    """The query-versus-reference table of dist_rect's (MRQ, MQR): returns (text, warning_text, flags)."""
+    L = load()
+    MRQ = np.ascontiguousarray(MRQ, dtype=np.uint32)
+    MQR = np.ascontiguousarray(MQR, dtype=np.uint32)
+    nr, nq = MRQ.shape[0], MQR.shape[0]
+    assert MRQ.shape == (nr, nq, 17) and MQR.shape == (nq, nr, 17)
+    assert len(ref_names) == nr and len(query_names) == nq
+    rn, qn = _names(ref_names), _names(query_names)
+    cap = 64 + 16 * nr + nq * (64 + 16 * nr) + sum(len(x) for x in ref_names) + sum(len(x) for x in query_names)
+    warn = C.create_string_buffer(1 << 20)
+    flags = C.c_int()
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = L.andi_hip_format_distances_rect(MRQ.ctypes.data, MQR.ctypes.data, rn, nr, qn, nq, model,
+                                                int(extra_verbose), int(truncate_names), int(warnings),
+                                                C.cast(out, _P), cap, C.cast(warn, _P), len(warn), C.byref(flags))
         if need < cap:
             break
         cap = need + 1
@@ -393,6 +427,11 @@ class Queries:
     def __len__(self):
         return len(self.seqs)
 
+    def view(self, first, count):
+        """queries [first, first + count) of this set on its device buffers (nothing copied): scan with it like any
+        staged set; close it before this one"""
+        return QueriesView(self, first, count)
+
     def close(self):
         if self._h and self.ctx._h:
             load().andi_hip_queries_free(self.ctx._h, self._h)
@@ -403,6 +442,18 @@ class Queries:
             self.close()
         except Exception:
             pass
+
+
+class QueriesView(Queries):
+    """andi_hip_queries_view: a column view of a staged set (Queries.view)."""
+
+    def __init__(self, parent: Queries, first, count):
+        self.ctx = parent.ctx
+        self.parent = parent  # (keeps the buffers it points at alive)
+        self.seqs = parent.seqs[first:first + count]
+        self._h = _P()
+        self.ctx._check(load().andi_hip_queries_view(self.ctx._h, parent._h, int(first), int(count), C.byref(self._h)),
+                        "queries_view")
 
 
 def match_positions(esa: Esa, queries: Queries, qidx, first, count, cached=True):
@@ -495,6 +546,25 @@ def bootstrap(ctx: Context, M, replicates, seed=0):
     return B
 
 
+def _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host, progress=None):
+    """(Opts, what must stay alive while it is used)"""
+    o = Opts()
+    load().andi_hip_default_opts(C.byref(o))
+    o.p_value, o.model, o.device, o.host_threads, o.segment = p_value, model, device, host_threads, segment
+    o.low_memory = int(low_memory)
+    o.sa_on_host = int(sa_on_host)
+    o.num_gpus = num_gpus
+    if devices is not None:
+        dl = (C.c_int * len(devices))(*devices)
+        o.devices, o.num_gpus = dl, len(devices)
+    keep = [dl] if devices is not None else []
+    if progress is not None:
+        cb = PROGRESS_FN(lambda done, total, ud: progress(done, total))
+        o.progress = cb
+        keep.append(cb)
+    return o, keep
+
+
 def dist_matrix(seqs, p_value=0.025, model=M_JC, device=0, host_threads=0, segment=0, num_gpus=1, devices=None,
                 low_memory=False, sa_on_host=False):
     """distMatrix (src/dist_hack.h:34): n*n*17 uint32, row = subject.  num_gpus / devices: the rows are
@@ -503,17 +573,28 @@ def dist_matrix(seqs, p_value=0.025, model=M_JC, device=0, host_threads=0, segme
     seqs = [bytes(s) for s in seqs]
     n = len(seqs)
     arr = _seq_array(seqs)
-    o = Opts()
-    L.andi_hip_default_opts(C.byref(o))
-    o.p_value, o.model, o.device, o.host_threads, o.segment = p_value, model, device, host_threads, segment
-    o.low_memory = int(low_memory)
-    o.sa_on_host = int(sa_on_host)
-    o.num_gpus = num_gpus
-    if devices is not None:
-        dl = (C.c_int * len(devices))(*devices)
-        o.devices, o.num_gpus = dl, len(devices)
+    o, _keep = _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host)
     M = np.zeros((n, n, 17), np.uint32)
     err = C.create_string_buffer(512)
     if L.andi_hip_dist_matrix(M.ctypes.data, arr, n, C.byref(o), err, len(err)):
         raise AndiHipError(err.value.decode())
     return M
+
+
+def dist_rect(refs, queries, p_value=0.025, model=M_JC, device=0, host_threads=0, segment=0, num_gpus=1, devices=None,
+              low_memory=False, sa_on_host=False, progress=None):
+    """The query-versus-reference mode (andi_hip_dist_rect): (MRQ, MQR), uint32 arrays (nr, nq, 17) and (nq, nr, 17) --
+    the cross blocks M[:nr, nr:] and M[nr:, :nr] of dist_matrix(refs + queries), bit for bit, computed alone.
+    progress(done, total): called from the devices' driver threads, total = 2 * nr * nq."""
+    L = load()
+    refs = [bytes(s) for s in refs]
+    queries = [bytes(s) for s in queries]
+    nr, nq = len(refs), len(queries)
+    ra, qa = _seq_array(refs), _seq_array(queries)
+    o, _keep = _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host, progress)
+    MRQ = np.zeros((nr, nq, 17), np.uint32)
+    MQR = np.zeros((nq, nr, 17), np.uint32)
+    err = C.create_string_buffer(512)
+    if L.andi_hip_dist_rect(MRQ.ctypes.data, MQR.ctypes.data, ra, nr, qa, nq, C.byref(o), err, len(err)):
+        raise AndiHipError(err.value.decode())
+    return MRQ, MQR

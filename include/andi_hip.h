@@ -12,6 +12,10 @@
  * success; on failure they return non-zero and write a message to
  * errbuf (when given).  Nothing here falls back to a CPU implementation of a
  * device step: without a usable HIP device the device entry points fail.
+ *
+ * ABI 5 also gained, without changing anything that was there, the query-versus-
+ * reference mode: andi_hip_dist_rect, andi_hip_queries_view and
+ * andi_hip_format_distances_rect (additions only; the version stays 5).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -99,6 +103,19 @@ int andi_hip_pack_symbols(const unsigned char *src, size_t len, unsigned char *o
 /* ------------------------------------------------------------------ */
 int andi_hip_dist_matrix(andi_hip_model *M, const andi_hip_seq *seqs, size_t n,
 						 const andi_hip_opts *opts, char *errbuf, size_t errlen);
+/* The query-versus-reference mode: the two cross blocks of andi_hip_dist_matrix over refs ++ queries, bit for bit, and
+ * nothing else -- MRQ (nr*nq, row r = reference r as subject: MRQ[r*nq+q] = M[r][nr+q]) and MQR (nq*nr, row q = query q
+ * as subject: MQR[q*nr+r] = M[nr+q][r]).  andi's distance of a pair needs both directions (model_average of the two,
+ * src/io.c:246-322).  The union is staged once as the query pool; reference rows scan a view of its last nq sequences,
+ * query rows a view of its first nr; no entry is a diagonal placeholder (a sequence in both sets is scanned against
+ * itself).  Same opts as the square call: model, p_value, low_memory, sa_on_host, num_gpus/devices (the reference rows
+ * and the query rows each tiled over the devices with andi_hip_row_block; rows are copied to MRQ/MQR directly, so
+ * andi_hip_last_gather reports "direct"), progress with total = 2*nr*nq.  Bad arguments (NULL pointers, nr or nq 0,
+ * an empty or oversized sequence) fail through errbuf before any HIP call.  Growing a matrix: old x old is kept, the new
+ * cross blocks come from this call with refs = old, queries = new, and new x new from andi_hip_dist_matrix. */
+int andi_hip_dist_rect(andi_hip_model *MRQ, andi_hip_model *MQR,
+					   const andi_hip_seq *refs, size_t nr, const andi_hip_seq *queries, size_t nq,
+					   const andi_hip_opts *opts, char *errbuf, size_t errlen);
 /* how the calling thread's last call collected its rows: "rccl", "direct (...)" (diagnostic; per thread).
  * A call that spans several devices initialises RCCL communicators, and RCCL reads the bootstrap interface from the
  * process environment only: unless NCCL_SOCKET_IFNAME is set, the library sets it to "lo" around ncclCommInitAll and
@@ -139,6 +156,16 @@ size_t andi_hip_format_distances(const andi_hip_model *M, const char *const *nam
 								 int model, int extra_verbose, int truncate_names, int warnings,
 								 char *out, size_t cap, char *warnbuf, size_t warncap,
 								 int *warn_flags);
+/* The table of the query-versus-reference mode (andi_hip_dist_rect's MRQ, MQR) into a caller buffer: "nq nr\n"; ten
+ * spaces and " %s" per reference name (truncated to ten characters under truncate_names); then per query its name as
+ * print_distances prints it and nr distances, estimate(model_average(MRQ[r][q], MQR[q][r])) -- MQR[q][r] alone under
+ * extra_verbose.  Every cell is the string print_distances prints for that pair of refs ++ queries; the %1.4f / %1.4e
+ * switch is decided over this whole table.  NaN and low-coverage warnings as print_distances words them, once per
+ * (query, reference) pair, into warnbuf; return value and *warn_flags as andi_hip_format_distances. */
+size_t andi_hip_format_distances_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR,
+									  const char *const *ref_names, size_t nr, const char *const *query_names, size_t nq,
+									  int model, int extra_verbose, int truncate_names, int warnings,
+									  char *out, size_t cap, char *warnbuf, size_t warncap, int *warn_flags);
 
 /* ------------------------------------------------------------------ */
 /* Device-resident objects                                             */
@@ -204,6 +231,11 @@ size_t andi_hip_esa_bytes(const andi_hip_esa *esa);
 int andi_hip_queries_stage(andi_hip_ctx *ctx, const andi_hip_seq *seqs, size_t n,
 						   andi_hip_queries **out);
 void andi_hip_queries_free(andi_hip_ctx *ctx, andi_hip_queries *q);
+/* Queries [first, first + count) of q, sharing q's device buffers (no copy, no upload): scan with it like any staged set
+ * (query k of the view is query first + k of q).  Free it with andi_hip_queries_free before q; that frees only what the
+ * view owns (its segmentation). */
+int andi_hip_queries_view(andi_hip_ctx *ctx, const andi_hip_queries *q, size_t first, size_t count,
+						  andi_hip_queries **out);
 
 /* get_match_cached / get_match (src/esa.c:615-656) for `count` consecutive
  * suffixes of query `qidx`: out[k] = match of Q[first+k ..] (fields l,i,j;
