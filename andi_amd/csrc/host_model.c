@@ -183,17 +183,26 @@ static void put_grow(sink *s, const char *fmt, ...) { /* a sink that owns its bu
 	}
 }
 
+/* the distance print_distances prints for cell (i, j): model_average of both directions (M[i][j] alone under extra_verbose),
+ * +0.0 on the diagonal -- what the formatter prints and andi_hip_distances returns */
+static double cell_distance(const andi_hip_model *M, size_t n, size_t i, size_t j, int model, int extra_verbose) {
+	if (i == j) return 0.0;
+	andi_hip_model datum = M[i * n + j];
+	if (!extra_verbose) datum = andi_hip_model_average(&M[i * n + j], &M[j * n + i]);
+	return andi_hip_estimate(&datum, model);
+}
+
 static void fmt_rows(fmt_job *job, size_t i0, size_t i1) {
 	const andi_hip_model *M = job->M;
 	const size_t n = job->n;
 	for (size_t i = i0; i < i1; i++) {
-		if (job->phase == 0) {
+		if (job->phase == 2) { /* andi_hip_distances: the distances alone */
+			for (size_t j = 0; j < n; j++) job->D[i * n + j] = cell_distance(M, n, i, j, job->model, 0);
+		} else if (job->phase == 0) {
 			int flags = 0, sci = 0;
 			sink *w = &job->row_warn[i];
 			for (size_t j = 0; j < n; j++) {
-				andi_hip_model datum = M[i * n + j];
-				if (!job->extra_verbose) datum = andi_hip_model_average(&M[i * n + j], &M[j * n + i]);
-				double d = job->D[i * n + j] = i == j ? 0.0 : andi_hip_estimate(&datum, job->model);
+				double d = job->D[i * n + j] = cell_distance(M, n, i, j, job->model, job->extra_verbose);
 				if (d > 0 && d < 0.001) sci = 1;
 				if (isnan(d) && job->warnings) {
 					flags |= 1;
@@ -289,6 +298,13 @@ size_t andi_hip_format_distances(const andi_hip_model *M, const char *const *nam
 	return o.len;
 }
 
+int andi_hip_distances(const andi_hip_model *M, size_t n, int model, double *D) {
+	if (!M || !D) return 1;
+	fmt_job job = {M, NULL, n, model, 0, 0, 0, D, NULL, NULL, NULL, NULL, 0, 0, 0};
+	fmt_run(&job, 2);
+	return 0;
+}
+
 /* The query-versus-reference table (andi_hip_dist_rect's two cross blocks, include/andi_hip.h): query q is row nr + q of
  * refs ++ queries, reference r is column r, so a cell is what fmt_rows computes for that pair of the union --
  * model_average(M[i][j], M[j][i]) with M[i][j] = MQR[q][r], M[j][i] = MRQ[r][q] (extra_verbose: MQR[q][r] alone) -- and the
@@ -342,5 +358,72 @@ size_t andi_hip_format_distances_rect(const andi_hip_model *MRQ, const andi_hip_
 	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
 	if (warnbuf && warncap) warnbuf[w.len < warncap ? w.len : warncap - 1] = '\0';
 	if (warn_flags) *warn_flags = flags;
+	return o.len;
+}
+
+/* a leaf of the Newick text: the name (cut to ten characters under truncate), quoted if it holds a character Newick
+ * gives a meaning to */
+static void put_leaf(sink *o, const char *name, int truncate) {
+	const size_t len = truncate ? strnlen(name, 10) : strlen(name);
+	int quote = 0;
+	for (size_t k = 0; k < len; k++) quote |= strchr(" \t()[]':;,", name[k]) != NULL && name[k] != '\0';
+	if (!quote) {
+		put(o, "%.*s", (int)len, name);
+		return;
+	}
+	put(o, "'");
+	for (size_t k = 0; k < len; k++) put(o, name[k] == '\'' ? "''" : "%c", name[k]);
+	put(o, "'");
+}
+
+/* andi_hip_nj's records as Newick text (include/andi_hip.h), depth first with a stack of its own instead of recursion */
+size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+							  char *out, size_t cap) {
+	sink o = {out, cap, 0};
+	if (out && cap) out[0] = '\0';
+	if (!J || !names || n < 2) return 0;
+	const size_t pairs = n == 2 ? 0 : n - 3, root = n == 2 ? 0 : n - 3; /* records 0 .. pairs-1 are the pair joins */
+	for (size_t s = 0; s <= root; s++) { /* every child a leaf or an earlier record's node: the walk below ends */
+		const int32_t ch[3] = {J[s].a, J[s].b, J[s].c};
+		const int kids = s == root && n > 2 ? 3 : 2;
+		for (int k = 0; k < kids; k++)
+			if (ch[k] < 0 || (size_t)ch[k] >= n + s || (s == root && (size_t)ch[k] >= n + pairs)) return 0;
+	}
+	typedef struct {
+		size_t rec; /* record of this node */
+		int next;   /* its next child */
+		double len; /* its own branch length */
+	} frame;
+	frame *stack = malloc((pairs + 1) * sizeof *stack);
+	if (!stack) return 0;
+	size_t depth = 0;
+	stack[depth++] = (frame){root, 0, 0.0};
+	put(&o, "(");
+	while (depth) {
+		frame *f = &stack[depth - 1];
+		const andi_hip_nj_join *r = &J[f->rec];
+		const int kids = f->rec == root && n > 2 ? 3 : 2;
+		if (f->next == kids) {
+			const double len = f->len;
+			depth--;
+			put(&o, ")");
+			if (depth) put(&o, ":%.8g", len);
+			else put(&o, ";\n");
+			continue;
+		}
+		const int k = f->next++;
+		if (k) put(&o, ",");
+		const size_t child = (size_t)(k == 0 ? r->a : k == 1 ? r->b : r->c);
+		const double len = k == 0 ? r->la : k == 1 ? r->lb : r->lc;
+		if (child < n) {
+			put_leaf(&o, names[child], truncate_names);
+			put(&o, ":%.8g", len);
+		} else {
+			stack[depth++] = (frame){child - n, 0, len};
+			put(&o, "(");
+		}
+	}
+	free(stack);
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
 	return o.len;
 }

@@ -1,0 +1,298 @@
+// nj.hip — neighbor-joining of a distance matrix on the device (andi_hip_nj, include/andi_hip.h).
+//
+// The reference stops at the matrix; its users run PHYLIP's neighbor on it (docs/manual/andi-manual.tex:301-341).  This
+// is that step on the MI355X, bit for bit the arithmetic contract in andi_hip.h (tests/nj_model.py restates it in NumPy).
+// D stays resident as doubles, indexed by SLOT: leaf i starts in slot i, a join's node takes the lower slot of its two
+// children and the other slot retires.  The active slots are kept as an ascending compacted list (act), ping-ponged
+// between two buffers, so every step reads only the r x r active block.  A step with r >= 4 active nodes is three
+// launches on the context's stream, with no host synchronisation between steps:
+//   k_nj_rowsum  R[x] for every active slot x: one wavefront per row, its active entries loaded by all lanes at once
+//                (1024 in flight), then added one after the other in slot order from +0.0 (sequential, as the contract
+//                asks) by a chain that reads them lane by lane;
+//   k_nj_argmin  the least (Q, id_x, id_y) of every 64 x 64 tile of the active upper triangle, one result per block;
+//   k_nj_join    one block: the least of those results, the record, the new node's row and column, the list compacted.
+// One D2H copy of the records at the end.  No graph capture, no grid-wide barrier, no atomics on the step path.
+#pragma clang fp contract(off)
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+#include "api_internal.h"
+
+static_assert(sizeof(andi_hip_nj_join) == 40, "andi_hip_nj_join: 3 ids, pad, 3 lengths");
+
+namespace {
+
+constexpr int RS_CHUNKS = 16;                // k_nj_rowsum: 16 x 64 entries of a row in flight per wavefront
+constexpr int TILE = 64;                     // k_nj_argmin: 64 x 64 pairs per block, 16 rows per wavefront
+constexpr int JOIN_THREADS = 1024;
+
+// a candidate pair: Q, the two node ids (ia < ib) and their slots
+struct Cand {
+	double q;
+	int32_t ia, ib, sa, sb;
+};
+
+// the contract's order: the least Q by value (-0.0 == +0.0), then the smaller id_x, then the smaller id_y.  A NaN Q (only
+// from overflow of finite input) orders after every number, so the pick is always a real pair.
+__device__ inline bool better(const Cand &a, const Cand &b) {
+	const bool na = __builtin_isnan(a.q), nb = __builtin_isnan(b.q);
+	if (na != nb) return nb;
+	if (!na && a.q != b.q) return a.q < b.q;
+	return a.ia < b.ia || (a.ia == b.ia && a.ib < b.ib);
+}
+
+__device__ inline Cand none() { return Cand{__builtin_nan(""), INT32_MAX, INT32_MAX, 0, 0}; }
+
+__device__ inline Cand shfl_xor(const Cand &c, int m) {
+	return Cand{__shfl_xor(c.q, m), __shfl_xor(c.ia, m), __shfl_xor(c.ib, m), __shfl_xor(c.sa, m), __shfl_xor(c.sb, m)};
+}
+
+__device__ inline Cand wave_min(Cand c) {
+	for (int m = 32; m > 0; m >>= 1) {
+		const Cand o = shfl_xor(c, m);
+		if (better(o, c)) c = o;
+	}
+	return c;
+}
+
+// the block's least candidate, returned to every thread (blockDim.x / 64 waves, at most 16)
+__device__ Cand block_min(Cand c) {
+	__shared__ Cand w[16];
+	c = wave_min(c);
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+	if (lane == 0) w[wave] = c;
+	__syncthreads();
+	c = w[0];
+	for (int k = 1; k < waves; ++k)
+		if (better(w[k], c)) c = w[k];
+	__syncthreads();
+	return c;
+}
+
+// Mirror the upper triangle (row i = block i), diagonal +0.0; the first non-finite D[i][j], i < j, in row-major order
+// goes to *bad as i * n + j.  act = id = identity.
+__global__ __launch_bounds__(256) void k_nj_init(double *__restrict__ D, uint32_t n, int32_t *__restrict__ act,
+												 int32_t *__restrict__ id, unsigned long long *bad) {
+	const uint32_t i = blockIdx.x;
+	double *row = D + (size_t)i * n;
+	unsigned long long first = ~0ull;
+	for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) {
+		if (j > i) {
+			if (!__builtin_isfinite(row[j]) && first == ~0ull) first = (unsigned long long)i * n + j;
+		} else {
+			row[j] = j < i ? D[(size_t)j * n + i] : 0.0;
+		}
+	}
+	if (first != ~0ull) atomicMin(bad, first);
+	if (threadIdx.x == 0) act[i] = (int32_t)i, id[i] = (int32_t)i;
+}
+
+// R[x] = sum over k = 0 .. r-1 of D[x][act[k]], in that order, from +0.0, for x = act[row]: one wavefront per row.  The
+// lanes load RS_CHUNKS x 64 entries of the row at once (all in flight together); the chain of adds then takes them lane by
+// lane (v_readlane into scalar registers), so the sum stays sequential while the loads are spread over every CU.
+__device__ inline double lane_value(double v, int l) {
+	const long long b = __double_as_longlong(v);
+	const int lo = __builtin_amdgcn_readlane((int)b, l), hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
+	return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+__global__ __launch_bounds__(256) void k_nj_rowsum(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ act,
+												   uint32_t r, double *__restrict__ R) {
+	const uint32_t x = blockIdx.x * 4 + (threadIdx.x >> 6);
+	const int lane = threadIdx.x & 63;
+	if (x >= r) return;
+	const size_t sx = (size_t)act[x];
+	const double *row = D + sx * n;
+	double acc = 0.0;
+	for (uint32_t base = 0; base < r; base += 64 * RS_CHUNKS) {
+		double v[RS_CHUNKS];
+#pragma unroll
+		for (int c = 0; c < RS_CHUNKS; ++c) {
+			const uint32_t k = base + 64 * c + lane;
+			v[c] = k < r ? row[act[k]] : 0.0;
+		}
+#pragma unroll
+		for (int c = 0; c < RS_CHUNKS; ++c) {
+			const uint32_t k0 = base + 64 * c;
+			if (k0 + 64 <= r) {
+#pragma unroll
+				for (int l = 0; l < 64; ++l) acc += lane_value(v[c], l);
+			} else if (k0 < r) {
+				for (int l = 0; l < (int)(r - k0); ++l) acc += lane_value(v[c], l);
+			}
+		}
+	}
+	if (lane == 0) R[sx] = acc;
+}
+
+// Block b = tile (tp, tq), tp <= tq, of the active pairs in list positions: wave w takes rows tp*64 + 16w .. +15, lane l
+// column tq*64 + l.  Q = ((r-2) * D[x][y] - R_x) - R_y with x the member of smaller id.
+__global__ __launch_bounds__(256) void k_nj_argmin(const double *__restrict__ D, uint32_t n,
+												   const int32_t *__restrict__ act, uint32_t r,
+												   const int32_t *__restrict__ id, const double *__restrict__ R,
+												   Cand *__restrict__ part) {
+	const uint64_t b = blockIdx.x;
+	uint32_t tq = (uint32_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+	while ((uint64_t)tq * (tq + 1) / 2 > b) --tq;
+	while ((uint64_t)(tq + 1) * (tq + 2) / 2 <= b) ++tq;
+	const uint32_t tp = (uint32_t)(b - (uint64_t)tq * (tq + 1) / 2);
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint32_t q = tq * TILE + lane;
+	Cand best = none();
+	if (q < r) {
+		const int32_t sq = act[q], iq = id[sq];
+		const double Rq = R[sq], c = (double)(r - 2);
+		const uint32_t p0 = tp * TILE + wave * 16;
+		double d[16];
+#pragma unroll
+		for (int k = 0; k < 16; ++k) {
+			const uint32_t p = p0 + k;
+			d[k] = p < q ? D[(size_t)act[p] * n + sq] : 0.0;
+		}
+#pragma unroll
+		for (int k = 0; k < 16; ++k) {
+			const uint32_t p = p0 + k;
+			if (p >= q) continue;
+			const int32_t sp = act[p], ip = id[sp];
+			const double Rp = R[sp];
+			Cand cand;
+			if (ip < iq) cand = Cand{(c * d[k] - Rp) - Rq, ip, iq, sp, sq};
+			else cand = Cand{(c * d[k] - Rq) - Rp, iq, ip, sq, sp};
+			if (better(cand, best)) best = cand;
+		}
+	}
+	best = block_min(best);
+	if (threadIdx.x == 0) part[b] = best;
+}
+
+// One block: the least of nparts tile results, its record, node u = n + step in the lower slot, the other slot retired
+// (act_in -> act_out, order kept).
+__global__ __launch_bounds__(JOIN_THREADS) void k_nj_join(double *__restrict__ D, uint32_t n,
+														  const int32_t *__restrict__ act_in, int32_t *__restrict__ act_out,
+														  uint32_t r, int32_t *__restrict__ id, const double *__restrict__ R,
+														  const Cand *__restrict__ part, uint32_t nparts,
+														  andi_hip_nj_join *__restrict__ rec, uint32_t step) {
+	Cand best = none();
+	for (uint32_t k = threadIdx.x; k < nparts; k += blockDim.x)
+		if (better(part[k], best)) best = part[k];
+	best = block_min(best);
+	const size_t sa = (size_t)best.sa, sb = (size_t)best.sb;
+	const size_t su = sa < sb ? sa : sb, so = sa < sb ? sb : sa;
+	const double d = D[sa * n + sb];
+	if (threadIdx.x == 0) {
+		const double la = d * 0.5 + (R[sa] - R[sb]) / (double)(2 * (r - 2));
+		andi_hip_nj_join j;
+		j.a = best.ia, j.b = best.ib, j.c = -1, j.pad = 0;
+		j.la = la, j.lb = d - la, j.lc = 0.0;
+		rec[step] = j;
+	}
+	for (uint32_t i = threadIdx.x; i < r; i += blockDim.x) {
+		const size_t k = (size_t)act_in[i];
+		if (k == so) continue;
+		act_out[i - (k > so)] = (int32_t)k;
+		if (k == su) continue;
+		const double v = ((D[sa * n + k] + D[sb * n + k]) - d) * 0.5;
+		D[su * n + k] = v;
+		D[k * n + su] = v;
+	}
+	if (threadIdx.x == 0) {
+		D[su * n + su] = 0.0;
+		id[su] = (int32_t)(n + step);
+	}
+}
+
+// The last record: the three remaining nodes x < y < z by id (r = 3), or the two leaves of n = 2.
+__global__ void k_nj_final(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ act, uint32_t r,
+						   const int32_t *__restrict__ id, andi_hip_nj_join *__restrict__ rec) {
+	if (threadIdx.x != 0) return;
+	andi_hip_nj_join j;
+	j.pad = 0;
+	if (r == 2) {
+		const double h = D[(size_t)act[0] * n + act[1]] * 0.5;
+		j.a = id[act[0]], j.b = id[act[1]], j.c = -1;
+		j.la = h, j.lb = h, j.lc = 0.0;
+	} else {
+		int32_t s[3] = {act[0], act[1], act[2]};
+		for (int a = 0; a < 2; ++a) // (by id)
+			for (int b = 0; b < 2 - a; ++b)
+				if (id[s[b]] > id[s[b + 1]]) {
+					const int32_t t = s[b];
+					s[b] = s[b + 1], s[b + 1] = t;
+				}
+		const double xy = D[(size_t)s[0] * n + s[1]], xz = D[(size_t)s[0] * n + s[2]], yz = D[(size_t)s[1] * n + s[2]];
+		j.a = id[s[0]], j.b = id[s[1]], j.c = id[s[2]];
+		j.la = ((xy + xz) - yz) * 0.5;
+		j.lb = ((xy + yz) - xz) * 0.5;
+		j.lc = ((xz + yz) - xy) * 0.5;
+	}
+	*rec = j;
+}
+
+uint64_t tiles_of(uint32_t r) {
+	const uint64_t t = (r + TILE - 1) / TILE;
+	return t * (t + 1) / 2;
+}
+
+} // namespace
+
+int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *joins) {
+	if (!ctx || !D || !joins || n < 2 || n > 65535) {
+		if (ctx) ctx->err = "andi_hip_nj: bad arguments (ctx, D and joins must be given, 2 <= n <= 65535)";
+		return 1;
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const uint32_t N = (uint32_t)n;
+	const size_t nrec = n == 2 ? 1 : n - 2;
+	double *dD = nullptr, *dR = nullptr;
+	int32_t *dact = nullptr, *did = nullptr;
+	Cand *dpart = nullptr;
+	andi_hip_nj_join *drec = nullptr;
+	unsigned long long *dbad = nullptr, bad = ~0ull;
+	hipError_t e = dmalloc(&dD, n * n);
+	if (e == hipSuccess) e = dmalloc(&dR, n);
+	if (e == hipSuccess) e = dmalloc(&dact, 3 * n); // two lists, the ids
+	if (e == hipSuccess) e = dmalloc(&dpart, tiles_of(N));
+	if (e == hipSuccess) e = dmalloc(&drec, nrec);
+	if (e == hipSuccess) e = dmalloc(&dbad, 1);
+	if (e == hipSuccess) did = dact + 2 * n;
+	hipStream_t st = ctx->stream;
+	if (e == hipSuccess) e = hipMemcpyAsync(dD, D, n * n * sizeof(double), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemsetAsync(dbad, 0xff, sizeof bad, st);
+	if (e == hipSuccess) {
+		k_nj_init<<<N, 256, 0, st>>>(dD, N, dact, did, dbad);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e == hipSuccess && bad != ~0ull) {
+		const size_t i = (size_t)(bad / n), j = (size_t)(bad % n);
+		char msg[160];
+		snprintf(msg, sizeof msg, "andi_hip_nj: D[%zu][%zu] is not finite (%g)", i, j, D[i * n + j]);
+		ctx->err = msg;
+	}
+	int32_t *act = dact, *act2 = dact + n;
+	for (uint32_t s = 0; e == hipSuccess && bad == ~0ull && n >= 4 && s < N - 3; ++s) {
+		const uint32_t r = N - s;
+		const uint64_t nb = tiles_of(r);
+		k_nj_rowsum<<<(r + 3) / 4, 256, 0, st>>>(dD, N, act, r, dR);
+		k_nj_argmin<<<(unsigned)nb, 256, 0, st>>>(dD, N, act, r, did, dR, dpart);
+		k_nj_join<<<1, JOIN_THREADS, 0, st>>>(dD, N, act, act2, r, did, dR, dpart, (uint32_t)nb, drec, s);
+		e = hipGetLastError();
+		int32_t *t = act;
+		act = act2, act2 = t;
+	}
+	if (e == hipSuccess && bad == ~0ull) {
+		k_nj_final<<<1, 64, 0, st>>>(dD, N, act, n == 2 ? 2 : 3, did, drec + (nrec - 1));
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess && bad == ~0ull) e = hipMemcpyAsync(joins, drec, nrec * sizeof *drec, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
+	for (void *p : {(void *)dD, (void *)dR, (void *)dact, (void *)dpart, (void *)drec, (void *)dbad})
+		(void)andi_arena::dev_free(p, false);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_nj", e);
+	return bad == ~0ull ? 0 : 1;
+}

@@ -12,6 +12,7 @@
 #include <fcntl.h>
 #include <getopt.h>
 #include <limits.h>
+#include <math.h>
 #include <pthread.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -364,6 +365,8 @@ static void usage(int status) {
 		"                       per query, one column per reference\n"
 		"      --reference-list=FILE  Read reference filenames from FILE; one per line\n"
 		"  -t, --threads=INT    Set the number of host threads; by default, all processors are used\n"
+		"      --tree=FILE      Write a neighbor-joining tree of each printed matrix to FILE (Newick, one line per\n"
+		"                       matrix)\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -440,6 +443,50 @@ static void print_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR, con
 	free(qn);
 }
 
+/* --tree: the neighbor-joining tree of the K-th printed matrix (1 = the point estimate) as one Newick line, from the
+ * averaged distances whatever -vv asks the matrix to print */
+typedef struct {
+	FILE *f;
+	const char *path;
+	andi_hip_ctx *ctx; /* one for all trees, on opts.device */
+	int device_for_ctx;
+	int failed;        /* it could not be created: said once */
+} tree_out;
+
+static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, size_t n, int model, int truncate, int k) {
+	if (t->failed) return;
+	char msg[512];
+	if (!t->ctx && andi_hip_ctx_create(&t->ctx, t->device_for_ctx, msg, sizeof msg)) {
+		t->failed = 1, t->ctx = NULL;
+		soft_warnx("No trees: %s", msg);
+		return;
+	}
+	double *D = malloc(n * n * sizeof *D);
+	andi_hip_nj_join *J = malloc(n * sizeof *J);
+	if (!D || !J || andi_hip_distances(M, n, model, D)) err(errno, "Could not allocate enough memory for the tree.");
+	for (size_t i = 0; i < n; i++)
+		for (size_t j = i + 1; j < n; j++)
+			if (!isfinite(D[i * n + j])) {
+				soft_warnx("No tree for matrix %d: the distance of '%s' and '%s' is not finite.", k, g[i].name, g[j].name);
+				free(D), free(J);
+				return;
+			}
+	if (andi_hip_nj(t->ctx, D, n, J)) {
+		soft_warnx("No tree for matrix %d: %s", k, andi_hip_last_error(t->ctx));
+		free(D), free(J);
+		return;
+	}
+	const char **names = xmalloc(n * sizeof *names);
+	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
+	size_t cap = 64 + n * 40;
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	const size_t need = andi_hip_format_newick(J, n, names, truncate, text, cap);
+	if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick(J, n, names, truncate, text, cap);
+	if (fputs(text, t->f) == EOF) err(1, "%s", t->path);
+	free(text), free(names), free(D), free(J);
+}
+
 /* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
 static int check_genomes(const genome_list *l, int truncate) {
 	int any_short = 0;
@@ -513,6 +560,7 @@ int main(int argc, char *argv[]) {
 												 {"progress", optional_argument, NULL, 0},
 												 {"reference", required_argument, NULL, 0},
 												 {"reference-list", required_argument, NULL, 0},
+												 {"tree", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -540,6 +588,7 @@ int main(int argc, char *argv[]) {
 	char **ref_files = NULL; /* --reference, --reference-list: the query-versus-reference mode */
 	size_t nref_files = 0, ref_cap = 0;
 	int rect = 0, bootstrap_given = 0;
+	tree_out tree = {0};
 
 	for (;;) {
 		int idx = 0;
@@ -551,6 +600,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "version")) version();
 				if (!strcmp(o, "truncate-names")) truncate = 1;
 				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files, &nfiles, &files_cap);
+				if (!strcmp(o, "tree")) tree.path = optarg;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
 				if (!strcmp(o, "reference")) {
 					rect = 1;
@@ -637,6 +687,9 @@ int main(int argc, char *argv[]) {
 		files[nfiles++] = strdup(argv[i]);
 	}
 	if (rect && bootstrap_given) errx(1, "Bootstrapping (-b) is not available together with --reference or --reference-list.");
+	if (rect && tree.path) errx(1, "A tree (--tree) is not available together with --reference or --reference-list.");
+	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
+	tree.device_for_ctx = opts.device;
 	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
 		if (isatty(STDIN_FILENO)) usage(EXIT_FAILURE);
@@ -696,6 +749,7 @@ int main(int argc, char *argv[]) {
 	clock_gettime(CLOCK_MONOTONIC, &ts2);
 
 	print_matrix(M, all.v, n, opts.model, verbose >= 2, truncate, 1);
+	if (tree.f) write_tree(&tree, M, all.v, n, opts.model, truncate, 1);
 	if (cli_trace) {
 		fflush(stdout);
 		clock_gettime(CLOCK_MONOTONIC, &ts3);
@@ -719,12 +773,16 @@ int main(int argc, char *argv[]) {
 			andi_hip_bootstrap(ctx, M, n, (uint64_t)time(NULL), bootstrap, B)) {
 			soft_warnx("Bootstrapping failed.");
 		} else {
-			for (unsigned long b = 0; b < bootstrap; b++)
+			for (unsigned long b = 0; b < bootstrap; b++) {
 				print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
+				if (tree.f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
+			}
 		}
 		if (ctx) andi_hip_ctx_destroy(ctx);
 		free(B);
 	}
+	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
+	if (tree.f && fclose(tree.f)) err(1, "%s", tree.path);
 	free(M);
 	free(in);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;

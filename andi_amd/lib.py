@@ -107,6 +107,9 @@ SYMBOLS = {
     "andi_hip_format_distances_rect": (C.c_size_t, [_P, _P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(C.c_char_p),
                                                     C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P,
                                                     C.c_size_t, C.POINTER(C.c_int)]),
+    "andi_hip_distances": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
+    "andi_hip_format_newick": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_nj": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -265,6 +268,37 @@ def format_distances_rect(MRQ, MQR, ref_names, query_names, model=M_JC, extra_ve
             break
         cap = need + 1
     return out.value.decode(), warn.value.decode(), flags.value
+
+
+# andi_hip_nj_join: a record of a neighbor-joining tree (ids a, b, c -- c = -1 but in the final record -- and branch lengths)
+NJ_JOIN = np.dtype([("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("pad", "<i4"), ("la", "<f8"), ("lb", "<f8"),
+                    ("lc", "<f8")])
+
+
+def distances(M, model=M_JC):
+    """The (n, n) float64 distances format_distances prints (model_average of both directions; diagonal +0.0)."""
+    M = np.ascontiguousarray(M, dtype=np.uint32)
+    n = M.shape[0]
+    assert M.shape == (n, n, 17)
+    D = np.empty((n, n), np.float64)
+    if load().andi_hip_distances(M.ctypes.data, n, model, D.ctypes.data):
+        raise AndiHipError("andi_hip_distances failed")
+    return D
+
+
+def newick(joins, names, truncate_names=False):
+    """The Newick line (ending in ";\n") of nj's records for the leaves `names`."""
+    J = np.ascontiguousarray(joins, dtype=NJ_JOIN)
+    n = len(names)
+    cn = _names(names)
+    cap = 64 + 40 * n + sum(len(x) for x in names)
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_newick(J.ctypes.data, n, cn, int(truncate_names), C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
 
 
 # ---------------------------------------------------------------- device objects
@@ -544,6 +578,17 @@ def bootstrap(ctx: Context, M, replicates, seed=0):
     B = np.empty((replicates, n, n, 17), np.uint32)
     ctx._check(load().andi_hip_bootstrap(ctx._h, M.ctypes.data, n, seed, replicates, B.ctypes.data), "bootstrap")
     return B
+
+
+def nj(ctx: Context, D):
+    """Neighbor-joining of the (n, n) distances D on the device (andi_hip_nj; only the upper triangle is read): the n - 2
+    records (one for n = 2) as a structured array of dtype NJ_JOIN."""
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    J = np.zeros(1 if n == 2 else max(n - 2, 0), NJ_JOIN)
+    ctx._check(load().andi_hip_nj(ctx._h, D.ctypes.data, n, J.ctypes.data), "nj")
+    return J
 
 
 def _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host, progress=None):

@@ -15,7 +15,8 @@
  *
  * ABI 5 also gained, without changing anything that was there, the query-versus-
  * reference mode: andi_hip_dist_rect, andi_hip_queries_view and
- * andi_hip_format_distances_rect (additions only; the version stays 5).
+ * andi_hip_format_distances_rect (additions only; the version stays 5); and the tree the matrix feeds:
+ * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -167,6 +168,28 @@ size_t andi_hip_format_distances_rect(const andi_hip_model *MRQ, const andi_hip_
 									  int model, int extra_verbose, int truncate_names, int warnings,
 									  char *out, size_t cap, char *warnbuf, size_t warncap, int *warn_flags);
 
+/* The distance matrix as doubles: D[i*n+j] = D[j*n+i] = andi_hip_estimate(model_average(M[i][j], M[j][i]), model) for
+ * i != j -- the unrounded value andi_hip_format_distances prints for that cell (without extra_verbose; it is the same
+ * computation) -- and D[i*n+i] = +0.0.  Row-parallel like the formatter.  Returns 1 on NULL pointers or when memory runs
+ * out.  No GPU is touched. */
+int andi_hip_distances(const andi_hip_model *M, size_t n, int model, double *D);
+
+/* One record of a neighbor-joining tree (andi_hip_nj): node ids a, b (and c for the final record, else -1) with the
+ * lengths of their branches.  40 bytes. */
+typedef struct {
+	int32_t a, b, c, pad;
+	double la, lb, lc;
+} andi_hip_nj_join;
+/* The Newick text of andi_hip_nj's records J (n leaves: n - 2 records, one for n = 2), one line ending in ";\n".  A leaf is
+ * names[i] (cut to ten characters under truncate_names, as the matrix prints it), in single quotes with every ' doubled
+ * if it holds a blank, a tab or one of ( ) [ ] ' : ; ,; a pair record is "(" T(a) ":" L(la) "," T(b) ":" L(lb) ")"; the
+ * final record "(" T(x):L(lx) "," T(y):L(ly) "," T(z):L(lz) ");" (two children for n = 2); L is %.8g.  Not recursive:
+ * any depth works.  Returns the bytes needed without the NUL, writes at most cap and NUL-terminates (as
+ * andi_hip_format_distances); records whose ids are not those andi_hip_nj gives (a child that is no leaf and no earlier
+ * record's node) give 0 and an empty string. */
+size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+							  char *out, size_t cap);
+
 /* ------------------------------------------------------------------ */
 /* Device-resident objects                                             */
 /* ------------------------------------------------------------------ */
@@ -262,6 +285,27 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects,
  * GSL from the clock, so only the distribution can be compared, not the draws. */
 int andi_hip_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uint64_t seed,
 					   size_t replicates, andi_hip_model *B);
+
+/* Neighbor-joining (Saitou & Nei 1987, as PHYLIP's neighbor) of the n x n distance matrix D (host memory, row-major) on
+ * the context's device.  Only D[i][j] with i < j is read; those entries are mirrored, the diagonal and the lower
+ * triangle are ignored.  Writes n - 2 records for n >= 3 -- n - 3 pair joins, then the final three -- and one for n = 2.
+ * A non-finite entry fails through the context's error, which names the first such D[i][j] in row-major order; nothing
+ * is written then.  2 <= n <= 65535; bad arguments fail with 1 before any HIP call.  Synchronous.
+ *
+ * The result is bit-exact to this contract (tests/nj_model.py restates it):
+ *  - leaf i has id i and starts in slot i; the node join step s creates (from 0) has id n + s and takes the lower slot of
+ *    its two children; the other slot leaves the active set;
+ *  - a step with r >= 4 active nodes: R_x is the sequential sum, from +0.0, of D[x][k] over the active slots k in
+ *    ascending order (x included, D[x][x] = +0.0); for each active pair, with x the member of smaller id,
+ *    Q = ((double)(r-2) * D[x][y] - R_x) - R_y, each operation rounded; the least Q by value (-0.0 == +0.0) is joined,
+ *    ties to the smaller id(x), then the smaller id(y); with a the smaller id, b the other and d = D[a][b]:
+ *    la = d*0.5 + (R_a - R_b) / (double)(2*(r-2)), lb = d - la, record {a, b, -1, 0, la, lb, 0.0}; for every other
+ *    active k, D[u][k] = D[k][u] = ((D[a][k] + D[b][k]) - d) * 0.5, D[u][u] = +0.0;
+ *  - r = 3: the nodes x < y < z by id, lx = ((D[x][y] + D[x][z]) - D[y][z]) * 0.5, ly = ((D[x][y] + D[y][z]) - D[x][z]) * 0.5,
+ *    lz = ((D[x][z] + D[y][z]) - D[x][y]) * 0.5, record {x, y, z, 0, lx, ly, lz};
+ *  - n = 2: {0, 1, -1, 0, D[0][1]*0.5, D[0][1]*0.5, 0.0};
+ *  - negative branch lengths are kept as computed. */
+int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *joins);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);

@@ -1,0 +1,201 @@
+"""Neighbor-joining trees without a GPU: the distances as doubles (andi_hip_distances) against the PHYLIP formatter's
+cells, the Newick formatter (andi_hip_format_newick) against tests/nj_model.py, andi_hip_nj's argument checks, and the
+command line's --tree option."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import nj_model
+from conftest import ROOT
+
+CLI = os.path.join(ROOT, "andi_amd", "andi-hip")
+NEW = ("andi_hip_distances", "andi_hip_nj", "andi_hip_format_newick")
+
+
+def _matrix(rng, n, low=2000):
+    M = np.zeros((n, n, 17), np.uint32)
+    for i in range(n):
+        for j in range(n):
+            if i == j:
+                M[i, j, 0] = M[i, j, 16] = 9
+                continue
+            total = int(rng.integers(low, 3_000_000))
+            p = rng.dirichlet(np.r_[np.full(4, 40.0), np.full(12, 0.6)])
+            c = rng.multinomial(total, p)
+            M[i, j, [0, 5, 10, 15]] = c[:4]
+            M[i, j, [1, 2, 3, 4, 6, 7, 8, 9, 11, 12, 13, 14]] = c[4:]
+            M[i, j, 16] = total + int(rng.integers(0, 1000))
+    return M
+
+
+def test_both_libraries_export_the_tree_entry_points():
+    from andi_amd import lib
+    for so in ("libandihip.so", "libandihip_test.so"):
+        L = C.CDLL(os.path.join(ROOT, "andi_amd", so))
+        for name in NEW:
+            assert getattr(L, name) is not None, (so, name)
+    header = open(os.path.join(ROOT, "include", "andi_hip.h")).read()
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, header) and name in lib.SYMBOLS
+    assert lib.load().andi_hip_abi_version() == 5
+
+
+@pytest.mark.parametrize("model", range(5))
+def test_distances_are_the_printed_cells(model):
+    from andi_amd import lib
+    rng = np.random.default_rng(100 + model)
+    n = 9
+    M = _matrix(rng, n)
+    M[2, 5, :] = 0  # a pair without anchors: nan from both directions' sum ...
+    M[5, 2, :] = 0
+    M[5, 2, 16] = M[2, 5, 16] = 1000
+    D = lib.distances(M, model)
+    text, _, _ = lib.format_distances(M, ["s%d" % i for i in range(n)], model, warnings=False)
+    rows = text.splitlines()[1:]
+    sci = "e" in rows[0].split()[1]
+    for i in range(n):
+        cells = rows[i].split()[1:]
+        for j in range(n):
+            if np.isnan(D[i, j]):  # (C prints a NaN with its sign bit as -nan)
+                assert cells[j] in ("nan", "-nan"), (model, i, j)
+            else:
+                assert (("%1.4e" if sci else "%1.4f") % D[i, j]) == cells[j], (model, i, j)
+    assert np.isnan(D[2, 5]) and np.isnan(D[5, 2])  # ... where the matrix says nan
+    assert (D.view(np.uint64) == D.T.view(np.uint64)).all()
+    assert (np.diag(D).view(np.uint64) == 0).all()  # +0.0, not -0.0
+
+
+def test_distances_of_a_larger_matrix_match_the_estimate_per_pair():
+    from andi_amd import lib
+    rng = np.random.default_rng(7)
+    n = 150  # (several formatter threads)
+    M = _matrix(rng, n)
+    D = lib.distances(M, lib.M_KIMURA)
+    for i, j in [(0, 1), (3, 149), (77, 12), (148, 149)]:
+        avg = M[i, j].astype(np.uint64) + M[j, i]
+        assert D[i, j] == lib.estimate(avg.astype(np.uint32), lib.M_KIMURA)
+    assert (D.view(np.uint64) == D.T.view(np.uint64)).all()
+
+
+@pytest.mark.parametrize("n", [2, 3, 4, 50])
+def test_newick_matches_the_model(n):
+    from andi_amd import lib
+    rng = np.random.default_rng(n)
+    D = rng.uniform(0.0, 1.0, (n, n))
+    J = nj_model.nj(D)
+    names = ["taxon_%d" % i for i in range(n)]
+    text = lib.newick(J, names)
+    assert text == nj_model.newick(J, names)
+    leaves, splits, _ = nj_model.parse_newick(text)
+    assert sorted(leaves) == sorted(names) and text.endswith(";\n")
+    assert text.count("(") == text.count(")") == max(n - 2, 1)
+
+
+def test_newick_quotes_and_truncates_names():
+    from andi_amd import lib
+    names = ["plain", "with blank", "it's", "a:b", "x,y", "(p)", "[q]", "semi;colon", "tab\there", "averyverylongname",
+             "long name's quoted"]
+    n = len(names)
+    J = nj_model.nj(np.random.default_rng(1).uniform(0.1, 1.0, (n, n)))
+    for trunc in (False, True):
+        text = lib.newick(J, names, truncate_names=trunc)
+        assert text == nj_model.newick(J, names, truncate_names=trunc), trunc
+        leaves, _, _ = nj_model.parse_newick(text)
+        want = [s[:10] for s in names] if trunc else names
+        assert sorted(leaves) == sorted(want)
+    text = lib.newick(J, names)
+    assert "'with blank'" in text and "'it''s'" in text and "plain:" in text and "'tab\there'" in text
+    assert "averyveryl:" in lib.newick(J, names, truncate_names=True)
+
+
+def test_newick_return_value_and_a_small_cap():
+    from andi_amd import lib
+    n = 12
+    J = nj_model.nj(np.random.default_rng(3).uniform(0.1, 1.0, (n, n)))
+    names = ["n%d" % i for i in range(n)]
+    full = nj_model.newick(J, names).encode()
+    Jc = np.ascontiguousarray(J, dtype=lib.NJ_JOIN)
+    L = lib.load()
+    for cap in (0, 1, 7, len(full), len(full) + 1):
+        buf = C.create_string_buffer(b"\x7f" * (cap + 4))
+        need = L.andi_hip_format_newick(Jc.ctypes.data, n, lib._names(names), 0, C.cast(buf, C.c_void_p) if cap else None,
+                                        cap)
+        assert need == len(full), cap
+        if cap:
+            k = min(len(full), cap - 1)
+            assert buf.raw[:k] == full[:k] and buf.raw[k] == 0, cap
+            assert buf.raw[cap:cap + 4] == b"\x7f" * 4  # nothing beyond cap
+
+
+def test_newick_of_a_65535_leaf_caterpillar():
+    from andi_amd import lib
+    n = 65535
+    J = np.zeros(n - 2, lib.NJ_JOIN)
+    # join leaf 0 and 1, then that node with leaf 2, ... : the deepest possible tree
+    J["a"][0], J["b"][0] = 0, 1
+    J["a"][1:n - 3] = n + np.arange(n - 4)
+    J["b"][1:n - 3] = np.arange(2, n - 2)
+    J["la"], J["lb"] = 0.5, 0.25
+    J[n - 3] = (n - 2, n - 1, n + n - 4, 0, 0.125, 0.125, 0.125)
+    names = ["t%d" % i for i in range(n)]
+    text = lib.newick(J, names)
+    assert text.startswith("(t65533:0.125,t65534:0.125," + "(" * (n - 3) + "t0:0.5,t1:0.25):0.5,t2:0.25):0.5,t3:0.25)")
+    assert text.endswith(",t65532:0.25):0.125);\n")
+    assert text == nj_model.newick(J, names)
+    assert text.count("(") == n - 2
+
+
+def test_newick_refuses_records_that_are_no_tree():
+    from andi_amd import lib
+    J = nj_model.nj(np.random.default_rng(4).uniform(0.1, 1.0, (5, 5)))
+    J["a"][0] = 5 + 1  # a node no earlier record made
+    assert lib.newick(J, ["a", "b", "c", "d", "e"]) == ""
+
+
+def test_nj_rejects_bad_arguments_without_a_device_call():
+    from andi_amd import lib
+    L = lib.load()
+    D = np.zeros((4, 4))
+    J = np.zeros(4, lib.NJ_JOIN)
+    assert L.andi_hip_nj(None, D.ctypes.data, 4, J.ctypes.data) == 1
+    # with no context, nothing else is looked at; the other checks come before any HIP call too
+    for args in [(None, None, 4, J.ctypes.data), (None, D.ctypes.data, 4, None), (None, D.ctypes.data, 1, J.ctypes.data),
+                 (None, D.ctypes.data, 0, J.ctypes.data), (None, D.ctypes.data, 65536, J.ctypes.data)]:
+        assert L.andi_hip_nj(*args) == 1, args
+
+
+def _fasta(path, name, seq):
+    with open(path, "w") as f:
+        f.write(">%s\n%s\n" % (name, seq))
+    return str(path)
+
+
+def test_cli_lists_the_tree_option():
+    p = subprocess.run([CLI, "--help"], capture_output=True, timeout=60)
+    assert p.returncode == 0 and "--tree=FILE" in p.stdout.decode()
+
+
+def test_cli_refuses_a_tree_of_the_reference_table(tmp_path):
+    a = _fasta(tmp_path / "a.fa", "a", "ACGT" * 400)
+    b = _fasta(tmp_path / "b.fa", "b", "ACGA" * 400)
+    for ref in ("--reference=" + a, "--reference-list=" + str(tmp_path / "list")):
+        p = subprocess.run([CLI, "--tree=" + str(tmp_path / "t.nwk"), ref, b], capture_output=True, timeout=60)
+        assert p.returncode == 1 and "--tree" in p.stderr.decode() and p.stdout == b""
+    # -b with --reference keeps its own message
+    p = subprocess.run([CLI, "-b", "2", "--reference=" + a, b], capture_output=True, timeout=60)
+    assert p.returncode == 1
+    assert "Bootstrapping (-b) is not available together with --reference" in p.stderr.decode()
+
+
+def test_cli_fails_on_an_unwritable_tree_file(tmp_path):
+    a = _fasta(tmp_path / "a.fa", "a", "ACGT" * 400)
+    b = _fasta(tmp_path / "b.fa", "b", "ACGA" * 400)
+    bad = str(tmp_path / "no" / "such" / "dir" / "t.nwk")
+    p = subprocess.run([CLI, "--tree=" + bad, a, b], capture_output=True, timeout=60)
+    err = p.stderr.decode()
+    assert p.returncode == 1 and bad in err and p.stdout == b""
+    assert "Comparing" not in err and "sequence" not in err  # (reported before any sequence is read)
