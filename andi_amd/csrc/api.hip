@@ -583,7 +583,7 @@ int esa_sort_suffixes(andi_hip_ctx *ctx, andi_hip_esa *e) {
 		ctx->sa_ws_bytes = need;
 	}
 	if (!ctx->sa_pinned && !(ctx->sa_pinned = (int32_t *)host_pool::word_get())) HIP_TRY(ctx, hipErrorOutOfMemory);
-	if (!e->rec && !andi_knob(KNOB_NO_SORTED_RECORDS)) { // (experiments: the index build then gathers from the text, as with a host-made suffix array)
+	if (!e->rec) {
 		HIP_TRY(ctx, andi_arena::dev_malloc((void **)&e->rec, (e->cap + 8) * sizeof(uint32_t)));
 		HIP_TRY(ctx, andi_arena::dev_malloc((void **)&e->rec2, (e->cap + 8) * sizeof(uint16_t)));
 		e->bytes += (e->cap + 8) * (sizeof(uint32_t) + sizeof(uint16_t));

@@ -48,29 +48,19 @@ __device__ __forceinline__ uint32_t pool_flag_of(uint32_t w) {
 	return (w & 0x1fu) | (((w >> 5) & 3u) << W_NX_SHIFT);
 }
 struct PoolScratch { // a window's scratch in global memory, one per resident wavefront
-	uint32_t *bits;  // [64 maxchunks + 64] bit (x - wbase): query symbol x != subject symbol x + dg
-	uint32_t *ebits; // (-DPOOL_SEPARATE_EBITS, the A/B build of round 5's layout: [64 maxchunks + 64] sweep R's stretches in a bitmap of their own; by default they are or-ed into `bits` and this is null)
+	uint32_t *bits;  // [64 maxchunks + 64] bit (x - wbase): query symbol x != subject symbol x + dg; sweep R ors its stretches in
 	PoolRec *rec;    // [hc]
 	PoolRes *res;    // [hc]
 	uint32_t hc;        // heads of a window that are walked (more: nothing is decided from the first one dropped on)
 	uint32_t maxchunks; // rounds of 2048 positions of a window at most
 };
 __host__ __device__ inline size_t pool_scratch_bytes(uint32_t maxchunks, uint32_t hc) {
-#ifdef POOL_SEPARATE_EBITS
-	return 2 * (size_t)(64 * maxchunks + 64) * sizeof(uint32_t) + (size_t)hc * (sizeof(PoolRec) + sizeof(PoolRes));
-#else
 	return (size_t)(64 * maxchunks + 64) * sizeof(uint32_t) + (size_t)hc * (sizeof(PoolRec) + sizeof(PoolRes));
-#endif
 }
 __device__ __forceinline__ PoolScratch pool_scratch_at(void *base, size_t idx, uint32_t maxchunks, uint32_t hc) {
 	char *p = (char *)base + idx * pool_scratch_bytes(maxchunks, hc);
 	PoolScratch g;
 	g.bits = (uint32_t *)p, p += (size_t)(64 * maxchunks + 64) * sizeof(uint32_t);
-#ifdef POOL_SEPARATE_EBITS
-	g.ebits = (uint32_t *)p, p += (size_t)(64 * maxchunks + 64) * sizeof(uint32_t);
-#else
-	g.ebits = nullptr;
-#endif
 	g.rec = (PoolRec *)p, p += (size_t)hc * sizeof(PoolRec);
 	g.res = (PoolRes *)p;
 	g.hc = hc, g.maxchunks = maxchunks;
@@ -211,9 +201,10 @@ __device__ __forceinline__ Planes ld_subject_planes(const PairCtx &c, int64_t s)
 // The same two fetches as the words come from memory -- no use of a loaded value, so that the loads of round t + 1 stay in flight
 // while round t is worked on (ld_subject_planes shifts its words at once: the wait for them then stands right behind the loads,
 // and sweep S paid the stream's whole latency every round; round 6) -- and what turns them into planes.
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x3_t __attribute__((ext_vector_type(3)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+// (aligned(4): the words lie at 4-byte multiples only -- three per block of 32 symbols)
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t u32x3_t __attribute__((ext_vector_type(3), aligned(4)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4), aligned(4)));
 struct RawPlanes { // (whole registers tuples as the loads deliver them: taken apart only where they are used -- a struct of nine words was
 	u32x3_t q;     // copied word by word at the loop's head, with the wait for the loads in front of the copies)
 	u32x4_t a;     // subject block: planes 0, 1, 2 and plane 0 of the next block
@@ -711,19 +702,12 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 	uint32_t eq0 = 0, eq1 = 0, eq2 = 0, eq3 = 0;      // (per lane) equal pairs in the stretches, by nucleotide: summed over the lanes once per window
 	// (an LDS add of every lane to one cell is turned into a scalar loop over the lanes by the compiler: 1500 scalar instructions per round of heads)
 	bool done = false;
-#ifdef POOL_SEPARATE_EBITS
-	for (uint32_t w = lane; w < nwords + 4; w += 64) G->ebits[w] = 0;
-	pool_sync();
-#define POOL_GAPBITS ebits
-#else
 	// The stretches are or-ed into the window's mismatch bits themselves (round 6; until then a second bitmap, zeroed and read
 	// back per window: 32 KB of the scratch traffic of a window of 131072 positions).  Every reader of the bits inside this sweep
 	// decides the same with or without a stretch's bits, whichever it happens to see: the first bit at or after a landing
 	// (pool_next_bit) is a mismatch -- stretches start at heads, which are mismatches --, and the last bit before a head or
 	// before `cur` (pool_prev_bit*) is compared with where the hop before landed: a bit inside that hop's stretch lies before
 	// its landing like the mismatches it covers.  Sweep S writes every word anew for the next window.
-#define POOL_GAPBITS bits
-#endif
 	for (uint32_t base = 0; base < nheads && !done; base += 64) {
 		const uint32_t k = base + lane;
 		const bool valid = k < nheads;
@@ -805,12 +789,12 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 						uint32_t m = ~0u;
 						if (t == 0) m &= ~0u << (o0 & 31u);
 						if (32 * wd + 32 > o1) m &= (1u << (o1 & 31u)) - 1u;
-						if (32 * wd < o1) (void)__hip_atomic_fetch_or(&G->POOL_GAPBITS[wd], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // (two stretches may meet in a word)
+						if (32 * wd < o1) (void)__hip_atomic_fetch_or(&G->bits[wd], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // (two stretches may meet in a word)
 					}
 					for (uint32_t wd = wd0 + 3; 32 * wd < o1; ++wd) {
 						uint32_t m = ~0u;
 						if (32 * wd + 32 > o1) m &= (1u << (o1 & 31u)) - 1u;
-						(void)__hip_atomic_fetch_or(&G->POOL_GAPBITS[wd], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+						(void)__hip_atomic_fetch_or(&G->bits[wd], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 					}
 				}
 				// (2) the equal symbols of an ordinary stretch (its mismatches were counted in sweep S): from the head's record; stretches
@@ -856,7 +840,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 	}
 	CSTAT(CS_MOVED, 1);
 	CSTAT(CS_COVERED, cur - e0);
-	pool_sync(); // (the stretches are in G->ebits: the atomics are done; the loads below read the device's copy, not this CU's cache)
+	pool_sync(); // (the stretches are in G->bits: the atomics are done; the loads below read the device's copy, not this CU's cache)
 	// the anchor that ends at cur: the one the last hop landed on if no mismatch lies between, else the one behind the mismatch before cur
 	uint32_t aQ, lw = 1;
 	{
@@ -878,7 +862,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 		auto load_gapbits = [&](uint32_t w0) {
 			u64x2_t v = (u64x2_t)(0ull);
 			if (32 * w0 < span && w0 + 4 * lane < nwords) {
-				const unsigned long long *ep = (const unsigned long long *)&G->POOL_GAPBITS[w0 + 4 * lane];
+				const unsigned long long *ep = (const unsigned long long *)&G->bits[w0 + 4 * lane];
 				v.x = __hip_atomic_load(ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v.y = __hip_atomic_load(ep + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			}
 			return v;
@@ -886,11 +870,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 		u64x2_t ev_next = load_gapbits(0);
 		for (uint32_t w0 = 0; 32 * w0 < span && !PKNOCK(3); w0 += 256) {
 			uint32_t u[4], before = 0;
-#ifdef POOL_SEPARATE_EBITS
-			const uint4 mv = *(const uint4 *)&G->bits[w0 + 4 * lane]; // (64 words of padding behind the window's)
-#else
-			const uint4 mv = make_uint4(0, 0, 0, 0); // (the bits with the stretches in them: ev, read past this CU's cache)
-#endif
+			// (the bits with the stretches in them, read past this CU's cache)
 			const uint4 ev = make_uint4((uint32_t)ev_next.x, (uint32_t)(ev_next.x >> 32), (uint32_t)ev_next.y, (uint32_t)(ev_next.y >> 32));
 			ev_next = load_gapbits(w0 + 256);
 #pragma unroll
@@ -902,7 +882,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 					if (e0 > x0) rm &= ~0u << (e0 - x0);
 					if (cur - x0 < WNT) rm &= (1u << (cur - x0)) - 1u;
 				}
-				u[j] = rm && w < nwords ? (pick(mv, j) | pick(ev, j)) & rm : 0u; // (an anchor may end behind the window: no bits there)
+				u[j] = rm && w < nwords ? pick(ev, j) & rm : 0u; // (an anchor may end behind the window: no bits there)
 				if (u[j]) before = x0 + 31u - (uint32_t)__builtin_clz(u[j]) + 2u;
 			}
 			const uint32_t scan = wave_scan_max(before);
@@ -1009,11 +989,6 @@ __device__ __forceinline__ void pool_segment(const ScanArgs &a, PoolLds &L, cons
 			const uint32_t from = st.lastQ + st.lastLen;
 			pool_stream(a, c, ch, L, G, end, chunks, pw);
 			const bool moved = pool_resolve(a, c, ch, L, G, end, pw, through, same);
-#ifdef POOL_FIXED_WINDOWS /* (A/B: round 5's policy) */
-			if (!through) {
-				chunks = a.pool_first;
-			} else
-#endif
 			if (moved && through) {
 				chunks = 2 * chunks < G->maxchunks ? 2 * chunks : G->maxchunks;
 			} else {

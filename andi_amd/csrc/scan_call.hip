@@ -74,10 +74,10 @@ struct ScanPlan {
 	uint32_t seg0 = 0;      // per-pair segment lengths: the shortest class
 	uint32_t max_class = 0;
 	uint64_t max_waves = 0; // per-pair segment lengths: wavefronts if every pair had the shortest segments (the grid)
-	uint32_t seg_factor = 0, quad_min_match = 0, knock = 0, pool_match = 0, route_all_few = 0, route_giveup = 0, route_soft_match = 0;
+	uint32_t seg_factor = 0, quad_min_match = 0, knock = 0, pool_match = 0, route_all_few = 0, route_giveup = 0;
 	uint32_t longest_q = 0, reduce_threads = 0, coop_reduce_threads = 0; // (the lane layouts', layout b's)
 	int exact_equal = 0;
-	bool force_reference = false, force_adaptive = false, debug_stitch = false;
+	bool force_reference = false, force_adaptive = false;
 };
 
 // pass C: 64 threads per pair where no query has more than 64 segments, else the lane scan's block
@@ -87,7 +87,6 @@ ScanPlan plan_call(andi_hip_esa *const *subjects, size_t nsub, const andi_hip_qu
 	ScanPlan P;
 	P.force_reference = andi_knob(KNOB_FORCE_REFERENCE) != nullptr;
 	P.force_adaptive = andi_knob(KNOB_FORCE_ADAPTIVE) != nullptr;
-	P.debug_stitch = andi_knob(KNOB_DEBUG_STITCH) != nullptr;
 	const bool uniform = andi_knob(KNOB_UNIFORM_SEGMENTS) != nullptr;
 	// segment == 0: the engine chooses.  With the lane scan and a moderate number of pairs
 	// the segment length is chosen per pair (scan_lane.hip: k_pair_estimate); otherwise one
@@ -146,7 +145,6 @@ ScanPlan plan_call(andi_hip_esa *const *subjects, size_t nsub, const andi_hip_qu
 	P.route_all_few = call_nt < (small_log ? 1ull << small_log : ANDI_ROUTE_SMALL_NT) ? 1u : 0u;
 	// (tests: hand pairs back early, so that the second lane layout runs; small calls route pairs the sampling cannot judge: a lower limit)
 	P.route_giveup = (uint32_t)knob_int(KNOB_COOP_GIVEUP, 1, INT32_MAX, P.route_all_few ? 256 : 1024);
-	P.route_soft_match = (uint32_t)knob_int(KNOB_ROUTE_SOFT, 1, INT32_MAX, 512); // (128 = k_lane_quad's class: tree-structured set 38.1 -> 39.4 % of the roofline at 512, C3-like 45.6 -> 48.1 %, C4 shape the same)
 	for (size_t i = 0; i < q->nq; ++i) P.longest_q = std::max(P.longest_q, (uint32_t)q->len[i]);
 	P.coop_reduce_threads = reduce_threads(P.longest_q, coop_seg);
 	P.exact_equal = (model == ANDI_M_LOGDET || model == ANDI_M_ANI) ? 1 : 0; // src/model.c:247
@@ -330,7 +328,6 @@ ScanArgs scan_args(andi_hip_ctx *ctx, const ScanPlan &P, size_t nsub, const andi
 	a.reduce_threads = P.reduce_threads;
 	a.route_all_few = P.route_all_few;
 	a.route_giveup = P.route_giveup;
-	a.route_soft_match = P.route_soft_match;
 	a.exact_equal = P.exact_equal;
 	return a;
 }
@@ -384,7 +381,7 @@ hipError_t launch_direct(andi_hip_ctx *ctx, ScanArgs &a, const char *&what) {
 // The pairs are sampled and routed; pass A by wavefronts (on a stream of its own) runs beside the lane scan's kernels; the
 // pairs it handed back -- rare: the host looks -- get a second lane layout a2; passes B and C once per layout.
 hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size_t b_off, const andi_hip_queries *q,
-						 const int64_t *h_self, size_t slots, size_t slots2, const char *&what) {
+						 size_t slots, size_t slots2, const char *&what) {
 	const size_t nsub = a.nsub, pairs_all = nsub * q->nq;
 	ScanArgs b = a;
 	b.adaptive = 0, b.coop = 1, b.route = ANDI_LAYOUT_COOP;
@@ -398,15 +395,6 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 		if (e == hipSuccess) e = andi_launch_pair_layout(a, ctx->stream);
 		t.stop();
 		if (e != hipSuccess) return what = "scan layout", e;
-	}
-	if (P.debug_stitch) { // diagnostics: how the pairs were routed
-		std::vector<uint8_t> cls(pairs_all);
-		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipMemcpy(cls.data(), a.pair_class, pairs_all, hipMemcpyDeviceToHost);
-		size_t n_coop = 0, n_quad = 0, n_other = 0;
-		for (size_t i = 0; i < pairs_all; ++i)
-			if (h_self[i / q->nq] != (int64_t)(i % q->nq)) (cls[i] & ANDI_ROUTE_COOP ? n_coop : cls[i] & 0x80u ? n_quad : n_other)++;
-		fprintf(stderr, "route: %zu pairs by wavefronts, %zu k_lane_quad's class, %zu other lanes (unrelated stretches suspected / short query / many pairs far apart)\n", n_coop, n_quad, n_other);
 	}
 	Timed t(ctx, 1);
 	// Which of the two goes first: the lane scan's kernels where its pairs are few -- behind the wavefront kernel a
@@ -522,19 +510,12 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 	// every error exit from here on first waits for the streams the launches fork work onto: their kernels read the scratch
 	// the next call may regrow, and the context's teardown waits for ctx->stream only
 	const char *what = nullptr;
-	const hipError_t e = P.routed ? launch_routed(ctx, P, a, b_off, q, h_self, slots, slots2, what) : launch_direct(ctx, a, what);
+	const hipError_t e = P.routed ? launch_routed(ctx, P, a, b_off, q, slots, slots2, what) : launch_direct(ctx, a, what);
 	if (e != hipSuccess) {
 		(void)hipStreamSynchronize(ctx->coop_stream);
 		(void)hipStreamSynchronize(ctx->side_stream);
 		(void)hipStreamSynchronize(ctx->stream);
 		return fail(ctx, what, e);
-	}
-	if (P.debug_stitch) { // diagnostics: segments stitched again per round, length of the last stage's list
-		uint32_t h[16];
-		(void)hipStreamSynchronize(ctx->stream);
-		(void)hipMemcpy(h, a.restitch_count, sizeof h, hipMemcpyDeviceToHost);
-		fprintf(stderr, "stitch: %zu slots; true chains that left on their own %u; stitched again in rounds: %u %u %u; last list %u\n", slots,
-				h[ANDI_RESTITCH_ROUNDS], h[0], h[1], h[2], h[8]);
 	}
 	(P.adaptive ? ctx->acc.adaptive_calls : ctx->acc.uniform_calls)++;
 	ctx->acc.scan_pairs += pairs;

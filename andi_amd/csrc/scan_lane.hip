@@ -190,13 +190,14 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 		// some 6 %: their chains probe at nearly every step and meet their neighbours' slowly; with long segments pass B has
 		// few lanes for those replays) -- take it where they are more than a tenth of the call; a few of them ride along
 		// with the wavefront kernel (k_pair_route).  (Pairs of k_lane_quad's class -- mean match 128 ... 511 -- were treated
-		// the same way at first: the wavefront kernel is the faster one for them, route_soft_match.)
+		// the same way at first: the wavefront kernel is the faster one for them.  Soft from a mean match of 512 rather than 128:
+		// tree-structured set 38.1 -> 39.4 % of the roofline, C3-like 45.6 -> 48.1 %, C4 shape the same.)
 		// (a pair that is merely far apart: a candidate of the wavefront kernel like the pairs small calls cannot judge -- not in a call
 		// that has pairs with unrelated stretches (k_pair_route: it may be one of them after all, and would be handed back), and a soft
 		// one: the lane scan's where such pairs are many.  The bench set's 18 farthest pairs ride along with the wavefront kernel
 		// instead of keeping the lane kernels busy beside it for 1.7 ms: step 7.63 -> 7.50 ms)
 		const bool far = islands && far_clean;
-		const bool soft = (sum >> 6) < ANDI_SPARSE_MATCH || (sum >> 6) >= a.route_soft_match || far;
+		const bool soft = (sum >> 6) < ANDI_SPARSE_MATCH || (sum >> 6) >= 512u || far;
 		if (far) islands = false, guess = true;
 		const bool quad = (sum >> 6) >= a.quad_min_match && !(islands && (sum >> 6) < ANDI_ISLAND_MEAN_MAX);
 		a.pair_class[pair] = (uint8_t)(cls | (quad ? 0x80u : 0u) | (coop_cand && !islands ? ANDI_ROUTE_COOP : 0u) | (soft ? ANDI_ROUTE_SOFT : 0u) |
@@ -674,8 +675,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_lane_quad(ScanArgs a) { // (4 wave
 // same divergence and stay in step.  (Persistent lanes that fetch their next segment
 // from a counter when done were measured 15-50 % slower: they mix pairs of different
 // divergence in one wavefront.)
-template <bool EXACT, int OCC, bool PER_PAIR>
-__global__ __launch_bounds__(BLOCK, OCC) void k_lane_cold(ScanArgs a) {
+// Waves per SIMD: per-pair segments 8 (64 registers, two spilled outside the loop): 6.29 ms against 6.41 at 7 and 6.6
+// at 6 on the bench set.  One segment length (the query's base and length are per lane): seven registers would be
+// spilled at 8 -- 7.69 against 6.90 ms at 7 (bench set, 4096-symbol segments), 2.67 against 2.50 (2000 x 16.5 kbp).
+template <bool EXACT, bool PER_PAIR>
+__global__ __launch_bounds__(BLOCK, PER_PAIR ? 8 : 7) void k_lane_cold(ScanArgs a) {
 	__shared__ uint32_t s_hist[16 * BLOCK];
 	if (!PER_PAIR && a.subjects[blockIdx.y].mode != ANDI_MODE_PROBE) return;
 	const LaneItem it = lane_item<BLOCK, PER_PAIR ? 1 : 2>(a);
@@ -1251,16 +1255,6 @@ hipError_t andi_launch_pack_symbols(const uint8_t *src, size_t bytes, uint8_t *N
 	return hipSuccess;
 }
 
-static int lane_occupancy(bool per_pair) { // waves per SIMD pass A is compiled for (experiments: ANDI_LANE_OCC)
-	const char *e = andi_knob(KNOB_LANE_OCC);
-	int v = e ? atoi(e) : 0;
-	if (v == 6 || v == 7 || v == 8) return v;
-	// per-pair segments: 8 (64 registers, two spilled outside the loop): 6.29 ms against 6.41 at 7 and 6.6 at 6 on the
-	// bench set.  One segment length (the query's base and length are per lane): seven registers would be spilled
-	// at 8 -- 7.69 against 6.90 ms at 7 (bench set, 4096-symbol segments), 2.67 against 2.50 (2000 x 16.5 kbp)
-	return per_pair ? 8 : 7;
-}
-
 template <bool EXACT>
 static hipError_t lane_cold(const ScanArgs &a, dim3 grid, hipStream_t st) {
 	const bool blocks4 = andi_knob(KNOB_QUAD_UNLISTED) != nullptr; // (experiments: k_lane_quad's wavefronts in the call's order)
@@ -1284,19 +1278,8 @@ static hipError_t lane_cold(const ScanArgs &a, dim3 grid, hipStream_t st) {
 			if (side) (void)hipEventRecord(a.side_join, a.side_stream);
 		}
 	}
-	if (a.adaptive) {
-		switch (lane_occupancy(true)) {
-			case 6: k_lane_cold<EXACT, 6, true><<<grid, BLOCK, 0, st>>>(a); break;
-			case 7: k_lane_cold<EXACT, 7, true><<<grid, BLOCK, 0, st>>>(a); break;
-			default: k_lane_cold<EXACT, 8, true><<<grid, BLOCK, 0, st>>>(a); break;
-		}
-	} else {
-		switch (lane_occupancy(false)) {
-			case 6: k_lane_cold<EXACT, 6, false><<<grid, BLOCK, 0, st>>>(a); break;
-			case 7: k_lane_cold<EXACT, 7, false><<<grid, BLOCK, 0, st>>>(a); break;
-			default: k_lane_cold<EXACT, 8, false><<<grid, BLOCK, 0, st>>>(a); break;
-		}
-	}
+	if (a.adaptive) k_lane_cold<EXACT, true><<<grid, BLOCK, 0, st>>>(a);
+	else k_lane_cold<EXACT, false><<<grid, BLOCK, 0, st>>>(a);
 	hipError_t e = hipSuccess;
 	if (counted) { // (an error here still joins the side stream: what it runs reads the call's scratch)
 		(void)hipMemcpyAsync(a.h_quad_waves, a.restitch_count + ANDI_QUAD_WAVES, sizeof(uint32_t), hipMemcpyDeviceToHost, a.side_stream);

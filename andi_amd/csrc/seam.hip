@@ -356,8 +356,6 @@ bool Driver::open() {
 	// each with a stream and a workspace of its own, so one subject's small launches and waits hide behind another's
 	// radix passes.
 	size_t sort_width = C.dev_prep && !C.o.low_memory ? std::min<size_t>(4, std::min(C.batch_max, rows)) : 1;
-	if (const char *sw = andi_knob(KNOB_SORT_WIDTH)) // (experiments)
-		if (atoi(sw) >= 1 && atoi(sw) <= 8) sort_width = std::min<size_t>((size_t)atoi(sw), std::min(C.batch_max, rows));
 	// (a workspace of 45 bytes per character each: together at most one chunk of the arena -- eight of them for 9.8 M characters pushed a
 	// 29-genome call past the 8 GiB the arena keeps from call to call, and every call paid the driver for its chunks again: 37 -> 177 ms;
 	// two sorters measured like four, profiles/r07_seam/)

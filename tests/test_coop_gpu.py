@@ -67,7 +67,7 @@ def test_logdet_and_ani_count_every_anchor(model):
     seqs.append(_revcomp(seqs[2]))
     seqs.append(synth.join_contigs(seqs[1], 6))
     want = orc.dist_matrix(seqs, model=model, threads=4)
-    for coop in (2, 5):
+    for coop in (2, 4, 5):
         for segment in (0, 3000):
             got = _matrix(seqs, model, coop, segment)
             assert (got == want).all(), (coop, segment, np.argwhere((got != want).any(axis=2))[:6].tolist())
