@@ -298,7 +298,8 @@ int andi_hip_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uin
  *  - a step with r >= 4 active nodes: R_x is the sequential sum, from +0.0, of D[x][k] over the active slots k in
  *    ascending order (x included, D[x][x] = +0.0); for each active pair, with x the member of smaller id,
  *    Q = ((double)(r-2) * D[x][y] - R_x) - R_y, each operation rounded; the least Q by value (-0.0 == +0.0) is joined,
- *    ties to the smaller id(x), then the smaller id(y); with a the smaller id, b the other and d = D[a][b]:
+ *    ties to the smaller id(x), then the smaller id(y); a NaN Q (finite input can overflow: inf - inf) orders after
+ *    every number, and among NaN Q values the same id order decides; with a the smaller id, b the other and d = D[a][b]:
  *    la = d*0.5 + (R_a - R_b) / (double)(2*(r-2)), lb = d - la, record {a, b, -1, 0, la, lb, 0.0}; for every other
  *    active k, D[u][k] = D[k][u] = ((D[a][k] + D[b][k]) - d) * 0.5, D[u][u] = +0.0;
  *  - r = 3: the nodes x < y < z by id, lx = ((D[x][y] + D[x][z]) - D[y][z]) * 0.5, ly = ((D[x][y] + D[y][z]) - D[x][z]) * 0.5,

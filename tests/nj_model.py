@@ -6,56 +6,83 @@ NJ_JOIN = np.dtype([("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("pad", "<i4"), ("
                     ("lc", "<f8")])
 
 
-def nj(D):
-    """The records andi_hip_nj writes for D (only the upper triangle is read), bit for bit."""
+def nj(D, steps=None):
+    """The records andi_hip_nj writes for D (only the upper triangle is read), bit for bit; with steps=k only the first k
+    records (each is a function of the state before its step alone, so a prefix stands on its own).
+
+    The contract's arithmetic, one step at a time.  C holds D by position, positions in ascending slot order; a join
+    overwrites the lower slot's row and column and retires the other position (live[p] = False).  Retired positions stay
+    in C, unread, until a quarter of C is retired, when C is compacted: no step copies the active block."""
     D = np.asarray(D, dtype=np.float64)
     n = D.shape[0]
+    nrec = 1 if n == 2 else n - 2
+    steps = nrec if steps is None else min(steps, nrec)
     iu = np.triu_indices(n, 1)
-    M = np.zeros((n, n))  # diagonal +0.0
-    M[iu] = D[iu]
-    M.T[iu] = D[iu]
-    if n == 2:
-        h = M[0, 1] * 0.5
-        return np.array([(0, 1, -1, 0, h, h, 0.0)], NJ_JOIN)
-    out = np.zeros(n - 2, NJ_JOIN)
-    ids = np.arange(n)
-    active = np.ones(n, bool)
-    for s in range(n - 3):
-        r = n - s
-        act = np.flatnonzero(active)  # ascending slots
-        sub = M[np.ix_(act, act)]
-        # R: a sequential sum per column from +0.0 (np.cumsum is sequential, np.sum pairwise); D is symmetric
-        R = np.cumsum(np.vstack([np.zeros((1, r)), sub]), axis=0)[-1]
-        idl = ids[act]
-        x_first = idl[:, None] < idl[None, :]  # row member has the smaller id
-        Rx = np.where(x_first, R[:, None], R[None, :])
-        Ry = np.where(x_first, R[None, :], R[:, None])
-        Q = (np.float64(r - 2) * sub - Rx) - Ry
-        Q[np.arange(r), np.arange(r)] = np.inf
-        cand = np.argwhere(Q == Q.min())
-        lo = np.minimum(idl[cand[:, 0]], idl[cand[:, 1]])
-        hi = np.maximum(idl[cand[:, 0]], idl[cand[:, 1]])
-        k = np.lexsort((hi, lo))[0]
-        pi, pj = cand[k]
-        if idl[pi] > idl[pj]:
-            pi, pj = pj, pi
-        sa, sb = act[pi], act[pj]
-        d = M[sa, sb]
-        la = d * 0.5 + (R[pi] - R[pj]) / np.float64(2 * (r - 2))
-        lb = d - la
-        out[s] = (ids[sa], ids[sb], -1, 0, la, lb, 0.0)
-        su, so = min(sa, sb), max(sa, sb)
-        others = act[(act != sa) & (act != sb)]
-        v = ((M[sa, others] + M[sb, others]) - d) * 0.5
-        M[su, others] = v
-        M[others, su] = v
-        M[su, su] = 0.0
-        active[so] = False
-        ids[su] = n + s
-    act = np.flatnonzero(active)
-    x, y, z = act[np.argsort(ids[act])]
-    xy, xz, yz = M[x, y], M[x, z], M[y, z]
-    out[n - 3] = (ids[x], ids[y], ids[z], 0, ((xy + xz) - yz) * 0.5, ((xy + yz) - xz) * 0.5, ((xz + yz) - xy) * 0.5)
+    C = np.zeros((n, n))  # diagonal +0.0
+    C[iu] = D[iu]
+    C.T[iu] = D[iu]
+    out = np.zeros(steps, NJ_JOIN)
+    if steps and n == 2:
+        h = C[0, 1] * 0.5
+        out[0] = (0, 1, -1, 0, h, h, 0.0)
+    if steps == 0 or n == 2:
+        return out
+    ids = np.arange(n)  # ids[p]: the id of the node at position p
+    live = np.ones(n, bool)
+    with np.errstate(all="ignore"):  # (overflow of finite input: inf and NaN are part of the contract)
+        for s in range(min(steps, n - 3)):
+            r = n - s
+            if len(live) - r > len(live) // 4:
+                C, ids, live = C[np.ix_(live, live)], ids[live], live[live]
+            # R_x: a sequential sum over the active slots in ascending order from +0.0, one row of C at a time (C is
+            # symmetric: row k is column k); entries at retired positions are never read below
+            R = np.zeros(len(live))
+            for k in np.flatnonzero(live):
+                R += C[k]
+
+            def q_rows(p0):
+                """Q for rows p0 .. p0+63 (row x, column y: ((r-2) * D[x][y] - R_x) - R_y), and which entries are
+                candidates: x and y active and id(x) < id(y), so every active pair once, with x the smaller id"""
+                rows = slice(p0, p0 + 64)
+                Q = (np.float64(r - 2) * C[rows] - R[rows, None]) - R[None, :]
+                pair = live[rows, None] & live[None, :] & (ids[rows, None] < ids[None, :])
+                return Q, pair
+
+            # the least Q by value (-0.0 == +0.0); a NaN Q orders after every number
+            least = {}  # row block -> its least non-NaN Q
+            for p0 in range(0, len(live), 64):
+                Q, pair = q_rows(p0)
+                num = pair & ~np.isnan(Q)
+                if num.any():
+                    least[p0] = Q.min(where=num, initial=np.inf)
+            if least:
+                m = min(least.values())
+                px, py = [], []
+                for p0 in (p0 for p0, q in least.items() if q == m):
+                    Q, pair = q_rows(p0)
+                    x, y = np.nonzero(pair & (Q == m))
+                    px.append(x + p0)
+                    py.append(y)
+                px, py = np.concatenate(px), np.concatenate(py)
+                k = np.lexsort((ids[py], ids[px]))[0]  # ties: the smaller id(x), then the smaller id(y)
+                pa, pb = px[k], py[k]
+            else:  # every Q is NaN: the id order alone, so the two smallest ids
+                pa, pb = sorted(np.flatnonzero(live), key=lambda p: ids[p])[:2]
+            d = C[pa, pb]
+            la = d * 0.5 + (R[pa] - R[pb]) / np.float64(2 * (r - 2))
+            out[s] = (ids[pa], ids[pb], -1, 0, la, d - la, 0.0)
+            pu, po = min(pa, pb), max(pa, pb)  # the new node takes the lower slot, the other retires
+            v = ((C[pa] + C[pb]) - d) * 0.5
+            v[pu] = 0.0
+            C[pu], C[:, pu] = v, v
+            ids[pu] = n + s
+            live[po] = False
+        if steps == n - 2:
+            act = np.flatnonzero(live)
+            x, y, z = act[np.argsort(ids[act])]  # (r = 3)
+            xy, xz, yz = C[x, y], C[x, z], C[y, z]
+            out[n - 3] = (ids[x], ids[y], ids[z], 0, ((xy + xz) - yz) * 0.5, ((xy + yz) - xz) * 0.5,
+                          ((xz + yz) - xy) * 0.5)
     return out
 
 

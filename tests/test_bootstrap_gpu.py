@@ -118,3 +118,50 @@ def test_bootstrap_cells_chi_square_against_the_oracle(ctx, orc):
             scale = np.sqrt(np.outer(np.diag(theory), np.diag(theory)))
             assert np.abs((cg - theory) / scale).max() < 0.08 and np.abs((co - theory) / scale).max() < 0.08
     print("smallest p-value over all cells and groups: %.3g" % worst)
+
+
+def test_bootstrap_at_full_length_counts_against_the_exact_law_and_the_oracle(ctx, orc):
+    """The same comparison at the counts of two 50 Mbp genomes (C5): N ~ 10^8 per pair, about 5 * 10^7 from each
+    direction.  Pair (0, 1): the diagonal at p ~ 0.25 (BTRS with n ~ 10^8), off-diagonal cells of 3 .. 150 (p ~ 10^-7 ..
+    10^-6, so n p falls on both sides of the switch from waiting times to BTRS at 10), and cell 10 holding more than half
+    of what is left after cell 9 (the flipped branch, p > 0.5).  Pair (0, 2): cell 0 alone is 0.6 of N (flipped at n =
+    10^8).  Pair (1, 2): a late tiny cell before a large last one (waiting times with n ~ 2 * 10^7)."""
+    import andi_amd
+    from conftest import binomial_gof_pvalue, two_sample_pvalue
+    reps = 10000
+    M = np.zeros((3, 3, 17), np.uint32)
+    M[0, 1, :16] = [12_500_000, 3, 8, 12, 30, 12_400_000, 60, 100, 150, 2, 15_000_000, 9, 20, 1, 40, 10_100_000]
+    M[1, 0, :16] = [12_400_000, 0, 2, 1, 9, 12_500_000, 40, 20, 100, 3, 14_900_000, 11, 25, 2, 35, 10_200_000]
+    M[0, 2, :16] = [30_000_000, 70, 15, 4, 25, 7_000_000, 300, 18, 2, 6, 6_500_000, 50, 90, 11, 3, 6_600_000]
+    M[2, 0, :16] = [30_100_000, 65, 12, 7, 20, 6_900_000, 280, 22, 1, 4, 6_400_000, 40, 80, 14, 5, 6_700_000]
+    M[1, 2, :16] = [12_000_000, 500, 400, 300, 200, 13_000_000, 100, 50, 40, 30, 12_000_000, 20, 10, 5, 2, 13_000_000]
+    M[2, 1, :16] = [12_100_000, 450, 420, 310, 190, 12_900_000, 110, 45, 35, 25, 12_100_000, 15, 12, 4, 1, 12_900_000]
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        M[i, j, 16], M[j, i, 16] = 50_000_000 + i, 50_100_000 + j
+    G = andi_amd.bootstrap(ctx, M, reps, seed=5050)
+    O = orc.bootstrap(M, reps, seed=5050)
+    worst = 1.0
+    for i, j in ((0, 1), (0, 2), (1, 2)):
+        c = M[i, j, :16].astype(np.int64) + M[j, i, :16]
+        N = int(c.sum())
+        assert 0.9e8 < N < 1.1e8
+        g, o = G[:, i, j, :16].astype(np.int64), O[:, i, j, :16].astype(np.int64)
+        assert (g.sum(axis=1) == N).all() and (o.sum(axis=1) == N).all()
+        assert (G[:, i, j] == G[:, j, i]).all()
+        assert (G[:, i, j, 16] == int(M[i, j, 16]) + int(M[j, i, 16])).all()  # seq_len is summed
+        groups = [(k,) for k in np.nonzero(c)[0]] + [(0, 5), (0, 5, 10, 15), (1, 2, 3, 4), (10, 15), (13, 14),
+                                                     (6, 7, 8, 9, 11)]
+        for cells in groups:
+            xs, ys, pc = g[:, list(cells)].sum(axis=1), o[:, list(cells)].sum(axis=1), c[list(cells)].sum() / N
+            p1, p2, p3 = binomial_gof_pvalue(xs, N, pc), binomial_gof_pvalue(ys, N, pc), two_sample_pvalue(xs, ys)
+            worst = min(worst, p1, p3)
+            assert p1 > 1e-5, ("device vs Binomial", i, j, cells, p1)
+            assert p2 > 1e-5, ("oracle vs Binomial", i, j, cells, p2)
+            assert p3 > 1e-5, ("device vs oracle", i, j, cells, p3)
+        # the covariance of the cells: N p_a (1 - p_a) on the diagonal, -N p_a p_b off it
+        big = np.nonzero(c * (N - c) / N > 50)[0]
+        cg, co = np.cov(g[:, big].T), np.cov(o[:, big].T)
+        theory = -np.outer(c[big], c[big]) / N + np.diag(c[big].astype(np.float64))
+        scale = np.sqrt(np.outer(np.diag(theory), np.diag(theory)))
+        assert np.abs((cg - theory) / scale).max() < 0.08 and np.abs((co - theory) / scale).max() < 0.08, (i, j)
+    print("smallest p-value over all cells and groups: %.3g" % worst)

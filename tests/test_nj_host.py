@@ -1,6 +1,6 @@
 """Neighbor-joining trees without a GPU: the distances as doubles (andi_hip_distances) against the PHYLIP formatter's
-cells, the Newick formatter (andi_hip_format_newick) against tests/nj_model.py, andi_hip_nj's argument checks, and the
-command line's --tree option."""
+cells, the Newick formatter (andi_hip_format_newick) against tests/nj_model.py, andi_hip_nj's argument checks, the
+command line's --tree option, and tests/nj_model.py itself against a second, scalar restatement of the contract."""
 import ctypes as C
 import os
 import re
@@ -199,3 +199,139 @@ def test_cli_fails_on_an_unwritable_tree_file(tmp_path):
     err = p.stderr.decode()
     assert p.returncode == 1 and bad in err and p.stdout == b""
     assert "Comparing" not in err and "sequence" not in err  # (reported before any sequence is read)
+
+
+# ------------------------------------------------- a second restatement of andi_hip_nj's contract, one operation at a time
+def _nj_scalar(D):
+    """include/andi_hip.h's neighbor-joining contract with Python floats (IEEE doubles, each operation rounded) and plain
+    loops, written from the header's text alone: the records as tuples (a, b, c, la, lb, lc)."""
+    n = len(D)
+    M = [[0.0] * n for _ in range(n)]  # by slot; only D[i][j], i < j, is read; the diagonal is +0.0
+    for i in range(n):
+        for j in range(i + 1, n):
+            M[i][j] = M[j][i] = float(D[i][j])
+    if n == 2:
+        return [(0, 1, -1, M[0][1] * 0.5, M[0][1] * 0.5, 0.0)]
+    node = list(range(n))  # node[slot]: the id in that slot
+    active = list(range(n))  # ascending slots
+    out = []
+    for s in range(n - 3):
+        r = len(active)
+        R = {}
+        for x in active:
+            acc = 0.0
+            for k in active:
+                acc = acc + M[x][k]
+            R[x] = acc
+        best = None  # (NaN?, Q, id(x), id(y), slot x, slot y)
+        for i in range(r):
+            for j in range(i + 1, r):
+                x, y = active[i], active[j]
+                if node[x] > node[y]:
+                    x, y = y, x
+                q = (float(r - 2) * M[x][y] - R[x]) - R[y]
+                nan = q != q
+                key = (nan, 0.0 if nan else q, node[x], node[y])  # (-0.0 == +0.0 in the comparison)
+                if best is None or key < best[:4]:
+                    best = key + (x, y)
+        a, b = best[4], best[5]
+        d = M[a][b]
+        la = d * 0.5 + (R[a] - R[b]) / float(2 * (r - 2))
+        out.append((node[a], node[b], -1, la, d - la, 0.0))
+        u, o = min(a, b), max(a, b)
+        for k in active:
+            if k != a and k != b:
+                M[u][k] = M[k][u] = ((M[a][k] + M[b][k]) - d) * 0.5
+        M[u][u] = 0.0
+        node[u] = n + s
+        active.remove(o)
+    x, y, z = sorted(active, key=lambda k: node[k])
+    xy, xz, yz = M[x][y], M[x][z], M[y][z]
+    out.append((node[x], node[y], node[z], ((xy + xz) - yz) * 0.5, ((xy + yz) - xz) * 0.5, ((xz + yz) - xy) * 0.5))
+    return out
+
+
+def _same_records(got, want):
+    """ids exactly; lengths by their bits, except that a NaN only has to be a NaN (its bits are the platform's)"""
+    for f in ("a", "b", "c"):
+        assert (got[f] == want[f]).all(), f
+    assert (got["pad"] == 0).all()
+    for f in ("la", "lb", "lc"):
+        g, w = got[f], want[f]
+        assert (np.isnan(g) == np.isnan(w)).all(), f
+        ok = ~np.isnan(w)
+        assert (g[ok].view(np.uint64) == w[ok].view(np.uint64)).all(), f
+
+
+def _as_records(rows):
+    J = np.zeros(len(rows), nj_model.NJ_JOIN)
+    for s, (a, b, c, la, lb, lc) in enumerate(rows):
+        J[s] = (a, b, c, 0, la, lb, lc)
+    return J
+
+
+def _cases(seed):
+    """(name, D): random, small integers (many exact ties in Q), duplicated leaves at +0.0 and -0.0, a lower triangle and
+    diagonal of garbage, and entries near the largest double, whose Q overflow to +-inf and NaN"""
+    rng = np.random.default_rng(seed)
+    for n in (2, 3, 4, 5, 6, 9, 17, 31, 40):
+        A = rng.uniform(0.0, 1.0, (n, n))
+        yield "random", np.triu(A, 1) + np.triu(A, 1).T
+        yield "garbage below", np.triu(A, 1) + np.tril(rng.uniform(-5, 5, (n, n)))
+        B = np.triu(rng.integers(0, 4, (n, n)).astype(float), 1)
+        yield "small integers", B + B.T
+        idx = np.sort(rng.integers(0, max(2, n // 2), n))
+        base = rng.uniform(0.0, 1.0, (n, n))
+        dup = (base + base.T)[np.ix_(idx, idx)]
+        same = idx[:, None] == idx[None, :]
+        dup[same] = np.where(rng.integers(0, 2, (n, n)) == 1, -0.0, 0.0)[same]
+        yield "duplicated leaves", dup
+        yield "near overflow", _overflowing(rng, n)
+
+
+def _overflowing(rng, n):
+    """finite entries, some of them near the largest double: row sums and (r-2) * D overflow to inf, inf - inf is NaN"""
+    A = rng.uniform(0.0, 1.0, (n, n)) * 1e307
+    A[rng.uniform(size=(n, n)) < 0.5] = rng.uniform(0.0, 1.0) * 10.0 ** rng.integers(0, 300)
+    A[:, rng.integers(0, n)] = 1.7e308
+    return np.triu(A, 1) + np.triu(A, 1).T
+
+
+def test_the_model_is_the_scalar_restatement():
+    overflowed = set()
+    for seed in range(4):
+        for name, D in _cases(seed):
+            want = _as_records(_nj_scalar(D))
+            _same_records(nj_model.nj(D), want)
+            if name == "near overflow":
+                overflowed |= {"nan" for v in want["la"] if np.isnan(v)} | {"inf" for v in want["la"] if np.isinf(v)}
+    assert overflowed == {"nan", "inf"}  # (the overflow cases do reach both)
+
+
+def test_nan_q_orders_after_every_number_then_by_id():
+    # r = 5, Q = (3 D - R_x) - R_y.  Leaves 0 and 1 are 1.7e308 from everything, so every row sum is inf: a pair with 0
+    # or 1 has Q = (inf - inf) - inf = NaN, a pair of 2, 3, 4 has Q = (3 D - inf) - inf = -inf.  NaN orders last.
+    big = 1.7e308
+    D = np.array([[0, big, big, big, big],
+                  [0, 0, big, big, big],
+                  [0, 0, 0, 1, 2],
+                  [0, 0, 0, 0, 3],
+                  [0, 0, 0, 0, 0]], float)
+    J = nj_model.nj(D)
+    _same_records(J, _as_records(_nj_scalar(D)))
+    assert (J["a"][0], J["b"][0]) == (2, 3)
+    # every Q NaN: the smallest pair of ids
+    D = np.full((6, 6), big)
+    J = nj_model.nj(D)
+    _same_records(J, _as_records(_nj_scalar(D)))
+    assert (J["a"][0], J["b"][0]) == (0, 1) and np.isnan(J["la"][0])
+
+
+def test_a_prefix_of_the_model_is_the_whole_run_cut_short():
+    rng = np.random.default_rng(12)
+    for n in (2, 3, 4, 7, 60, 130):
+        A = np.triu(rng.integers(0, 3, (n, n)).astype(float), 1)
+        J = nj_model.nj(A + A.T)
+        for k in sorted({0, 1, n // 3, max(n - 3, 0), n - 2, n}):
+            P = nj_model.nj(A + A.T, steps=k)
+            assert P.dtype == J.dtype and P.tobytes() == J[:k].tobytes(), (n, k)
