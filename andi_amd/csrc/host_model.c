@@ -376,9 +376,10 @@ static void put_leaf(sink *o, const char *name, int truncate) {
 	put(o, "'");
 }
 
-/* andi_hip_nj's records as Newick text (include/andi_hip.h), depth first with a stack of its own instead of recursion */
-size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
-							  char *out, size_t cap) {
+/* andi_hip_nj's records as Newick text (include/andi_hip.h), depth first with a stack of its own instead of recursion;
+ * with support, support[s] is the label behind the ")" of pair record s */
+size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
+									  const char *const *names, int truncate_names, char *out, size_t cap) {
 	sink o = {out, cap, 0};
 	if (out && cap) out[0] = '\0';
 	if (!J || !names || n < 2) return 0;
@@ -407,6 +408,7 @@ size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *c
 			const double len = f->len;
 			depth--;
 			put(&o, ")");
+			if (depth && support) put(&o, "%u", (unsigned)support[f->rec]);
 			if (depth) put(&o, ":%.8g", len);
 			else put(&o, ";\n");
 			continue;
@@ -426,4 +428,9 @@ size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *c
 	free(stack);
 	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
 	return o.len;
+}
+
+size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+							  char *out, size_t cap) {
+	return andi_hip_format_newick_support(J, NULL, n, names, truncate_names, out, cap);
 }

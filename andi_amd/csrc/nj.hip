@@ -12,12 +12,20 @@
 //   k_nj_argmin  the least (Q, id_x, id_y) of every 64 x 64 tile of the active upper triangle, one result per block;
 //   k_nj_join    one block: the least of those results, the record, the new node's row and column, the list compacted.
 // One D2H copy of the records at the end.  No graph capture, no grid-wide barrier, no atomics on the step path.
+//
+// Every kernel takes the REPLICATE as its grid's second dimension (andi_hip_nj_batch): matrices of one n are all at the
+// same r at step s, so a step of a whole group of them is still these three launches.  The buffers hold one replicate
+// after the other -- D (n x n), R (n), the lists (two act lists and the ids: 3n), the tile results, the records -- and a
+// block offsets its pointers by blockIdx.y.  andi_hip_nj is the group of one.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
 
 #include "api_internal.h"
 
@@ -73,9 +81,12 @@ __device__ Cand block_min(Cand c) {
 }
 
 // Mirror the upper triangle (row i = block i), diagonal +0.0; the first non-finite D[i][j], i < j, in row-major order
-// goes to *bad as i * n + j.  act = id = identity.
-__global__ __launch_bounds__(256) void k_nj_init(double *__restrict__ D, uint32_t n, int32_t *__restrict__ act,
-												 int32_t *__restrict__ id, unsigned long long *bad) {
+// goes to the replicate's bad word as i * n + j.  act = id = identity.
+__global__ __launch_bounds__(256) void k_nj_init(double *__restrict__ D, uint32_t n, int32_t *__restrict__ lists,
+												 unsigned long long *bad) {
+	const size_t rep = blockIdx.y;
+	D += rep * n * n, bad += rep;
+	int32_t *act = lists + rep * 3 * n, *id = act + 2 * (size_t)n;
 	const uint32_t i = blockIdx.x;
 	double *row = D + (size_t)i * n;
 	unsigned long long first = ~0ull;
@@ -99,8 +110,11 @@ __device__ inline double lane_value(double v, int l) {
 	return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
-__global__ __launch_bounds__(256) void k_nj_rowsum(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ act,
-												   uint32_t r, double *__restrict__ R) {
+__global__ __launch_bounds__(256) void k_nj_rowsum(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ lists,
+												   uint32_t cur, uint32_t r, double *__restrict__ R) {
+	const size_t rep = blockIdx.y;
+	D += rep * n * n, R += rep * n;
+	const int32_t *act = lists + rep * 3 * n + cur;
 	const uint32_t x = blockIdx.x * 4 + (threadIdx.x >> 6);
 	const int lane = threadIdx.x & 63;
 	if (x >= r) return;
@@ -131,9 +145,11 @@ __global__ __launch_bounds__(256) void k_nj_rowsum(const double *__restrict__ D,
 // Block b = tile (tp, tq), tp <= tq, of the active pairs in list positions: wave w takes rows tp*64 + 16w .. +15, lane l
 // column tq*64 + l.  Q = ((r-2) * D[x][y] - R_x) - R_y with x the member of smaller id.
 __global__ __launch_bounds__(256) void k_nj_argmin(const double *__restrict__ D, uint32_t n,
-												   const int32_t *__restrict__ act, uint32_t r,
-												   const int32_t *__restrict__ id, const double *__restrict__ R,
-												   Cand *__restrict__ part) {
+												   const int32_t *__restrict__ lists, uint32_t cur, uint32_t r,
+												   const double *__restrict__ R, Cand *__restrict__ part, uint32_t part_stride) {
+	const size_t rep = blockIdx.y;
+	D += rep * n * n, R += rep * n, part += rep * part_stride;
+	const int32_t *act = lists + rep * 3 * n + cur, *id = lists + rep * 3 * n + 2 * (size_t)n;
 	const uint64_t b = blockIdx.x;
 	uint32_t tq = (uint32_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
 	while ((uint64_t)tq * (tq + 1) / 2 > b) --tq;
@@ -169,12 +185,15 @@ __global__ __launch_bounds__(256) void k_nj_argmin(const double *__restrict__ D,
 }
 
 // One block: the least of nparts tile results, its record, node u = n + step in the lower slot, the other slot retired
-// (act_in -> act_out, order kept).
-__global__ __launch_bounds__(JOIN_THREADS) void k_nj_join(double *__restrict__ D, uint32_t n,
-														  const int32_t *__restrict__ act_in, int32_t *__restrict__ act_out,
-														  uint32_t r, int32_t *__restrict__ id, const double *__restrict__ R,
-														  const Cand *__restrict__ part, uint32_t nparts,
-														  andi_hip_nj_join *__restrict__ rec, uint32_t step) {
+// (the list at cur -> the other list, order kept).
+__global__ __launch_bounds__(JOIN_THREADS) void k_nj_join(double *__restrict__ D, uint32_t n, int32_t *__restrict__ lists,
+														  uint32_t cur, uint32_t r, const double *__restrict__ R,
+														  const Cand *__restrict__ part, uint32_t part_stride, uint32_t nparts,
+														  andi_hip_nj_join *__restrict__ rec, uint32_t nrec, uint32_t step) {
+	const size_t rep = blockIdx.y;
+	D += rep * n * n, R += rep * n, part += rep * part_stride, rec += rep * nrec;
+	const int32_t *act_in = lists + rep * 3 * n + cur;
+	int32_t *act_out = lists + rep * 3 * n + (n - cur), *id = lists + rep * 3 * n + 2 * (size_t)n;
 	Cand best = none();
 	for (uint32_t k = threadIdx.x; k < nparts; k += blockDim.x)
 		if (better(part[k], best)) best = part[k];
@@ -205,9 +224,12 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_nj_join(double *__restrict__ D
 }
 
 // The last record: the three remaining nodes x < y < z by id (r = 3), or the two leaves of n = 2.
-__global__ void k_nj_final(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ act, uint32_t r,
-						   const int32_t *__restrict__ id, andi_hip_nj_join *__restrict__ rec) {
+__global__ void k_nj_final(const double *__restrict__ D, uint32_t n, const int32_t *__restrict__ lists, uint32_t cur,
+						   uint32_t r, andi_hip_nj_join *__restrict__ rec, uint32_t nrec) {
 	if (threadIdx.x != 0) return;
+	const size_t rep = blockIdx.y;
+	D += rep * n * n, rec += rep * nrec + (nrec - 1);
+	const int32_t *act = lists + rep * 3 * n + cur, *id = lists + rep * 3 * n + 2 * (size_t)n;
 	andi_hip_nj_join j;
 	j.pad = 0;
 	if (r == 2) {
@@ -236,6 +258,88 @@ uint64_t tiles_of(uint32_t r) {
 	return t * (t + 1) / 2;
 }
 
+constexpr unsigned long long NOT_BAD = ~0ull;
+constexpr size_t MAX_GROUP = 65535;             // a grid's second dimension
+constexpr size_t GROUP_BYTES = (size_t)4 << 30; // andi_hip_nj_batch: device memory of a group of replicates, at most (one always fits)
+
+// device bytes of one replicate: D, R, the lists, the tile results, the records, the bad word
+size_t replicate_bytes(size_t n) {
+	const size_t nrec = n == 2 ? 1 : n - 2;
+	return n * n * sizeof(double) + n * sizeof(double) + 3 * n * sizeof(int32_t) + tiles_of((uint32_t)n) * sizeof(Cand) +
+		   nrec * sizeof(andi_hip_nj_join) + sizeof(unsigned long long);
+}
+
+// the buffers of a group of g replicates of n x n, one replicate after the other in each
+struct NjBuffers {
+	double *D = nullptr, *R = nullptr;
+	int32_t *lists = nullptr; // per replicate: two act lists, the ids
+	Cand *part = nullptr;
+	andi_hip_nj_join *rec = nullptr;
+	unsigned long long *bad = nullptr;
+};
+
+// (the caller has waited for the stream)
+void nj_free(NjBuffers &b) {
+	for (void *p : {(void *)b.D, (void *)b.R, (void *)b.lists, (void *)b.part, (void *)b.rec, (void *)b.bad})
+		if (p) (void)andi_arena::dev_free(p, false);
+	b = NjBuffers{};
+}
+
+hipError_t nj_alloc(NjBuffers &b, size_t n, size_t g) {
+	const size_t nrec = n == 2 ? 1 : n - 2;
+	hipError_t e = dmalloc(&b.D, g * n * n);
+	if (e == hipSuccess) e = dmalloc(&b.R, g * n);
+	if (e == hipSuccess) e = dmalloc(&b.lists, g * 3 * n);
+	if (e == hipSuccess) e = dmalloc(&b.part, g * tiles_of((uint32_t)n));
+	if (e == hipSuccess) e = dmalloc(&b.rec, g * nrec);
+	if (e == hipSuccess) e = dmalloc(&b.bad, g);
+	return e;
+}
+
+// Neighbor-joining of g matrices (host, one after the other) in buffers for at least g: bad[k] receives replicate k's
+// first non-finite entry (i * n + j) or NOT_BAD, joins the records of all g when at least one matrix is usable -- and
+// nothing when none is.  A bad replicate among good ones is NOT kept out of the step kernels: better() and none() make
+// every pick a real pair of active slots whatever the values in D are (every index comes from the lists and the ids,
+// never from a distance), so its steps run like any other's on NaN and inf, fault nothing, and leave records the caller
+// throws away (andi_hip_nj_batch zeroes them).  Synchronous; the one host synchronisation before the steps is the read of
+// the bad words, none between steps.
+hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint32_t N, uint32_t g, andi_hip_nj_join *joins,
+					unsigned long long *bad) {
+	const size_t n = N, nrec = n == 2 ? 1 : n - 2;
+	const uint32_t parts = (uint32_t)tiles_of(N);
+	hipStream_t st = ctx->stream;
+	hipError_t e = hipMemcpyAsync(b.D, D, g * n * n * sizeof(double), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemsetAsync(b.bad, 0xff, g * sizeof *bad, st);
+	if (e == hipSuccess) {
+		k_nj_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.bad);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(bad, b.bad, g * sizeof *bad, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e != hipSuccess) return e;
+	bool any_good = false;
+	for (uint32_t k = 0; k < g; ++k) any_good |= bad[k] == NOT_BAD;
+	if (!any_good) return hipSuccess;
+	uint32_t cur = 0; // where in a replicate's lists the current act list starts: 0 or n
+	for (uint32_t s = 0; e == hipSuccess && n >= 4 && s < N - 3; ++s) {
+		const uint32_t r = N - s;
+		const uint64_t nb = tiles_of(r);
+		k_nj_rowsum<<<dim3((r + 3) / 4, g), 256, 0, st>>>(b.D, N, b.lists, cur, r, b.R);
+		k_nj_argmin<<<dim3((unsigned)nb, g), 256, 0, st>>>(b.D, N, b.lists, cur, r, b.R, b.part, parts);
+		k_nj_join<<<dim3(1, g), JOIN_THREADS, 0, st>>>(b.D, N, b.lists, cur, r, b.R, b.part, parts, (uint32_t)nb, b.rec,
+														(uint32_t)nrec, s);
+		e = hipGetLastError();
+		cur = N - cur;
+	}
+	if (e == hipSuccess) {
+		k_nj_final<<<dim3(1, g), 64, 0, st>>>(b.D, N, b.lists, cur, n == 2 ? 2 : 3, b.rec, (uint32_t)nrec);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(joins, b.rec, g * nrec * sizeof *joins, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	return e;
+}
+
 } // namespace
 
 int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *joins) {
@@ -244,55 +348,58 @@ int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const uint32_t N = (uint32_t)n;
-	const size_t nrec = n == 2 ? 1 : n - 2;
-	double *dD = nullptr, *dR = nullptr;
-	int32_t *dact = nullptr, *did = nullptr;
-	Cand *dpart = nullptr;
-	andi_hip_nj_join *drec = nullptr;
-	unsigned long long *dbad = nullptr, bad = ~0ull;
-	hipError_t e = dmalloc(&dD, n * n);
-	if (e == hipSuccess) e = dmalloc(&dR, n);
-	if (e == hipSuccess) e = dmalloc(&dact, 3 * n); // two lists, the ids
-	if (e == hipSuccess) e = dmalloc(&dpart, tiles_of(N));
-	if (e == hipSuccess) e = dmalloc(&drec, nrec);
-	if (e == hipSuccess) e = dmalloc(&dbad, 1);
-	if (e == hipSuccess) did = dact + 2 * n;
-	hipStream_t st = ctx->stream;
-	if (e == hipSuccess) e = hipMemcpyAsync(dD, D, n * n * sizeof(double), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) e = hipMemsetAsync(dbad, 0xff, sizeof bad, st);
-	if (e == hipSuccess) {
-		k_nj_init<<<N, 256, 0, st>>>(dD, N, dact, did, dbad);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(&bad, dbad, sizeof bad, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e == hipSuccess && bad != ~0ull) {
+	NjBuffers b;
+	unsigned long long bad = NOT_BAD;
+	hipError_t e = nj_alloc(b, n, 1);
+	if (e == hipSuccess) e = nj_group(ctx, b, D, (uint32_t)n, 1, joins, &bad);
+	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
+	nj_free(b);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_nj", e);
+	if (bad != NOT_BAD) {
 		const size_t i = (size_t)(bad / n), j = (size_t)(bad % n);
 		char msg[160];
 		snprintf(msg, sizeof msg, "andi_hip_nj: D[%zu][%zu] is not finite (%g)", i, j, D[i * n + j]);
 		ctx->err = msg;
+		return 1;
 	}
-	int32_t *act = dact, *act2 = dact + n;
-	for (uint32_t s = 0; e == hipSuccess && bad == ~0ull && n >= 4 && s < N - 3; ++s) {
-		const uint32_t r = N - s;
-		const uint64_t nb = tiles_of(r);
-		k_nj_rowsum<<<(r + 3) / 4, 256, 0, st>>>(dD, N, act, r, dR);
-		k_nj_argmin<<<(unsigned)nb, 256, 0, st>>>(dD, N, act, r, did, dR, dpart);
-		k_nj_join<<<1, JOIN_THREADS, 0, st>>>(dD, N, act, act2, r, did, dR, dpart, (uint32_t)nb, drec, s);
-		e = hipGetLastError();
-		int32_t *t = act;
-		act = act2, act2 = t;
+	return 0;
+}
+
+int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, andi_hip_nj_join *joins, int64_t *bad) {
+	if (!ctx || !D || !joins || !bad || count == 0 || n < 2 || n > 65535) {
+		if (ctx) ctx->err = "andi_hip_nj_batch: bad arguments (ctx, D, joins and bad must be given, count >= 1, 2 <= n <= 65535)";
+		return 1;
 	}
-	if (e == hipSuccess && bad == ~0ull) {
-		k_nj_final<<<1, 64, 0, st>>>(dD, N, act, n == 2 ? 2 : 3, did, drec + (nrec - 1));
-		e = hipGetLastError();
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t nrec = n == 2 ? 1 : n - 2;
+	// the group: as many replicates as GROUP_BYTES hold (at least one), as a grid's second dimension takes, as there are
+	size_t G = GROUP_BYTES / replicate_bytes(n);
+	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
+	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing
+		const long long f = atoll(v);
+		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
 	}
-	if (e == hipSuccess && bad == ~0ull) e = hipMemcpyAsync(joins, drec, nrec * sizeof *drec, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
-	for (void *p : {(void *)dD, (void *)dR, (void *)dact, (void *)dpart, (void *)drec, (void *)dbad})
-		(void)andi_arena::dev_free(p, false);
-	if (e != hipSuccess) return fail(ctx, "andi_hip_nj", e);
-	return bad == ~0ull ? 0 : 1;
+	if (G > count) G = count;
+	NjBuffers b;
+	hipError_t e = nj_alloc(b, n, G);
+	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix andi_hip_nj needs too
+		nj_free(b);
+		(void)hipGetLastError();
+		G = (G + 1) / 2;
+		e = nj_alloc(b, n, G);
+	}
+	std::vector<unsigned long long> hb(G);
+	for (size_t first = 0; e == hipSuccess && first < count; first += G) {
+		const size_t g = count - first < G ? count - first : G;
+		andi_hip_nj_join *J = joins + first * nrec;
+		e = nj_group(ctx, b, D + first * n * n, (uint32_t)n, (uint32_t)g, J, hb.data());
+		for (size_t k = 0; e == hipSuccess && k < g; ++k) {
+			bad[first + k] = hb[k] == NOT_BAD ? -1 : (int64_t)hb[k];
+			if (hb[k] != NOT_BAD) memset(J + k * nrec, 0, nrec * sizeof *J);
+		}
+	}
+	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
+	nj_free(b);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_nj_batch", e);
+	return 0;
 }

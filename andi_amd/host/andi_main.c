@@ -367,6 +367,8 @@ static void usage(int status) {
 		"  -t, --threads=INT    Set the number of host threads; by default, all processors are used\n"
 		"      --tree=FILE      Write a neighbor-joining tree of each printed matrix to FILE (Newick, one line per\n"
 		"                       matrix)\n"
+		"      --support=FILE   With -b: write the tree of the first matrix to FILE, each inner branch labelled with the\n"
+		"                       number of bootstrap matrices whose tree has that branch\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -453,6 +455,21 @@ typedef struct {
 	int failed;        /* it could not be created: said once */
 } tree_out;
 
+/* one Newick line of the records J (with the support values as inner labels, if given) to f */
+static void put_tree(FILE *f, const char *path, const andi_hip_nj_join *J, const uint32_t *support, const genome *g, size_t n,
+					 int truncate) {
+	const char **names = xmalloc(n * sizeof *names);
+	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
+	size_t cap = 64 + n * 52;
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	const size_t need = andi_hip_format_newick_support(J, support, n, names, truncate, text, cap);
+	if (need >= cap)
+		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_support(J, support, n, names, truncate, text, cap);
+	if (fputs(text, f) == EOF) err(1, "%s", path);
+	free(text), free(names);
+}
+
 static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, size_t n, int model, int truncate, int k) {
 	if (t->failed) return;
 	char msg[512];
@@ -476,15 +493,70 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, si
 		free(D), free(J);
 		return;
 	}
-	const char **names = xmalloc(n * sizeof *names);
-	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
-	size_t cap = 64 + n * 40;
-	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
-	char *text = xmalloc(cap);
-	const size_t need = andi_hip_format_newick(J, n, names, truncate, text, cap);
-	if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick(J, n, names, truncate, text, cap);
-	if (fputs(text, t->f) == EOF) err(1, "%s", t->path);
-	free(text), free(names), free(D), free(J);
+	put_tree(t->f, t->path, J, NULL, g, n, truncate);
+	free(D), free(J);
+}
+
+/* --support: the tree of the point estimate with, on every inner branch, the number of bootstrap matrices whose tree has
+ * that branch.  The replicates' trees come from andi_hip_nj_batch, in chunks that bound the host's doubles; the counts
+ * of the chunks add up.  With --tree, the replicates' lines of that file are written from the same records (bit for bit
+ * those of andi_hip_nj, so the same text), in the same order. */
+static void write_support(FILE *f, const char *path, tree_out *t, andi_hip_ctx *ctx, const andi_hip_model *M,
+						  const andi_hip_model *B, unsigned long replicates, const genome *g, size_t n, int model, int truncate) {
+	const size_t nrec = n == 2 ? 1 : n - 2, nsup = n > 3 ? n - 3 : 1;
+	size_t chunk = ((size_t)1 << 30) / (n * n * sizeof(double)); /* at most 1 GiB of doubles at a time */
+	chunk = chunk < 1 ? 1 : chunk > replicates ? replicates : chunk;
+	double *D = malloc(chunk * n * n * sizeof *D);
+	andi_hip_nj_join *J = malloc(nrec * sizeof *J), *R = malloc(chunk * nrec * sizeof *R);
+	int64_t *bad = malloc(chunk * sizeof *bad);
+	uint8_t *skip = malloc(chunk);
+	uint32_t *total = calloc(nsup, sizeof *total), *part = calloc(nsup, sizeof *part);
+	if (!D || !J || !R || !bad || !skip || !total || !part || andi_hip_distances(M, n, model, D))
+		err(errno, "Could not allocate enough memory for the support values.");
+	int point_ok = 1;
+	for (size_t i = 0; i < n && point_ok; i++)
+		for (size_t j = i + 1; j < n; j++)
+			if (!isfinite(D[i * n + j])) {
+				soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
+				point_ok = 0;
+				break;
+			}
+	if (point_ok && andi_hip_nj(ctx, D, n, J)) {
+		soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+		point_ok = 0;
+	}
+	unsigned long counted = 0;
+	for (unsigned long first = 0; first < replicates; first += chunk) {
+		const size_t c = replicates - first < chunk ? replicates - first : chunk;
+		for (size_t k = 0; k < c; k++)
+			if (andi_hip_distances(B + (first + k) * n * n, n, model, D + k * n * n))
+				err(errno, "Could not allocate enough memory for the support values.");
+		if (andi_hip_nj_batch(ctx, D, n, c, R, bad)) {
+			soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+			point_ok = 0;
+			break;
+		}
+		for (size_t k = 0; k < c; k++) {
+			skip[k] = bad[k] >= 0;
+			if (skip[k])
+				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s' is not finite.", first + (unsigned long)k + 2,
+						   g[bad[k] / (int64_t)n].name, g[bad[k] % (int64_t)n].name);
+			else if (t->f) put_tree(t->f, t->path, R + k * nrec, NULL, g, n, truncate);
+			counted += !skip[k];
+		}
+		if (!point_ok) continue; /* (the replicates' lines of --tree are still written) */
+		if (andi_hip_nj_support(ctx, J, R, n, c, skip, part)) {
+			soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+			point_ok = 0;
+			continue;
+		}
+		for (size_t s = 0; s + 3 < n; s++) total[s] += part[s];
+	}
+	if (point_ok) {
+		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
+		put_tree(f, path, J, total, g, n, truncate);
+	}
+	free(D), free(J), free(R), free(bad), free(skip), free(total), free(part);
 }
 
 /* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
@@ -561,6 +633,7 @@ int main(int argc, char *argv[]) {
 												 {"reference", required_argument, NULL, 0},
 												 {"reference-list", required_argument, NULL, 0},
 												 {"tree", required_argument, NULL, 0},
+												 {"support", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -589,6 +662,8 @@ int main(int argc, char *argv[]) {
 	size_t nref_files = 0, ref_cap = 0;
 	int rect = 0, bootstrap_given = 0;
 	tree_out tree = {0};
+	const char *support_path = NULL; /* --support */
+	FILE *support_f = NULL;
 
 	for (;;) {
 		int idx = 0;
@@ -601,6 +676,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "truncate-names")) truncate = 1;
 				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files, &nfiles, &files_cap);
 				if (!strcmp(o, "tree")) tree.path = optarg;
+				if (!strcmp(o, "support")) support_path = optarg;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
 				if (!strcmp(o, "reference")) {
 					rect = 1;
@@ -688,7 +764,10 @@ int main(int argc, char *argv[]) {
 	}
 	if (rect && bootstrap_given) errx(1, "Bootstrapping (-b) is not available together with --reference or --reference-list.");
 	if (rect && tree.path) errx(1, "A tree (--tree) is not available together with --reference or --reference-list.");
+	if (rect && support_path) errx(1, "Support values (--support) are not available together with --reference or --reference-list.");
+	if (support_path && !bootstrap) errx(1, "Support values (--support) need bootstrap matrices: give -b N with N of at least 2.");
 	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
+	if (support_path && !(support_f = fopen(support_path, "w"))) err(1, "%s", support_path);
 	tree.device_for_ctx = opts.device;
 	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
@@ -775,14 +854,16 @@ int main(int argc, char *argv[]) {
 		} else {
 			for (unsigned long b = 0; b < bootstrap; b++) {
 				print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
-				if (tree.f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
+				if (tree.f && !support_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
 			}
+			if (support_f) write_support(support_f, support_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model, truncate);
 		}
 		if (ctx) andi_hip_ctx_destroy(ctx);
 		free(B);
 	}
 	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
 	if (tree.f && fclose(tree.f)) err(1, "%s", tree.path);
+	if (support_f && fclose(support_f)) err(1, "%s", support_path);
 	free(M);
 	free(in);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;

@@ -109,7 +109,10 @@ SYMBOLS = {
                                                     C.c_size_t, C.POINTER(C.c_int)]),
     "andi_hip_distances": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "andi_hip_format_newick": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_format_newick_support": (C.c_size_t, [_P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
     "andi_hip_nj": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "andi_hip_nj_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
+    "andi_hip_nj_support": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -286,15 +289,24 @@ def distances(M, model=M_JC):
     return D
 
 
-def newick(joins, names, truncate_names=False):
-    """The Newick line (ending in ";\n") of nj's records for the leaves `names`."""
+def newick(joins, names, truncate_names=False, support=None):
+    """The Newick line (ending in ";\n") of nj's records for the leaves `names`; with support (nj_support's counts, one
+    per pair record) each count is the label of its internal node."""
     J = np.ascontiguousarray(joins, dtype=NJ_JOIN)
     n = len(names)
     cn = _names(names)
     cap = 64 + 40 * n + sum(len(x) for x in names)
+    if support is not None:
+        support = np.ascontiguousarray(support, dtype=np.uint32)
+        assert len(support) >= max(n - 3, 0)
+        cap += 10 * n
     for _ in range(2):  # (the call returns the bytes it needs)
         out = C.create_string_buffer(cap)
-        need = load().andi_hip_format_newick(J.ctypes.data, n, cn, int(truncate_names), C.cast(out, _P), cap)
+        if support is None:
+            need = load().andi_hip_format_newick(J.ctypes.data, n, cn, int(truncate_names), C.cast(out, _P), cap)
+        else:
+            need = load().andi_hip_format_newick_support(J.ctypes.data, support.ctypes.data, n, cn, int(truncate_names),
+                                                         C.cast(out, _P), cap)
         if need < cap:
             break
         cap = need + 1
@@ -589,6 +601,37 @@ def nj(ctx: Context, D):
     J = np.zeros(1 if n == 2 else max(n - 2, 0), NJ_JOIN)
     ctx._check(load().andi_hip_nj(ctx._h, D.ctypes.data, n, J.ctypes.data), "nj")
     return J
+
+
+def nj_batch(ctx: Context, Ds):
+    """Neighbor-joining of the (count, n, n) distances Ds in shared launches (andi_hip_nj_batch): (J, bad) -- J[k] the
+    records nj(ctx, Ds[k]) gives, bit for bit, as a (count, nrec) array of dtype NJ_JOIN; bad[k] = -1, or i * n + j of
+    matrix k's first non-finite entry, and then J[k] is all zero."""
+    Ds = np.ascontiguousarray(Ds, dtype=np.float64)
+    assert Ds.ndim == 3 and Ds.shape[1] == Ds.shape[2]
+    count, n = Ds.shape[0], Ds.shape[1]
+    J = np.zeros((count, 1 if n == 2 else max(n - 2, 0)), NJ_JOIN)
+    bad = np.zeros(count, np.int64)
+    ctx._check(load().andi_hip_nj_batch(ctx._h, Ds.ctypes.data, n, count, J.ctypes.data, bad.ctypes.data), "nj_batch")
+    return J, bad
+
+
+def nj_support(ctx: Context, J, reps, skip=None):
+    """Bootstrap support (andi_hip_nj_support): for every pair record of the tree J (n - 2 records) the number of the
+    replicate trees reps (count, n - 2), but those with skip[k] set, that hold the same bipartition of the leaves:
+    uint32[n - 3]."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    reps = np.ascontiguousarray(reps, dtype=NJ_JOIN)
+    n = len(J) + 2
+    assert reps.ndim == 2 and reps.shape[1] == len(J)
+    if skip is not None:
+        skip = np.ascontiguousarray(skip, dtype=np.uint8)
+        assert skip.shape == (reps.shape[0],)
+    support = np.zeros(max(n - 3, 0), np.uint32)
+    ctx._check(load().andi_hip_nj_support(ctx._h, J.ctypes.data, reps.ctypes.data, n, reps.shape[0],
+                                          skip.ctypes.data if skip is not None else None, support.ctypes.data),
+               "nj_support")
+    return support
 
 
 def _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host, progress=None):

@@ -16,7 +16,8 @@
  * ABI 5 also gained, without changing anything that was there, the query-versus-
  * reference mode: andi_hip_dist_rect, andi_hip_queries_view and
  * andi_hip_format_distances_rect (additions only; the version stays 5); and the tree the matrix feeds:
- * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well).
+ * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well); and bootstrap support on that
+ * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -189,6 +190,12 @@ typedef struct {
  * record's node) give 0 and an empty string. */
 size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
 							  char *out, size_t cap);
+/* The same text with support values as internal node labels: the decimal support[s] directly behind the ")" that closes
+ * pair record s, 0 <= s < n - 3 -- "(A:0.1,B:0.2)87:0.05".  The number is the COUNT andi_hip_nj_support gives, not a
+ * percentage; the final record gets no label.  support == NULL gives exactly the bytes of the function above (both are
+ * one walk).  Return value, cap and the rule for malformed records as above. */
+size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
+									  const char *const *names, int truncate_names, char *out, size_t cap);
 
 /* ------------------------------------------------------------------ */
 /* Device-resident objects                                             */
@@ -307,6 +314,29 @@ int andi_hip_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uin
  *  - n = 2: {0, 1, -1, 0, D[0][1]*0.5, D[0][1]*0.5, 0.0};
  *  - negative branch lengths are kept as computed. */
 int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *joins);
+/* Neighbor-joining of `count` matrices of one n in shared launches: D is count row-major n x n matrices one after the
+ * other (host memory, upper triangles read), joins receives count * nrec records, nrec = n - 2 (1 for n = 2), matrix k's
+ * from joins + k * nrec on -- bit for bit what the call above writes for D + k*n*n (the same kernels, the replicate as
+ * the grid's second dimension; a step of all matrices is the three launches a step of one is).  bad[k] = -1 for a usable
+ * matrix; else i*n + j of its first non-finite D[i][j] (i < j, row-major order), its nrec records are all-zero bytes, and
+ * the other matrices are not affected.  Returns 0 when it ran, bad matrices or not; 1 through the context's error on a
+ * HIP error; 1 before any HIP call on bad arguments (a NULL pointer, count == 0, n outside 2 ... 65535).  When
+ * count * n * n * 8 bytes do not fit the device (or count > 65535) the matrices are taken in groups; the results do not
+ * depend on the grouping, and the call does not fail on size while one matrix fits.  Synchronous. */
+int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, andi_hip_nj_join *joins, int64_t *bad);
+/* Bootstrap support of the branches of `tree` (n - 2 records) among the `count` replicate trees `reps` (count * (n - 2)
+ * records, replicate k's from reps + k*(n - 2) on).  Pair record s of a tree, 0 <= s < n - 3, defines the bipartition
+ * {L, leaves \ L} with L the leaves below node n + s; an unrooted binary tree has exactly these n - 3 non-trivial
+ * bipartitions.  support[s] = the number of replicates k with !skip || !skip[k] whose tree has the same bipartition as an
+ * UNORDERED pair of sets: trees of one unrooted topology joined in another order, or with another final three, agree on
+ * every branch.  The count is exact (a hash of the leaf set only pre-filters; a match is confirmed on the sets).  n < 4:
+ * nothing is written, returns 0.  The records are validated on the host before any HIP call, in O(n * count): the ids
+ * must be those andi_hip_nj gives -- every child a leaf or an earlier record's node (andi_hip_format_newick's rule) and
+ * every node a child exactly once; a skipped replicate's records are not looked at (skip may be NULL).  Bad arguments (a
+ * NULL ctx, tree, reps or support, count == 0, n outside 2 ... 65535) and bad records return 1 through the context's
+ * error.  Not recursive: any depth works; the replicates' leaf sets are built in groups that fit the device.  Synchronous. */
+int andi_hip_nj_support(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
+						size_t count, const uint8_t *skip, uint32_t *support);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
