@@ -6,5 +6,6 @@ benchmark.
 """
 from . import lib, synth  # noqa: F401
 from .lib import (AndiHipError, Context, bootstrap, Esa, Queries, M_ANI, M_JC, M_KIMURA, M_LOGDET, M_RAW,  # noqa: F401
-                  dist_matrix, dist_rect, distances, estimate, format_distances, format_distances_rect,
-                  match_positions, newick, nj, nj_batch, nj_support, scan_rows, subject_prepare, suffix_array)
+                  consensus, dist_matrix, dist_rect, distances, estimate, format_distances, format_distances_rect,
+                  match_positions, newick, newick_consensus, nj, nj_batch, nj_splits, nj_support,
+                  scan_rows, subject_prepare, suffix_array)

@@ -434,3 +434,179 @@ size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *c
 							  char *out, size_t cap) {
 	return andi_hip_format_newick_support(J, NULL, n, names, truncate_names, out, cap);
 }
+
+/* ------------------------------------------------------------------ */
+/* The majority-rule consensus tree of a bootstrap (include/andi_hip.h) */
+/* ------------------------------------------------------------------ */
+#define NO_SPLIT 0xffffffffu
+
+static uint32_t uf_find(uint32_t *uf, uint32_t x) { /* (path halving) */
+	while (uf[x] != x) x = uf[x] = uf[uf[x]];
+	return x;
+}
+
+static int cmp_u64(const void *a, const void *b) {
+	const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+	return x < y ? -1 : x > y;
+}
+
+int andi_hip_consensus(const andi_hip_nj_join *reps, size_t n, size_t count, const uint8_t *skip, const uint32_t *ids,
+					   size_t nsplits, const uint32_t *freq, const uint64_t *sets, andi_hip_cons_node *nodes, size_t *ninner) {
+	if (!reps || !nodes || !ninner || count == 0 || n < 2 || n > 65535) return 1;
+	const size_t S = n > 3 ? n - 3 : 0, nrec = n == 2 ? 1 : n - 2, W = (n + 63) / 64;
+	if (S && (!ids || !freq || !sets || nsplits == 0)) return 1;
+	size_t used = 0, m = 0;
+	for (size_t k = 0; k < count; k++) used += !skip || !skip[k];
+	if (used == 0) return 1;
+	if (!S) nsplits = 0;
+
+	/* the splits that enter: node_of[id] = the inner node of split id (0 ... m-1), or NO_SPLIT */
+	int rc = 1;
+	uint32_t *node_of = malloc((nsplits ? nsplits : 1) * sizeof *node_of);
+	uint32_t *split_of = malloc((S ? S : 1) * sizeof *split_of), *occ = calloc(S ? S : 1, sizeof *occ);
+	double *isum = calloc(S ? S : 1, sizeof *isum), *lsum = calloc(n, sizeof *lsum), *above = malloc((n + S) * sizeof *above);
+	uint8_t *seen = malloc(n + S);
+	uint64_t *order = malloc((S ? S : 1) * sizeof *order);
+	uint32_t *uf = malloc(4 * n * sizeof *uf); /* the leaves' components: union-find, sizes, marks, the node on top */
+	uint32_t *roots = malloc(n * sizeof *roots); /* the components of one set */
+	if (!node_of || !split_of || !occ || !isum || !lsum || !above || !seen || !order || !uf || !roots) goto done;
+	for (size_t id = 0; id < nsplits; id++) {
+		node_of[id] = NO_SPLIT;
+		if (2 * (uint64_t)freq[id] <= used) continue;
+		if (m == S) goto done; /* (more than n - 3 majority splits: they cannot all be compatible) */
+		split_of[m] = (uint32_t)id, node_of[id] = (uint32_t)m++;
+	}
+
+	/* the sums of the branch lengths, replicates in ascending order */
+	for (size_t k = 0; k < count; k++) {
+		if (skip && skip[k]) continue;
+		const andi_hip_nj_join *R = reps + k * nrec;
+		memset(seen, 0, n + S);
+		for (size_t t = 0; t < nrec; t++) {
+			const int32_t ch[3] = {R[t].a, R[t].b, R[t].c};
+			const double len[3] = {R[t].la, R[t].lb, R[t].lc};
+			const int nk = t + 1 == nrec && n > 2 ? 3 : 2;
+			for (int c = 0; c < nk; c++) {
+				if (ch[c] < 0 || (size_t)ch[c] >= n + S || seen[ch[c]]) goto done;
+				seen[ch[c]] = 1, above[ch[c]] = len[c];
+			}
+		} /* (n + S children, none twice: every node but the last record's has its branch) */
+		for (size_t i = 0; i < n; i++) lsum[i] += above[i];
+		for (size_t s = 0; s < S; s++) {
+			const uint32_t id = ids[k * S + s];
+			if (id >= nsplits) goto done; /* (NO_SPLIT in a used replicate included) */
+			const uint32_t j = node_of[id];
+			if (j != NO_SPLIT) isum[j] += above[n + s], occ[j]++;
+		}
+	}
+
+	/* parents: the majority sets in ascending size; each must be a union of whole components of the leaves so far (a
+	 * laminar family), whose top nodes become its children and which it then merges */
+	uint32_t *csize = uf + n, *mark = uf + 2 * n, *top = uf + 3 * n;
+	for (size_t i = 0; i < n; i++) uf[i] = top[i] = (uint32_t)i, csize[i] = 1, mark[i] = 0;
+	for (size_t j = 0; j < m; j++) {
+		const uint64_t *X = sets + (size_t)split_of[j] * W;
+		size_t size = 0;
+		for (size_t w = 0; w < W; w++) size += (size_t)__builtin_popcountll(X[w]);
+		const uint64_t valid = n & 63 ? (1ull << (n & 63)) - 1 : ~0ull;
+		if (occ[j] != freq[split_of[j]] || (X[0] & 1) || (X[W - 1] & ~valid) || size < 2 || size > n - 2) goto done;
+		order[j] = (uint64_t)size << 32 | j;
+	}
+	qsort(order, m, sizeof *order, cmp_u64);
+	for (size_t o = 0; o < m; o++) {
+		const uint32_t j = (uint32_t)order[o];
+		const size_t size = (size_t)(order[o] >> 32);
+		const uint64_t *X = sets + (size_t)split_of[j] * W;
+		size_t nroots = 0, total = 0;
+		for (size_t w = 0; w < W; w++)
+			for (uint64_t bits = X[w]; bits; bits &= bits - 1) {
+				const uint32_t r = uf_find(uf, (uint32_t)(w * 64 + (size_t)__builtin_ctzll(bits)));
+				if (mark[r] == o + 1) continue;
+				mark[r] = (uint32_t)o + 1, roots[nroots++] = r, total += csize[r];
+			}
+		if (total != size) goto done; /* a component reaches out of the set: not laminar */
+		uint32_t big = roots[0];
+		for (size_t q = 1; q < nroots; q++)
+			if (csize[roots[q]] > csize[big]) big = roots[q];
+		for (size_t q = 0; q < nroots; q++) {
+			nodes[top[roots[q]]].parent = (int32_t)(n + j);
+			if (roots[q] != big) uf[roots[q]] = big;
+		}
+		csize[big] = (uint32_t)size, top[big] = (uint32_t)(n + j), mark[big] = (uint32_t)o + 1;
+	}
+	for (size_t i = 0; i < n; i++) nodes[top[uf_find(uf, (uint32_t)i)]].parent = (int32_t)(n + m);
+	for (size_t i = 0; i < n; i++) nodes[i].support = (uint32_t)used, nodes[i].length = lsum[i] / (double)used;
+	for (size_t j = 0; j < m; j++)
+		nodes[n + j].support = freq[split_of[j]], nodes[n + j].length = isum[j] / (double)freq[split_of[j]];
+	nodes[n + m] = (andi_hip_cons_node){-1, (uint32_t)used, 0.0};
+	*ninner = m;
+	rc = 0;
+done:
+	free(node_of), free(split_of), free(occ), free(isum), free(lsum), free(above), free(seen), free(order), free(uf), free(roots);
+	return rc;
+}
+
+/* one walk over the consensus nodes from the root, depth first with a stack of its own; kids[first[v] .. first[v+1]) are
+ * v's children in the order of the text.  Returns the nodes it met; writes the text only with o. */
+static size_t cons_walk(const andi_hip_cons_node *nodes, size_t n, size_t root, const uint32_t *first, const uint32_t *kids,
+						uint32_t *stack, uint32_t *next, const char *const *names, int truncate, sink *o) {
+	size_t depth = 0, met = 1;
+	stack[depth++] = (uint32_t)root, next[root] = first[root];
+	if (o) put(o, "(");
+	while (depth) {
+		const uint32_t v = stack[depth - 1];
+		if (next[v] == first[v + 1]) {
+			depth--;
+			if (!o) continue;
+			if (depth) put(o, ")%u:%.8g", (unsigned)nodes[v].support, nodes[v].length);
+			else put(o, ");\n");
+			continue;
+		}
+		if (o && next[v] != first[v]) put(o, ",");
+		const uint32_t c = kids[next[v]++];
+		met++;
+		if (c < n) {
+			if (o) put_leaf(o, names[c], truncate), put(o, ":%.8g", nodes[c].length);
+		} else {
+			stack[depth++] = c, next[c] = first[c];
+			if (o) put(o, "(");
+		}
+	}
+	return met;
+}
+
+size_t andi_hip_format_newick_consensus(const andi_hip_cons_node *nodes, size_t n, size_t ninner,
+										const char *const *names, int truncate_names, char *out, size_t cap) {
+	sink o = {out, cap, 0};
+	if (out && cap) out[0] = '\0';
+	if (!nodes || !names || n < 2 || n > 65535 || ninner > n) return 0;
+	const size_t root = n + ninner, total = root + 1;
+	if (nodes[root].parent != -1) return 0;
+	uint32_t *first = calloc(total + 1, sizeof *first), *kids = malloc(total * sizeof *kids);
+	uint32_t *fill = malloc(total * sizeof *fill), *stack = malloc(total * sizeof *stack), *next = malloc(total * sizeof *next);
+	uint8_t *seen = calloc(total, 1);
+	size_t need = 0;
+	if (!first || !kids || !fill || !stack || !next || !seen) goto done;
+	for (size_t v = 0; v < root; v++) {
+		const int32_t p = nodes[v].parent;
+		if (p < (int32_t)n || (size_t)p > root) goto done; /* a parent is an inner node or the root */
+		first[p + 1]++;
+	}
+	for (size_t v = n; v < total; v++)
+		if (first[v + 1] < 2) goto done; /* an inner node (and the root) has two children at least */
+	for (size_t v = 0; v < total; v++) first[v + 1] += first[v], fill[v] = first[v];
+	/* the children of every node in ascending order of their least leaf: from leaf 0, 1, ... upwards, each node is entered
+	 * at its parent when the first leaf -- its least -- reaches it */
+	size_t entered = 0;
+	for (size_t l = 0; l < n; l++)
+		for (uint32_t v = (uint32_t)l; v != root && !seen[v]; v = (uint32_t)nodes[v].parent)
+			seen[v] = 1, kids[fill[nodes[v].parent]++] = v, entered++;
+	if (entered != root) goto done; /* an inner node without a leaf below it */
+	if (cons_walk(nodes, n, root, first, kids, stack, next, names, truncate_names, NULL) != total) goto done; /* a cycle */
+	cons_walk(nodes, n, root, first, kids, stack, next, names, truncate_names, &o);
+	need = o.len;
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
+done:
+	free(first), free(kids), free(fill), free(stack), free(next), free(seen);
+	return need;
+}

@@ -369,6 +369,8 @@ static void usage(int status) {
 		"                       matrix)\n"
 		"      --support=FILE   With -b: write the tree of the first matrix to FILE, each inner branch labelled with the\n"
 		"                       number of bootstrap matrices whose tree has that branch\n"
+		"      --consensus=FILE With -b: write the majority-rule consensus tree of the bootstrap matrices' trees to FILE,\n"
+		"                       each inner branch labelled with the number of those trees that have it\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -497,23 +499,43 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, si
 	free(D), free(J);
 }
 
-/* --support: the tree of the point estimate with, on every inner branch, the number of bootstrap matrices whose tree has
+/* the consensus tree's one Newick line to f */
+static void put_consensus(FILE *f, const char *path, const andi_hip_cons_node *nodes, size_t ninner, const genome *g, size_t n,
+						  int truncate) {
+	const char **names = xmalloc(n * sizeof *names);
+	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
+	size_t cap = 64 + n * 80;
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	const size_t need = andi_hip_format_newick_consensus(nodes, n, ninner, names, truncate, text, cap);
+	if (need >= cap)
+		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_consensus(nodes, n, ninner, names, truncate, text, cap);
+	if (fputs(text, f) == EOF) err(1, "%s", path);
+	free(text), free(names);
+}
+
+/* --support (f): the tree of the point estimate with, on every inner branch, the number of bootstrap matrices whose tree has
  * that branch.  The replicates' trees come from andi_hip_nj_batch, in chunks that bound the host's doubles; the counts
  * of the chunks add up.  With --tree, the replicates' lines of that file are written from the same records (bit for bit
- * those of andi_hip_nj, so the same text), in the same order. */
-static void write_support(FILE *f, const char *path, tree_out *t, andi_hip_ctx *ctx, const andi_hip_model *M,
-						  const andi_hip_model *B, unsigned long replicates, const genome *g, size_t n, int model, int truncate) {
+ * those of andi_hip_nj, so the same text), in the same order.
+ * --consensus (cf): the majority-rule consensus of the replicates' trees, from the same records -- the replicates are
+ * joined once whichever of the three files are asked for; all chunks' records are kept (40 bytes each) and go through one
+ * andi_hip_nj_splits call behind the loop. */
+static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath, tree_out *t, andi_hip_ctx *ctx,
+						  const andi_hip_model *M, const andi_hip_model *B, unsigned long replicates, const genome *g, size_t n,
+						  int model, int truncate) {
 	const size_t nrec = n == 2 ? 1 : n - 2, nsup = n > 3 ? n - 3 : 1;
 	size_t chunk = ((size_t)1 << 30) / (n * n * sizeof(double)); /* at most 1 GiB of doubles at a time */
 	chunk = chunk < 1 ? 1 : chunk > replicates ? replicates : chunk;
+	const size_t kept = cf ? replicates : chunk; /* the replicates whose records and skip flags stay */
 	double *D = malloc(chunk * n * n * sizeof *D);
-	andi_hip_nj_join *J = malloc(nrec * sizeof *J), *R = malloc(chunk * nrec * sizeof *R);
+	andi_hip_nj_join *J = malloc(nrec * sizeof *J), *Rall = malloc(kept * nrec * sizeof *Rall);
 	int64_t *bad = malloc(chunk * sizeof *bad);
-	uint8_t *skip = malloc(chunk);
+	uint8_t *skipall = malloc(kept);
 	uint32_t *total = calloc(nsup, sizeof *total), *part = calloc(nsup, sizeof *part);
-	if (!D || !J || !R || !bad || !skip || !total || !part || andi_hip_distances(M, n, model, D))
+	if (!D || !J || !Rall || !bad || !skipall || !total || !part || (f && andi_hip_distances(M, n, model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
-	int point_ok = 1;
+	int point_ok = f != NULL, cons_ok = cf != NULL;
 	for (size_t i = 0; i < n && point_ok; i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
@@ -528,12 +550,15 @@ static void write_support(FILE *f, const char *path, tree_out *t, andi_hip_ctx *
 	unsigned long counted = 0;
 	for (unsigned long first = 0; first < replicates; first += chunk) {
 		const size_t c = replicates - first < chunk ? replicates - first : chunk;
+		andi_hip_nj_join *R = cf ? Rall + first * nrec : Rall;
+		uint8_t *skip = cf ? skipall + first : skipall;
 		for (size_t k = 0; k < c; k++)
 			if (andi_hip_distances(B + (first + k) * n * n, n, model, D + k * n * n))
 				err(errno, "Could not allocate enough memory for the support values.");
 		if (andi_hip_nj_batch(ctx, D, n, c, R, bad)) {
-			soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-			point_ok = 0;
+			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+			if (cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
+			point_ok = cons_ok = 0;
 			break;
 		}
 		for (size_t k = 0; k < c; k++) {
@@ -556,7 +581,28 @@ static void write_support(FILE *f, const char *path, tree_out *t, andi_hip_ctx *
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
 		put_tree(f, path, J, total, g, n, truncate);
 	}
-	free(D), free(J), free(R), free(bad), free(skip), free(total), free(part);
+	if (cons_ok && counted == 0) {
+		soft_warnx("No consensus tree: no bootstrap matrix has a tree.");
+		cons_ok = 0;
+	}
+	if (cons_ok) {
+		uint32_t *ids = malloc(replicates * nsup * sizeof *ids), *freq = NULL;
+		uint64_t *sets = NULL;
+		size_t nsplits = 0, ninner = 0;
+		andi_hip_cons_node *nodes = malloc((2 * n - 1) * sizeof *nodes);
+		if (!ids || !nodes) err(errno, "Could not allocate enough memory for the consensus tree.");
+		if (andi_hip_nj_splits(ctx, Rall, n, replicates, skipall, ids, &nsplits, &freq, &sets)) {
+			soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
+		} else if (andi_hip_consensus(Rall, n, replicates, skipall, ids, nsplits, freq, sets, nodes, &ninner)) {
+			soft_warnx("No consensus tree: the bootstrap matrices' trees are inconsistent.");
+		} else {
+			if (counted < replicates) soft_warnx("Consensus tree from %lu of %lu bootstrap matrices.", counted, replicates);
+			put_consensus(cf, cpath, nodes, ninner, g, n, truncate);
+		}
+		andi_hip_free(freq), andi_hip_free(sets);
+		free(ids), free(nodes);
+	}
+	free(D), free(J), free(Rall), free(bad), free(skipall), free(total), free(part);
 }
 
 /* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
@@ -634,6 +680,7 @@ int main(int argc, char *argv[]) {
 												 {"reference-list", required_argument, NULL, 0},
 												 {"tree", required_argument, NULL, 0},
 												 {"support", required_argument, NULL, 0},
+												 {"consensus", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -664,6 +711,8 @@ int main(int argc, char *argv[]) {
 	tree_out tree = {0};
 	const char *support_path = NULL; /* --support */
 	FILE *support_f = NULL;
+	const char *consensus_path = NULL; /* --consensus */
+	FILE *consensus_f = NULL;
 
 	for (;;) {
 		int idx = 0;
@@ -677,6 +726,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files, &nfiles, &files_cap);
 				if (!strcmp(o, "tree")) tree.path = optarg;
 				if (!strcmp(o, "support")) support_path = optarg;
+				if (!strcmp(o, "consensus")) consensus_path = optarg;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
 				if (!strcmp(o, "reference")) {
 					rect = 1;
@@ -766,8 +816,11 @@ int main(int argc, char *argv[]) {
 	if (rect && tree.path) errx(1, "A tree (--tree) is not available together with --reference or --reference-list.");
 	if (rect && support_path) errx(1, "Support values (--support) are not available together with --reference or --reference-list.");
 	if (support_path && !bootstrap) errx(1, "Support values (--support) need bootstrap matrices: give -b N with N of at least 2.");
+	if (rect && consensus_path) errx(1, "A consensus tree (--consensus) is not available together with --reference or --reference-list.");
+	if (consensus_path && !bootstrap) errx(1, "A consensus tree (--consensus) needs bootstrap matrices: give -b N with N of at least 2.");
 	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
 	if (support_path && !(support_f = fopen(support_path, "w"))) err(1, "%s", support_path);
+	if (consensus_path && !(consensus_f = fopen(consensus_path, "w"))) err(1, "%s", consensus_path);
 	tree.device_for_ctx = opts.device;
 	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
@@ -848,15 +901,19 @@ int main(int argc, char *argv[]) {
 	if (bootstrap) { /* calculate_bootstrap, src/process.c:289-321 */
 		andi_hip_ctx *ctx = NULL;
 		andi_hip_model *B = malloc(bootstrap * n * n * sizeof *B);
+		/* the reference seeds its generator from the clock; ANDI_HIP_SEED=k draws the same matrices on every run */
+		const uint64_t seed = getenv("ANDI_HIP_SEED") ? strtoull(getenv("ANDI_HIP_SEED"), NULL, 10) : (uint64_t)time(NULL);
 		if (!B || andi_hip_ctx_create(&ctx, opts.device, msg, sizeof msg) ||
-			andi_hip_bootstrap(ctx, M, n, (uint64_t)time(NULL), bootstrap, B)) {
+			andi_hip_bootstrap(ctx, M, n, seed, bootstrap, B)) {
 			soft_warnx("Bootstrapping failed.");
 		} else {
 			for (unsigned long b = 0; b < bootstrap; b++) {
 				print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
-				if (tree.f && !support_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
+				if (tree.f && !support_f && !consensus_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
 			}
-			if (support_f) write_support(support_f, support_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model, truncate);
+			if (support_f || consensus_f)
+				write_support(support_f, support_path, consensus_f, consensus_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model,
+							  truncate);
 		}
 		if (ctx) andi_hip_ctx_destroy(ctx);
 		free(B);
@@ -864,6 +921,7 @@ int main(int argc, char *argv[]) {
 	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
 	if (tree.f && fclose(tree.f)) err(1, "%s", tree.path);
 	if (support_f && fclose(support_f)) err(1, "%s", support_path);
+	if (consensus_f && fclose(consensus_f)) err(1, "%s", consensus_path);
 	free(M);
 	free(in);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;

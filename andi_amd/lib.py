@@ -110,9 +110,14 @@ SYMBOLS = {
     "andi_hip_distances": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "andi_hip_format_newick": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
     "andi_hip_format_newick_support": (C.c_size_t, [_P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_consensus": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, _P, _P, C.POINTER(C.c_size_t)]),
+    "andi_hip_format_newick_consensus": (C.c_size_t, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P,
+                                                      C.c_size_t]),
     "andi_hip_nj": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "andi_hip_nj_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "andi_hip_nj_support": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P]),
+    "andi_hip_nj_splits": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_size_t), C.POINTER(_P),
+                                     C.POINTER(_P)]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -307,6 +312,62 @@ def newick(joins, names, truncate_names=False, support=None):
         else:
             need = load().andi_hip_format_newick_support(J.ctypes.data, support.ctypes.data, n, cn, int(truncate_names),
                                                          C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
+
+
+# andi_hip_cons_node: a node of a consensus tree (its parent's index, -1 for the root; the replicates that have its branch; its length)
+CONS_NODE = np.dtype([("parent", "<i4"), ("support", "<u4"), ("length", "<f8")])
+
+
+def _skip(skip, count):
+    if skip is None:
+        return None
+    skip = np.ascontiguousarray(skip, dtype=np.uint8)
+    assert skip.shape == (count,)
+    return skip
+
+
+def consensus(reps, ids, freq, sets, skip=None, n=None):
+    """The majority-rule consensus tree (andi_hip_consensus) of the replicate trees reps (count, n - 2) from nj_splits'
+    (ids, freq, sets): the nodes as a structured array of dtype CONS_NODE -- the n leaves, the majority splits in
+    ascending id order, the root last.  n: the number of leaves, where one record per replicate leaves it open (2 or 3;
+    by default 2 if the first replicate's record has no third child)."""
+    reps = np.ascontiguousarray(reps, dtype=NJ_JOIN)
+    assert reps.ndim == 2
+    count = reps.shape[0]
+    if n is None:
+        n = 2 if reps.shape[1] == 1 and int(reps[0, 0]["c"]) < 0 else reps.shape[1] + 2
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    freq = np.ascontiguousarray(freq, dtype=np.uint32)
+    sets = np.ascontiguousarray(sets, dtype=np.uint64)
+    assert ids.size == count * max(n - 3, 0) and sets.size == freq.size * ((n + 63) // 64)
+    skip = _skip(skip, count)
+    nodes = np.zeros(max(2 * n - 2, 3), CONS_NODE)
+    m = C.c_size_t(0)
+    if load().andi_hip_consensus(reps.ctypes.data, n, count, skip.ctypes.data if skip is not None else None,
+                                 ids.ctypes.data, freq.size, freq.ctypes.data, sets.ctypes.data, nodes.ctypes.data,
+                                 C.byref(m)):
+        raise AndiHipError("andi_hip_consensus: inconsistent arguments")
+    return nodes[:n + m.value + 1].copy()
+
+
+def newick_consensus(nodes, names, truncate_names=False):
+    """The Newick line (ending in ";\n") of consensus' nodes for the leaves `names`: every inner node labelled with the
+    number of replicates that have its branch; "" for malformed nodes."""
+    nodes = np.ascontiguousarray(nodes, dtype=CONS_NODE)
+    n = len(names)
+    ninner = len(nodes) - n - 1
+    if ninner < 0:
+        return ""
+    cn = _names(names)
+    cap = 64 + 60 * n + sum(len(x) for x in names)
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_newick_consensus(nodes.ctypes.data, n, ninner, cn, int(truncate_names),
+                                                       C.cast(out, _P), cap)
         if need < cap:
             break
         cap = need + 1
@@ -632,6 +693,29 @@ def nj_support(ctx: Context, J, reps, skip=None):
                                           skip.ctypes.data if skip is not None else None, support.ctypes.data),
                "nj_support")
     return support
+
+
+def nj_splits(ctx: Context, reps, skip=None):
+    """Every distinct bipartition among the replicate trees reps (count, n - 2), but those with skip[k] set
+    (andi_hip_nj_splits): (ids, freq, sets) -- ids (count, n - 3) uint32, the split of every pair record, numbered by first
+    appearance (0xFFFFFFFF in a skipped replicate); freq[id] the replicates that have split id; sets (nsplits, W) uint64,
+    its leaf set on the side without leaf 0."""
+    reps = np.ascontiguousarray(reps, dtype=NJ_JOIN)
+    assert reps.ndim == 2
+    count, n = reps.shape[0], reps.shape[1] + 2
+    skip = _skip(skip, count)
+    ids = np.zeros((count, max(n - 3, 0)), np.uint32)
+    nsplits, pf, ps = C.c_size_t(0), _P(), _P()
+    ctx._check(load().andi_hip_nj_splits(ctx._h, reps.ctypes.data, n, count, skip.ctypes.data if skip is not None else None,
+                                         ids.ctypes.data, C.byref(nsplits), C.byref(pf), C.byref(ps)), "nj_splits")
+    W, T = (n + 63) // 64, nsplits.value
+    try:
+        freq = np.ctypeslib.as_array(C.cast(pf, C.POINTER(C.c_uint32)), (T,)).copy() if T else np.zeros(0, np.uint32)
+        sets = np.ctypeslib.as_array(C.cast(ps, C.POINTER(C.c_uint64)), (T, W)).copy() if T else np.zeros((0, W), np.uint64)
+    finally:
+        load().andi_hip_free(pf)
+        load().andi_hip_free(ps)
+    return ids, freq, sets
 
 
 def _opts(p_value, model, device, host_threads, segment, num_gpus, devices, low_memory, sa_on_host, progress=None):

@@ -17,7 +17,8 @@
  * reference mode: andi_hip_dist_rect, andi_hip_queries_view and
  * andi_hip_format_distances_rect (additions only; the version stays 5); and the tree the matrix feeds:
  * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well); and bootstrap support on that
- * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only).
+ * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only); and the majority-rule
+ * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -197,6 +198,47 @@ size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *c
 size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
 									  const char *const *names, int truncate_names, char *out, size_t cap);
 
+/* One node of a consensus tree (andi_hip_consensus): the index of its parent in the same array (-1 for the root), the
+ * number of replicates that have the branch above it, and that branch's length.  16 bytes. */
+typedef struct {
+	int32_t parent;
+	uint32_t support;
+	double length;
+} andi_hip_cons_node;
+/* The majority-rule consensus tree (PHYLIP consense's "MR") of the replicate trees reps (count * (n - 2) records; one
+ * record per replicate for n = 2), from what andi_hip_nj_splits said about them: ids (count * (n - 3)), nsplits, freq,
+ * sets; skip as there.  No GPU is touched.  With used = the number of replicates with !skip || !skip[k]:
+ *  - split id enters iff 2 * freq[id] > used (a strict majority; a split in exactly half of the replicates stays out).
+ *    Such splits are pairwise compatible, and as every canonical side lacks leaf 0 they are a laminar family: any two
+ *    are nested or disjoint;
+ *  - nodes (room for 2n - 2 entries; 3 for n = 2): nodes[0 .. n) the leaves, nodes[n .. n + m) the majority splits in
+ *    ascending id order, m returned in *ninner, nodes[n + m] the root {-1, used, +0.0};
+ *  - an inner node's parent is the smallest majority split that properly contains its set, else the root; a leaf's
+ *    parent is the smallest majority split that contains the leaf, else the root; leaf 0's parent is the root;
+ *  - an inner node's support is freq[id], a leaf's is used;
+ *  - an inner node's length: the sequential sum, from +0.0, in ascending k (and ascending s within k), of the length of
+ *    the branch above node n + s -- the la, lb or lc of the record that has n + s as a child -- over every used replicate
+ *    k and pair record s with ids[k*(n-3) + s] == id, divided by (double)freq[id]; a leaf's length: the same sum of its
+ *    own branch over all used replicates, divided by (double)used;
+ *  - n = 2 and n = 3: the leaves under the root, m = 0 (ids, freq and sets are not read).
+ * Returns 1, with nodes and *ninner unspecified, on a NULL reps, nodes or ninner (ids, freq, sets for n >= 4 and nsplits
+ * > 0), n outside 2 ... 65535, count == 0, used == 0, and on inconsistent arguments: a child id of a used replicate that
+ * is out of range or a child twice, an id >= nsplits that is not 0xFFFFFFFF, a used replicate with an id 0xFFFFFFFF, a
+ * majority split that does not occur freq[id] times among the ids, whose set is empty or holds leaf 0 or a leaf >= n, or
+ * majority sets that are not laminar.  Work: O(count * n) plus the number of leaves of every majority split (at most
+ * n^2 / 2, a caterpillar).  Not recursive. */
+int andi_hip_consensus(const andi_hip_nj_join *reps, size_t n, size_t count, const uint8_t *skip, const uint32_t *ids,
+					   size_t nsplits, const uint32_t *freq, const uint64_t *sets, andi_hip_cons_node *nodes, size_t *ninner);
+/* The Newick text of andi_hip_consensus's nodes (n leaves, ninner inner nodes, the root at n + ninner), one line ending
+ * in ";\n".  The children of a node are listed in ascending order of the least leaf id below them (so leaf 0 comes first
+ * at the root).  A leaf is name ":" L, the name quoted and truncated exactly as andi_hip_format_newick does; an inner
+ * node is "(" children ")" support ":" L, the support in decimal; the root is "(" children ");"; L is %.8g.  Not
+ * recursive: a 65535-leaf caterpillar works.  Return value and cap as andi_hip_format_newick.  Malformed nodes give 0 and
+ * an empty string: n < 2, a parent that is no inner node and not the root (or a root whose parent is not -1), a cycle,
+ * an inner node with fewer than two children. */
+size_t andi_hip_format_newick_consensus(const andi_hip_cons_node *nodes, size_t n, size_t ninner,
+										const char *const *names, int truncate_names, char *out, size_t cap);
+
 /* ------------------------------------------------------------------ */
 /* Device-resident objects                                             */
 /* ------------------------------------------------------------------ */
@@ -337,6 +379,31 @@ int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count
  * error.  Not recursive: any depth works; the replicates' leaf sets are built in groups that fit the device.  Synchronous. */
 int andi_hip_nj_support(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
 						size_t count, const uint8_t *skip, uint32_t *support);
+/* Every distinct non-trivial bipartition ("split") among the `count` replicate trees `reps` (as above: count * (n - 2)
+ * records, what andi_hip_nj_batch writes), with its frequency: what a consensus tree is made of (andi_hip_consensus).
+ * A split is kept as its canonical side, the leaf set WITHOUT leaf 0 (a set that holds leaf 0 counts as its complement),
+ * in W = ceil(n / 64) words, bit i & 63 of word i >> 6 = leaf i.  Distinct splits are numbered by first appearance:
+ * replicates in ascending k (those with skip && skip[k] left out and not looked at), within a replicate the pair records
+ * in ascending s; the first split seen is id 0.
+ *  - ids[k*(n-3) + s] = the id of the bipartition of pair record s of replicate k; 0xFFFFFFFF for a skipped replicate;
+ *  - *nsplits = the number of distinct splits;
+ *  - (*freq)[id] = the number of used replicates whose tree has split id (a valid tree has each of its splits once);
+ *  - (*sets)[id*W + w] = word w of the canonical side of split id.
+ * *freq and *sets are malloc'ed by the library: free each with andi_hip_free.  The result is exact: a hash of the set only
+ * pre-filters, two sets are one split iff all W canonical words agree, whatever else shares their hash.  n < 4: *nsplits
+ * = 0, *freq = *sets = NULL, ids is not written (it may be NULL), returns 0.  Every replicate skipped: *nsplits = 0, the
+ * pointers NULL, ids all 0xFFFFFFFF, returns 0.  Argument checks (a NULL ctx, reps, ids, nsplits, freq or sets, count ==
+ * 0, n outside 2 ... 65535) and the validation of the used replicates' records are those of andi_hip_nj_support, on the
+ * host before any HIP call; they return 1 through the context's error.  Not recursive; the replicates' leaf sets are
+ * built in groups that fit the device and are never resident all at once.
+ * Unlike andi_hip_nj_support this call CAN FAIL ON SIZE: the table of the distinct splits -- W * 8 + 28 bytes each -- is
+ * resident on the device.  It gets room for every set of every used replicate or, if that is more, for as many splits as
+ * half of the device memory that is free at the call holds; when the trees have more distinct splits than that, the call
+ * returns 1 and the context's error names the bytes the table needed (at 65535 leaves a split is 8 KiB and a tree has
+ * 65532 of them: 537 MB per replicate that shares no branch with the others).  On any failure *nsplits = 0 and the
+ * pointers are NULL.  Synchronous. */
+int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n, size_t count, const uint8_t *skip,
+					   uint32_t *ids, size_t *nsplits, uint32_t **freq, uint64_t **sets);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
