@@ -377,9 +377,11 @@ static void put_leaf(sink *o, const char *name, int truncate) {
 }
 
 /* andi_hip_nj's records as Newick text (include/andi_hip.h), depth first with a stack of its own instead of recursion;
- * with support, support[s] is the label behind the ")" of pair record s */
-size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
-									  const char *const *names, int truncate_names, char *out, size_t cap) {
+ * the label behind the ")" of pair record s is support[s] if support is given, else the transfer bootstrap expectation
+ * from depth, transfer and used if depth is given, else none */
+static size_t format_newick(const andi_hip_nj_join *J, const uint32_t *support, const uint32_t *depth,
+							const uint64_t *transfer, size_t used, size_t n, const char *const *names, int truncate_names,
+							char *out, size_t cap) {
 	sink o = {out, cap, 0};
 	if (out && cap) out[0] = '\0';
 	if (!J || !names || n < 2) return 0;
@@ -397,19 +399,21 @@ size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t 
 	} frame;
 	frame *stack = malloc((pairs + 1) * sizeof *stack);
 	if (!stack) return 0;
-	size_t depth = 0;
-	stack[depth++] = (frame){root, 0, 0.0};
+	size_t top = 0;
+	stack[top++] = (frame){root, 0, 0.0};
 	put(&o, "(");
-	while (depth) {
-		frame *f = &stack[depth - 1];
+	while (top) {
+		frame *f = &stack[top - 1];
 		const andi_hip_nj_join *r = &J[f->rec];
 		const int kids = f->rec == root && n > 2 ? 3 : 2;
 		if (f->next == kids) {
 			const double len = f->len;
-			depth--;
+			const size_t rec = f->rec;
+			top--;
 			put(&o, ")");
-			if (depth && support) put(&o, "%u", (unsigned)support[f->rec]);
-			if (depth) put(&o, ":%.8g", len);
+			if (top && support) put(&o, "%u", (unsigned)support[rec]);
+			else if (top && depth) put(&o, "%.6g", 1.0 - (double)transfer[rec] / ((double)used * (double)(depth[rec] - 1)));
+			if (top) put(&o, ":%.8g", len);
 			else put(&o, ";\n");
 			continue;
 		}
@@ -421,7 +425,7 @@ size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t 
 			put_leaf(&o, names[child], truncate_names);
 			put(&o, ":%.8g", len);
 		} else {
-			stack[depth++] = (frame){child - n, 0, len};
+			stack[top++] = (frame){child - n, 0, len};
 			put(&o, "(");
 		}
 	}
@@ -430,9 +434,24 @@ size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t 
 	return o.len;
 }
 
+size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
+									  const char *const *names, int truncate_names, char *out, size_t cap) {
+	return format_newick(J, support, NULL, NULL, 0, n, names, truncate_names, out, cap);
+}
+
 size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
 							  char *out, size_t cap) {
-	return andi_hip_format_newick_support(J, NULL, n, names, truncate_names, out, cap);
+	return format_newick(J, NULL, NULL, NULL, 0, n, names, truncate_names, out, cap);
+}
+
+size_t andi_hip_format_newick_transfer(const andi_hip_nj_join *J, const uint32_t *depth, const uint64_t *transfer,
+									   size_t used, size_t n, const char *const *names, int truncate_names,
+									   char *out, size_t cap) {
+	if (out && cap) out[0] = '\0';
+	if (!depth || !transfer || used == 0) return 0;
+	for (size_t s = 0; s + 3 < n; s++)
+		if (depth[s] < 2) return 0;
+	return format_newick(J, NULL, depth, transfer, used, n, names, truncate_names, out, cap);
 }
 
 /* ------------------------------------------------------------------ */

@@ -371,6 +371,8 @@ static void usage(int status) {
 		"                       number of bootstrap matrices whose tree has that branch\n"
 		"      --consensus=FILE With -b: write the majority-rule consensus tree of the bootstrap matrices' trees to FILE,\n"
 		"                       each inner branch labelled with the number of those trees that have it\n"
+		"      --transfer=FILE  With -b: write the tree of the first matrix to FILE, each inner branch labelled with its\n"
+		"                       transfer bootstrap expectation (TBE, between 0 and 1) over the bootstrap matrices' trees\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -472,6 +474,21 @@ static void put_tree(FILE *f, const char *path, const andi_hip_nj_join *J, const
 	free(text), free(names);
 }
 
+/* the same line with the transfer bootstrap expectation as inner labels */
+static void put_transfer_tree(FILE *f, const char *path, const andi_hip_nj_join *J, const uint32_t *depth, const uint64_t *transfer,
+							  size_t used, const genome *g, size_t n, int truncate) {
+	const char **names = xmalloc(n * sizeof *names);
+	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
+	size_t cap = 64 + n * 60;
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	const size_t need = andi_hip_format_newick_transfer(J, depth, transfer, used, n, names, truncate, text, cap);
+	if (need >= cap)
+		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_transfer(J, depth, transfer, used, n, names, truncate, text, cap);
+	if (fputs(text, f) == EOF) err(1, "%s", path);
+	free(text), free(names);
+}
+
 static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, size_t n, int model, int truncate, int k) {
 	if (t->failed) return;
 	char msg[512];
@@ -519,9 +536,11 @@ static void put_consensus(FILE *f, const char *path, const andi_hip_cons_node *n
  * of the chunks add up.  With --tree, the replicates' lines of that file are written from the same records (bit for bit
  * those of andi_hip_nj, so the same text), in the same order.
  * --consensus (cf): the majority-rule consensus of the replicates' trees, from the same records -- the replicates are
- * joined once whichever of the three files are asked for; all chunks' records are kept (40 bytes each) and go through one
- * andi_hip_nj_splits call behind the loop. */
-static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath, tree_out *t, andi_hip_ctx *ctx,
+ * joined once whichever of the four files are asked for; all chunks' records are kept (40 bytes each) and go through one
+ * andi_hip_nj_splits call behind the loop.
+ * --transfer (tf): the point estimate's tree again, labelled with the transfer bootstrap expectation: per chunk one
+ * andi_hip_nj_transfer call next to the support count's, on the same records; the chunks' sums add up. */
+static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath, FILE *tf, const char *tpath, tree_out *t, andi_hip_ctx *ctx,
 						  const andi_hip_model *M, const andi_hip_model *B, unsigned long replicates, const genome *g, size_t n,
 						  int model, int truncate) {
 	const size_t nrec = n == 2 ? 1 : n - 2, nsup = n > 3 ? n - 3 : 1;
@@ -532,20 +551,24 @@ static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath
 	andi_hip_nj_join *J = malloc(nrec * sizeof *J), *Rall = malloc(kept * nrec * sizeof *Rall);
 	int64_t *bad = malloc(chunk * sizeof *bad);
 	uint8_t *skipall = malloc(kept);
-	uint32_t *total = calloc(nsup, sizeof *total), *part = calloc(nsup, sizeof *part);
-	if (!D || !J || !Rall || !bad || !skipall || !total || !part || (f && andi_hip_distances(M, n, model, D)))
+	uint32_t *total = calloc(nsup, sizeof *total), *part = calloc(nsup, sizeof *part), *depth = calloc(nsup, sizeof *depth);
+	uint64_t *ttotal = calloc(nsup, sizeof *ttotal), *tpart = calloc(nsup, sizeof *tpart);
+	if (!D || !J || !Rall || !bad || !skipall || !total || !part || !depth || !ttotal || !tpart ||
+		((f || tf) && andi_hip_distances(M, n, model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
-	int point_ok = f != NULL, cons_ok = cf != NULL;
-	for (size_t i = 0; i < n && point_ok; i++)
+	int point_ok = f != NULL, trans_ok = tf != NULL, cons_ok = cf != NULL;
+	for (size_t i = 0; i < n && (point_ok || trans_ok); i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
-				soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
-				point_ok = 0;
+				if (f) soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
+				if (tf) soft_warnx("No transfer support: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
+				point_ok = trans_ok = 0;
 				break;
 			}
-	if (point_ok && andi_hip_nj(ctx, D, n, J)) {
-		soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-		point_ok = 0;
+	if ((point_ok || trans_ok) && andi_hip_nj(ctx, D, n, J)) {
+		if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+		point_ok = trans_ok = 0;
 	}
 	unsigned long counted = 0;
 	for (unsigned long first = 0; first < replicates; first += chunk) {
@@ -558,7 +581,8 @@ static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath
 		if (andi_hip_nj_batch(ctx, D, n, c, R, bad)) {
 			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
 			if (cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
-			point_ok = cons_ok = 0;
+			if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+			point_ok = cons_ok = trans_ok = 0;
 			break;
 		}
 		for (size_t k = 0; k < c; k++) {
@@ -569,17 +593,33 @@ static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath
 			else if (t->f) put_tree(t->f, t->path, R + k * nrec, NULL, g, n, truncate);
 			counted += !skip[k];
 		}
-		if (!point_ok) continue; /* (the replicates' lines of --tree are still written) */
-		if (andi_hip_nj_support(ctx, J, R, n, c, skip, part)) {
-			soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-			point_ok = 0;
-			continue;
+		/* (whatever fails below, the replicates' lines of --tree are still written) */
+		if (point_ok) {
+			if (andi_hip_nj_support(ctx, J, R, n, c, skip, part)) {
+				soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+				point_ok = 0;
+			} else
+				for (size_t s = 0; s + 3 < n; s++) total[s] += part[s];
 		}
-		for (size_t s = 0; s + 3 < n; s++) total[s] += part[s];
+		if (trans_ok) {
+			if (andi_hip_nj_transfer(ctx, J, R, n, c, skip, depth, tpart, NULL)) {
+				soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+				trans_ok = 0;
+			} else
+				for (size_t s = 0; s + 3 < n; s++) ttotal[s] += tpart[s];
+		}
 	}
 	if (point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
 		put_tree(f, path, J, total, g, n, truncate);
+	}
+	if (trans_ok && counted == 0) {
+		soft_warnx("No transfer support: no bootstrap matrix has a tree.");
+		trans_ok = 0;
+	}
+	if (trans_ok) {
+		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
+		put_transfer_tree(tf, tpath, J, depth, ttotal, counted, g, n, truncate);
 	}
 	if (cons_ok && counted == 0) {
 		soft_warnx("No consensus tree: no bootstrap matrix has a tree.");
@@ -602,7 +642,7 @@ static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath
 		andi_hip_free(freq), andi_hip_free(sets);
 		free(ids), free(nodes);
 	}
-	free(D), free(J), free(Rall), free(bad), free(skipall), free(total), free(part);
+	free(D), free(J), free(Rall), free(bad), free(skipall), free(total), free(part), free(depth), free(ttotal), free(tpart);
 }
 
 /* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
@@ -681,6 +721,7 @@ int main(int argc, char *argv[]) {
 												 {"tree", required_argument, NULL, 0},
 												 {"support", required_argument, NULL, 0},
 												 {"consensus", required_argument, NULL, 0},
+												 {"transfer", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -713,6 +754,8 @@ int main(int argc, char *argv[]) {
 	FILE *support_f = NULL;
 	const char *consensus_path = NULL; /* --consensus */
 	FILE *consensus_f = NULL;
+	const char *transfer_path = NULL; /* --transfer */
+	FILE *transfer_f = NULL;
 
 	for (;;) {
 		int idx = 0;
@@ -727,6 +770,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "tree")) tree.path = optarg;
 				if (!strcmp(o, "support")) support_path = optarg;
 				if (!strcmp(o, "consensus")) consensus_path = optarg;
+				if (!strcmp(o, "transfer")) transfer_path = optarg;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
 				if (!strcmp(o, "reference")) {
 					rect = 1;
@@ -818,9 +862,12 @@ int main(int argc, char *argv[]) {
 	if (support_path && !bootstrap) errx(1, "Support values (--support) need bootstrap matrices: give -b N with N of at least 2.");
 	if (rect && consensus_path) errx(1, "A consensus tree (--consensus) is not available together with --reference or --reference-list.");
 	if (consensus_path && !bootstrap) errx(1, "A consensus tree (--consensus) needs bootstrap matrices: give -b N with N of at least 2.");
+	if (rect && transfer_path) errx(1, "Transfer support (--transfer) is not available together with --reference or --reference-list.");
+	if (transfer_path && !bootstrap) errx(1, "Transfer support (--transfer) needs bootstrap matrices: give -b N with N of at least 2.");
 	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
 	if (support_path && !(support_f = fopen(support_path, "w"))) err(1, "%s", support_path);
 	if (consensus_path && !(consensus_f = fopen(consensus_path, "w"))) err(1, "%s", consensus_path);
+	if (transfer_path && !(transfer_f = fopen(transfer_path, "w"))) err(1, "%s", transfer_path);
 	tree.device_for_ctx = opts.device;
 	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
@@ -909,10 +956,10 @@ int main(int argc, char *argv[]) {
 		} else {
 			for (unsigned long b = 0; b < bootstrap; b++) {
 				print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
-				if (tree.f && !support_f && !consensus_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
+				if (tree.f && !support_f && !consensus_f && !transfer_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
 			}
-			if (support_f || consensus_f)
-				write_support(support_f, support_path, consensus_f, consensus_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model,
+			if (support_f || consensus_f || transfer_f)
+				write_support(support_f, support_path, consensus_f, consensus_path, transfer_f, transfer_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model,
 							  truncate);
 		}
 		if (ctx) andi_hip_ctx_destroy(ctx);
@@ -922,6 +969,7 @@ int main(int argc, char *argv[]) {
 	if (tree.f && fclose(tree.f)) err(1, "%s", tree.path);
 	if (support_f && fclose(support_f)) err(1, "%s", support_path);
 	if (consensus_f && fclose(consensus_f)) err(1, "%s", consensus_path);
+	if (transfer_f && fclose(transfer_f)) err(1, "%s", transfer_path);
 	free(M);
 	free(in);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;

@@ -110,6 +110,8 @@ SYMBOLS = {
     "andi_hip_distances": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "andi_hip_format_newick": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
     "andi_hip_format_newick_support": (C.c_size_t, [_P, _P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_format_newick_transfer": (C.c_size_t, [_P, _P, _P, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P,
+                                                     C.c_size_t]),
     "andi_hip_consensus": (C.c_int, [_P, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, _P, _P, _P, C.POINTER(C.c_size_t)]),
     "andi_hip_format_newick_consensus": (C.c_size_t, [_P, C.c_size_t, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P,
                                                       C.c_size_t]),
@@ -118,6 +120,7 @@ SYMBOLS = {
     "andi_hip_nj_support": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "andi_hip_nj_splits": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_size_t), C.POINTER(_P),
                                      C.POINTER(_P)]),
+    "andi_hip_nj_transfer": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, _P]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -312,6 +315,27 @@ def newick(joins, names, truncate_names=False, support=None):
         else:
             need = load().andi_hip_format_newick_support(J.ctypes.data, support.ctypes.data, n, cn, int(truncate_names),
                                                          C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
+
+
+def newick_transfer(joins, depth, transfer, used, names, truncate_names=False):
+    """The Newick line of nj's records with the transfer bootstrap expectation as the label of every inner branch
+    (andi_hip_format_newick_transfer), from nj_transfer's depth and transfer summed over `used` replicates; "" where the
+    library refuses (used == 0, a depth below 2, malformed records)."""
+    J = np.ascontiguousarray(joins, dtype=NJ_JOIN)
+    n = len(names)
+    cn = _names(names)
+    depth = np.ascontiguousarray(depth, dtype=np.uint32)
+    transfer = np.ascontiguousarray(transfer, dtype=np.uint64)
+    assert len(depth) >= max(n - 3, 0) and len(transfer) >= max(n - 3, 0)
+    cap = 64 + 56 * n + sum(len(x) for x in names)
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_newick_transfer(J.ctypes.data, depth.ctypes.data, transfer.ctypes.data, int(used), n, cn,
+                                                      int(truncate_names), C.cast(out, _P), cap)
         if need < cap:
             break
         cap = need + 1
@@ -693,6 +717,26 @@ def nj_support(ctx: Context, J, reps, skip=None):
                                           skip.ctypes.data if skip is not None else None, support.ctypes.data),
                "nj_support")
     return support
+
+
+def nj_transfer(ctx: Context, J, reps, skip=None, per=False):
+    """Transfer bootstrap support (andi_hip_nj_transfer) of the tree J (n - 2 records) among the replicate trees reps
+    (count, n - 2), but those with skip[k] set: (depth, transfer) -- uint32[n - 3], the size of the smaller side of every
+    pair record's bipartition, and uint64[n - 3], its transfer index summed over the used replicates; with per=True also
+    the (count, n - 3) uint32 transfer indices themselves (0xFFFFFFFF in a skipped replicate's row)."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    reps = np.ascontiguousarray(reps, dtype=NJ_JOIN)
+    n = len(J) + 2
+    assert reps.ndim == 2 and reps.shape[1] == len(J)
+    count = reps.shape[0]
+    skip = _skip(skip, count)
+    depth = np.zeros(max(n - 3, 0), np.uint32)
+    transfer = np.zeros(max(n - 3, 0), np.uint64)
+    each = np.zeros((count, max(n - 3, 0)), np.uint32) if per else None
+    ctx._check(load().andi_hip_nj_transfer(ctx._h, J.ctypes.data, reps.ctypes.data, n, count,
+                                           skip.ctypes.data if skip is not None else None, depth.ctypes.data,
+                                           transfer.ctypes.data, each.ctypes.data if per else None), "nj_transfer")
+    return (depth, transfer, each) if per else (depth, transfer)
 
 
 def nj_splits(ctx: Context, reps, skip=None):

@@ -18,7 +18,8 @@
  * andi_hip_format_distances_rect (additions only; the version stays 5); and the tree the matrix feeds:
  * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well); and bootstrap support on that
  * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only); and the majority-rule
- * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only).
+ * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only);
+ * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -197,6 +198,14 @@ size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *c
  * one walk).  Return value, cap and the rule for malformed records as above. */
 size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
 									  const char *const *names, int truncate_names, char *out, size_t cap);
+/* The same walk with the transfer bootstrap expectation (TBE) as internal node labels, from andi_hip_nj_transfer's depth
+ * and transfer and the number `used` of replicates that were summed: behind the ")" of pair record s, %.6g of
+ * 1.0 - (double)transfer[s] / ((double)used * (double)(depth[s] - 1)), each operation rounded; the final record gets no
+ * label.  Return value, cap and malformed records as andi_hip_format_newick.  used == 0, a depth[s] < 2 (s < n - 3) and a
+ * NULL depth or transfer give 0 and an empty string, whatever n. */
+size_t andi_hip_format_newick_transfer(const andi_hip_nj_join *J, const uint32_t *depth, const uint64_t *transfer,
+									   size_t used, size_t n, const char *const *names, int truncate_names,
+									   char *out, size_t cap);
 
 /* One node of a consensus tree (andi_hip_consensus): the index of its parent in the same array (-1 for the root), the
  * number of replicates that have the branch above it, and that branch's length.  16 bytes. */
@@ -404,6 +413,26 @@ int andi_hip_nj_support(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const a
  * pointers are NULL.  Synchronous. */
 int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n, size_t count, const uint8_t *skip,
 					   uint32_t *ids, size_t *nsplits, uint32_t **freq, uint64_t **sets);
+/* Transfer bootstrap support (Lemoine et al., Nature 2018) of the branches of `tree` among the replicate trees `reps`;
+ * tree, reps, n, count and skip as andi_hip_nj_support.  Pair record s (0 <= s < n - 3) of a tree defines the leaf set
+ * L_s below node n + s; for two leaf sets h(A, B) = |A xor B| over the n leaves, and the transfer distance is
+ * d(A, B) = min(h, n - h), which does not depend on the side either bipartition is kept on.
+ *  - depth[s] = min(|L_s|, n - |L_s|) of the tree's pair record s (n - 3 values; >= 2 for andi_hip_nj's records);
+ *  - per[k*(n-3) + s], the transfer index of branch s in replicate k, = min(depth[s] - 1, min over the pair records t of
+ *    replicate k of d(L_s, L_{k,t})): the cap depth[s] - 1 is what the replicate's leaf branches contribute (a leaf of
+ *    the smaller side is that far away).  0xFFFFFFFF for a skipped replicate.  per may be NULL;
+ *  - transfer[s] = the sum of per[k][s] over the used replicates, 64 bits (n - 3 values).  The sums of calls over
+ *    disjoint chunks of replicates add up to the sum of one call.
+ * The transfer bootstrap expectation of branch s is 1 - transfer[s] / (used * (depth[s] - 1)), which
+ * andi_hip_format_newick_transfer prints.  The number of used replicates with per[k][s] == 0 is andi_hip_nj_support's
+ * support[s].  Everything is an integer and exact.  n < 4: nothing is written, returns 0.  Every replicate skipped:
+ * transfer all 0, depth written, per all 0xFFFFFFFF, returns 0.  Bad arguments (a NULL ctx, tree, reps, depth or
+ * transfer, count == 0, n outside 2 ... 65535) and the validation of the tree's and the used replicates' records are
+ * those of andi_hip_nj_support, on the host before any HIP call; they return 1 through the context's error.  The
+ * replicates' leaf sets are built in groups that fit the device; the results do not depend on the grouping, and the call
+ * does not fail on size while one tree's sets fit.  Work: (n - 3)^2 * used * ceil(n / 64) word pairs.  Synchronous. */
+int andi_hip_nj_transfer(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
+						 size_t count, const uint8_t *skip, uint32_t *depth, uint64_t *transfer, uint32_t *per);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
