@@ -5,7 +5,7 @@ package is the thin Python mirror of that interface used by the tests and the
 benchmark.
 """
 from . import lib, synth  # noqa: F401
-from .lib import (AndiHipError, Context, bootstrap, Esa, Queries, M_ANI, M_JC, M_KIMURA, M_LOGDET, M_RAW,  # noqa: F401
-                  consensus, dist_matrix, dist_rect, distances, estimate, format_distances, format_distances_rect,
+from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_range, Esa, Queries, M_ANI, M_JC, M_KIMURA, M_LOGDET, M_RAW,  # noqa: F401
+                  consensus, dist_matrix, dist_rect, distances, estimate, estimate_portable, format_distances, format_distances_rect,
                   match_positions, newick, newick_consensus, newick_transfer, nj, nj_batch, nj_splits, nj_support, nj_transfer,
                   scan_rows, subject_prepare, suffix_array)

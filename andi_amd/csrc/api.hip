@@ -1164,27 +1164,37 @@ int andi_hip_copy_ceiling(andi_hip_ctx *ctx, size_t bytes, int reps, double *gbp
 }
 
 // ------------------------------------------------------------------ bootstrap
+int andi_hip_bootstrap_range(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uint64_t seed, size_t first,
+							 size_t count, andi_hip_model *B) {
+	if (!ctx || !M || !B || n == 0 || n > 65535 || first > 0xffffffffull || count > 0xffffffffull ||
+		first + count > 0xffffffffull) {
+		if (ctx) ctx->err = "andi_hip_bootstrap_range: bad arguments (ctx, M and B must be given, 1 <= n <= 65535, first + count < 2^32)";
+		return 1;
+	}
+	if (count == 0) return 0;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t one = n * n * sizeof(andi_hip_model);
+	andi_hip_model *dM = nullptr, *dB = nullptr;
+	hipError_t e = hipMalloc((void **)&dM, one);
+	if (e == hipSuccess) e = hipMalloc((void **)&dB, one * count);
+	if (e == hipSuccess) e = hipMemcpyAsync(dM, M, one, hipMemcpyHostToDevice, ctx->stream);
+	if (e == hipSuccess)
+		e = andi_launch_bootstrap(dM, dB, (uint32_t)n, (uint32_t)first, (uint32_t)count, seed, ctx->stream);
+	if (e == hipSuccess) e = hipMemcpyAsync(B, dB, one * count, hipMemcpyDeviceToHost, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	(void)andi_arena::dev_free(dM);
+	(void)andi_arena::dev_free(dB);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_bootstrap_range", e);
+	return 0;
+}
+
 int andi_hip_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uint64_t seed,
 					   size_t replicates, andi_hip_model *B) {
 	if (!ctx || !M || !B || n == 0 || n > 65535) {
 		if (ctx) ctx->err = "andi_hip_bootstrap: bad arguments";
 		return 1;
 	}
-	if (replicates == 0) return 0;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const size_t one = n * n * sizeof(andi_hip_model);
-	andi_hip_model *dM = nullptr, *dB = nullptr;
-	hipError_t e = hipMalloc((void **)&dM, one);
-	if (e == hipSuccess) e = hipMalloc((void **)&dB, one * replicates);
-	if (e == hipSuccess) e = hipMemcpyAsync(dM, M, one, hipMemcpyHostToDevice, ctx->stream);
-	if (e == hipSuccess)
-		e = andi_launch_bootstrap(dM, dB, (uint32_t)n, (uint32_t)replicates, seed, ctx->stream);
-	if (e == hipSuccess) e = hipMemcpyAsync(B, dB, one * replicates, hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-	(void)andi_arena::dev_free(dM);
-	(void)andi_arena::dev_free(dB);
-	if (e != hipSuccess) return fail(ctx, "andi_hip_bootstrap", e);
-	return 0;
+	return andi_hip_bootstrap_range(ctx, M, n, seed, 0, replicates, B);
 }
 
 void andi_hip_reload_knobs(void) { g_knobs.store(new KnobSnapshot(), std::memory_order_release); }

@@ -10,105 +10,25 @@
 // every (replicate, pair) owns a counter-based Philox stream, so the result is a
 // pure function of (seed, replicate, i, j) whatever the launch geometry, and all
 // replicates of a matrix are one launch.
+//
+// andi_hip_bootstrap_nj (nj.hip) never has the replicates as models: k_pair_sums adds the two directions of every pair
+// once per call, and k_bootstrap_dist draws a (replicate, pair) from those sums and stores the one double its tree needs --
+// the portable estimate (andi_estimate.h) of the drawn counts doubled, which is what model_average makes of the mirrored
+// replicate.  Draw and estimator are the functions k_bootstrap and the host use, so both are bit-exact to them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "andi_estimate.h"
 #include "andi_hip.h"
 #include "bootstrap.h"
+#include "bootstrap_draw.h"
 
 namespace {
 
-// Philox4x32-10 (Salmon et al., SC'11)
-struct Philox {
-	uint32_t ctr[4], key[2], out[4];
-	int have;
-	__device__ Philox(uint64_t seed, uint64_t stream, uint64_t sub) : have(0) {
-		ctr[0] = 0, ctr[1] = (uint32_t)sub, ctr[2] = (uint32_t)stream, ctr[3] = (uint32_t)(stream >> 32);
-		key[0] = (uint32_t)seed, key[1] = (uint32_t)(seed >> 32);
-	}
-	__device__ void round(uint32_t *c, const uint32_t *k) {
-		uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-		uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k[0], n1 = (uint32_t)p1;
-		uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k[1], n3 = (uint32_t)p0;
-		c[0] = n0, c[1] = n1, c[2] = n2, c[3] = n3;
-	}
-	__device__ void refill() {
-		uint32_t c[4] = {ctr[0], ctr[1], ctr[2], ctr[3]}, k[2] = {key[0], key[1]};
-		for (int r = 0; r < 10; ++r) {
-			round(c, k);
-			k[0] += 0x9E3779B9u, k[1] += 0xBB67AE85u;
-		}
-		out[0] = c[0], out[1] = c[1], out[2] = c[2], out[3] = c[3];
-		ctr[0]++; // 2^32 blocks per stream is far more than one pair ever needs
-		have = 4;
-	}
-	__device__ double uniform() { // (0, 1), 53 random bits
-		if (have < 2) refill();
-		uint64_t hi = out[--have], lo = out[--have];
-		uint64_t bits = ((hi << 32) | lo) >> 11;
-		return ((double)bits + 0.5) * (1.0 / 9007199254740992.0);
-	}
-};
-
-__device__ double stirling_tail(double k) { // log(k!) - [Stirling's leading terms]
-	const double tab[10] = {0.0810614667953272, 0.0413406959554092, 0.0276779256849983, 0.02079067210376509,
-							0.0166446911898211, 0.0138761288230707, 0.0118967099458917, 0.0104112652619720,
-							0.00925546218271273, 0.00833056343336287};
-	if (k <= 9) return tab[(int)k];
-	double kp1sq = (k + 1) * (k + 1);
-	return (1.0 / 12 - (1.0 / 360 - 1.0 / 1260 / kp1sq) / kp1sq) / (k + 1);
-}
-
-// Binomial(n, p), exact: waiting-time method for small n*p, BTRS (Hoermann 1993,
-// "The generation of binomial random variates") otherwise.
-__device__ uint64_t binomial(Philox &g, uint64_t n, double p) {
-	if (n == 0 || p <= 0.0) return 0;
-	if (p >= 1.0) return n;
-	const bool flip = p > 0.5;
-	if (flip) p = 1.0 - p;
-	uint64_t k;
-	const double nd = (double)n;
-	if (nd * p < 10.0) {
-		const double lq = log1p(-p);
-		double sum = 0.0;
-		k = 0;
-		for (;;) {
-			sum += ceil(log(g.uniform()) / lq);
-			if (sum > nd) break;
-			++k;
-		}
-	} else {
-		const double q = 1.0 - p, spq = sqrt(nd * p * q);
-		const double b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p;
-		const double c = nd * p + 0.5, vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq;
-		const double r = p / q, m = floor((nd + 1) * p);
-		for (;;) {
-			double u = g.uniform() - 0.5, v = g.uniform();
-			double us = 0.5 - fabs(u);
-			double kd = floor((2 * a / us + b) * u + c);
-			if (kd < 0 || kd > nd) continue;
-			if (us >= 0.07 && v <= vr) {
-				k = (uint64_t)kd;
-				break;
-			}
-			v = log(v * alpha / (a / (us * us) + b));
-			double ub = (m + 0.5) * log((m + 1) / (r * (nd - m + 1))) +
-						(nd + 1) * log((nd - m + 1) / (nd - kd + 1)) +
-						(kd + 0.5) * log(r * (nd - kd + 1) / (kd + 1)) + stirling_tail(m) +
-						stirling_tail(nd - m) - stirling_tail(kd) - stirling_tail(nd - kd);
-			if (v <= ub) {
-				k = (uint64_t)kd;
-				break;
-			}
-		}
-	}
-	return flip ? n - k : k;
-}
-
-// One thread per (replicate, unordered pair incl. diagonal).
+// One thread per (replicate, unordered pair incl. diagonal); replicate rep of the launch is rep0 + rep of the stream.
 __global__ __launch_bounds__(256) void k_bootstrap(const andi_hip_model *__restrict__ M,
 												   andi_hip_model *__restrict__ B, uint32_t n,
-												   uint32_t replicates, uint64_t seed) {
+												   uint32_t rep0, uint32_t replicates, uint64_t seed) {
 	const uint64_t per = (uint64_t)n * (n + 1) / 2;
 	uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (gid >= per * replicates) return;
@@ -135,33 +55,90 @@ __global__ __launch_bounds__(256) void k_bootstrap(const andi_hip_model *__restr
 		return;
 	}
 	const andi_hip_model a = M[(size_t)i * n + j], b = M[(size_t)j * n + i];
-	uint64_t counts[16], total = 0;
-	for (int c = 0; c < 16; ++c) { // model_average, src/model.c:39-46
-		counts[c] = (uint64_t)(uint32_t)(a.counts[c] + b.counts[c]);
-		total += counts[c];
-	}
+	uint32_t sums[16];
+	for (int c = 0; c < 16; ++c) sums[c] = a.counts[c] + b.counts[c]; // model_average, src/model.c:39-46
 	res.seq_len = a.seq_len + b.seq_len;
-	// multinomial by conditional binomials (the construction gsl_ran_multinomial uses)
-	Philox g(seed, (uint64_t)rep, (uint64_t)i * n + j);
-	uint64_t left = total, mass = total;
-	for (int c = 0; c < 16; ++c) {
-		uint64_t draw = 0;
-		if (counts[c] > 0 && left > 0)
-			draw = counts[c] >= mass ? left : binomial(g, left, (double)counts[c] / (double)mass);
-		res.counts[c] = (uint32_t)draw;
-		left -= draw;
-		mass -= counts[c];
-	}
+	bootstrap_draw(seed, (uint64_t)rep0 + rep, (uint64_t)i * n + j, sums, res.counts);
 	out[(size_t)i * n + j] = res;
 	out[(size_t)j * n + i] = res; // src/process.c:314
 }
 
+// where row i of the packed strict upper triangle starts: pair (i, j), i < j, is entry tri_start(i) + j - i - 1
+__device__ inline uint64_t tri_start(uint64_t i, uint64_t n) { return i * (2 * n - i - 1) / 2; }
+
+// S[t][c] = M[i][j].counts[c] + M[j][i].counts[c] (32-bit, wrapping as model_average) for every pair t = (i, j), i < j:
+// block row i, sixteen consecutive threads per pair, so the 64 bytes of a pair's counts are read and written as one piece.
+__global__ __launch_bounds__(256) void k_pair_sums(const andi_hip_model *__restrict__ M, uint32_t *__restrict__ S, uint32_t n) {
+	const uint32_t i = blockIdx.y;
+	const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const uint64_t j = (uint64_t)i + 1 + (item >> 4);
+	const uint32_t c = (uint32_t)item & 15;
+	if (j >= n) return;
+	const uint64_t t = tri_start(i, n) + (j - i - 1);
+	S[t * 16 + c] = M[(size_t)i * n + j].counts[c] + M[(size_t)j * n + i].counts[c];
+}
+
+// One thread per (replicate of the group = blockIdx.y, pair): the sums, the draw of replicate rep0 + blockIdx.y, the
+// estimate, one double to D[rep][i * n + j] (the upper triangle; k_nj_init mirrors it).
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_bootstrap_dist(const uint4 *__restrict__ S, double *__restrict__ D, uint32_t n,
+														uint32_t rep0, uint64_t seed) {
+	const uint64_t per = (uint64_t)n * (n - 1) / 2;
+	uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= per) return;
+	const uint32_t rep = blockIdx.y;
+	uint32_t i;
+	{ // unrank t -> (i, j), i < j: rows have n-1, n-2, ... entries; a short search from an estimate
+		const double w = 2.0 * n - 1;
+		const double est = (w - sqrt(w * w - 8.0 * (double)t)) / 2.0;
+		i = est > 0 ? (uint32_t)est : 0;
+		if (i > n - 2) i = n - 2;
+		while (i > 0 && tri_start(i, n) > t) --i;
+		while (i + 2 < n && tri_start(i + 1, n) <= t) ++i;
+	}
+	const uint32_t j = i + 1 + (uint32_t)(t - tri_start(i, n));
+	uint32_t sums[16];
+	for (int q = 0; q < 4; ++q) {
+		const uint4 v = S[t * 4 + q];
+		sums[4 * q] = v.x, sums[4 * q + 1] = v.y, sums[4 * q + 2] = v.z, sums[4 * q + 3] = v.w;
+	}
+	uint32_t draw[16];
+	bootstrap_draw(seed, (uint64_t)rep0 + rep, (uint64_t)i * n + j, sums, draw);
+	andi_hip_model m;
+	for (int c = 0; c < 16; ++c) m.counts[c] = draw[c] + draw[c]; // model_average of the replicate's (i, j) and (j, i)
+	m.seq_len = 0;                                                // (no estimator reads it)
+	D[(size_t)rep * n * n + (size_t)i * n + j] = andi_estimate_portable(&m, MODEL);
+}
+
 } // namespace
 
-hipError_t andi_launch_bootstrap(const andi_hip_model *M_dev, andi_hip_model *B_dev, uint32_t n,
+hipError_t andi_launch_bootstrap(const andi_hip_model *M_dev, andi_hip_model *B_dev, uint32_t n, uint32_t first,
 								 uint32_t replicates, uint64_t seed, hipStream_t st) {
 	const uint64_t items = (uint64_t)n * (n + 1) / 2 * replicates;
 	if (items == 0) return hipSuccess;
-	k_bootstrap<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(M_dev, B_dev, n, replicates, seed);
+	k_bootstrap<<<(unsigned)((items + 255) / 256), 256, 0, st>>>(M_dev, B_dev, n, first, replicates, seed);
+	return hipGetLastError();
+}
+
+hipError_t andi_launch_pair_sums(const andi_hip_model *M_dev, uint32_t *S_dev, uint32_t n, hipStream_t st) {
+	if (n < 2) return hipSuccess;
+	k_pair_sums<<<dim3((unsigned)(((uint64_t)(n - 1) * 16 + 255) / 256), n - 1), 256, 0, st>>>(M_dev, S_dev, n);
+	return hipGetLastError();
+}
+
+hipError_t andi_launch_bootstrap_dist(const uint32_t *S_dev, double *D_dev, uint32_t n, int model, uint32_t first,
+									  uint32_t group, uint64_t seed, hipStream_t st) {
+	const uint64_t per = (uint64_t)n * (n - 1) / 2;
+	if (per == 0 || group == 0) return hipSuccess;
+	const dim3 grid((unsigned)((per + 255) / 256), group);
+	const uint4 *S = (const uint4 *)S_dev;
+	switch (model) {
+		case ANDI_M_RAW: k_bootstrap_dist<ANDI_M_RAW><<<grid, 256, 0, st>>>(S, D_dev, n, first, seed); break;
+		case ANDI_M_JC: k_bootstrap_dist<ANDI_M_JC><<<grid, 256, 0, st>>>(S, D_dev, n, first, seed); break;
+		case ANDI_M_KIMURA: k_bootstrap_dist<ANDI_M_KIMURA><<<grid, 256, 0, st>>>(S, D_dev, n, first, seed); break;
+		case ANDI_M_LOGDET: k_bootstrap_dist<ANDI_M_LOGDET><<<grid, 256, 0, st>>>(S, D_dev, n, first, seed); break;
+		case ANDI_M_ANI: k_bootstrap_dist<ANDI_M_ANI><<<grid, 256, 0, st>>>(S, D_dev, n, first, seed); break;
+		default: return hipErrorInvalidValue;
+	}
 	return hipGetLastError();
 }

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "bootstrap.h"
 
 static_assert(sizeof(andi_hip_nj_join) == 40, "andi_hip_nj_join: 3 ids, pad, 3 lengths");
 
@@ -296,7 +297,9 @@ hipError_t nj_alloc(NjBuffers &b, size_t n, size_t g) {
 	return e;
 }
 
-// Neighbor-joining of g matrices (host, one after the other) in buffers for at least g: bad[k] receives replicate k's
+// Neighbor-joining of g matrices (host, one after the other; D == nullptr: their upper triangles are in b.D already, left
+// there by kernels on the context's stream) in buffers for at least g; D_out, if given, receives the g matrices as
+// k_nj_init leaves them (mirrored, diagonal +0.0), copied before the first join step: bad[k] receives replicate k's
 // first non-finite entry (i * n + j) or NOT_BAD, joins the records of all g when at least one matrix is usable -- and
 // nothing when none is.  A bad replicate among good ones is NOT kept out of the step kernels: better() and none() make
 // every pick a real pair of active slots whatever the values in D are (every index comes from the lists and the ids,
@@ -304,16 +307,17 @@ hipError_t nj_alloc(NjBuffers &b, size_t n, size_t g) {
 // throws away (andi_hip_nj_batch zeroes them).  Synchronous; the one host synchronisation before the steps is the read of
 // the bad words, none between steps.
 hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint32_t N, uint32_t g, andi_hip_nj_join *joins,
-					unsigned long long *bad) {
+					unsigned long long *bad, double *D_out = nullptr) {
 	const size_t n = N, nrec = n == 2 ? 1 : n - 2;
 	const uint32_t parts = (uint32_t)tiles_of(N);
 	hipStream_t st = ctx->stream;
-	hipError_t e = hipMemcpyAsync(b.D, D, g * n * n * sizeof(double), hipMemcpyHostToDevice, st);
+	hipError_t e = D ? hipMemcpyAsync(b.D, D, g * n * n * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
 	if (e == hipSuccess) e = hipMemsetAsync(b.bad, 0xff, g * sizeof *bad, st);
 	if (e == hipSuccess) {
 		k_nj_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.bad);
 		e = hipGetLastError();
 	}
+	if (e == hipSuccess && D_out) e = hipMemcpyAsync(D_out, b.D, g * n * n * sizeof(double), hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipMemcpyAsync(bad, b.bad, g * sizeof *bad, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
 	if (e != hipSuccess) return e;
@@ -337,6 +341,26 @@ hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint
 	}
 	if (e == hipSuccess) e = hipMemcpyAsync(joins, b.rec, g * nrec * sizeof *joins, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	return e;
+}
+
+// The buffers of andi_hip_nj_batch's group: as many replicates as GROUP_BYTES hold (at least one), as a grid's second
+// dimension takes, as there are; G receives the group's size.
+hipError_t nj_alloc_group(NjBuffers &b, size_t n, size_t count, size_t &G) {
+	G = GROUP_BYTES / replicate_bytes(n);
+	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
+	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing
+		const long long f = atoll(v);
+		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
+	}
+	if (G > count) G = count;
+	hipError_t e = nj_alloc(b, n, G);
+	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix andi_hip_nj needs too
+		nj_free(b);
+		(void)hipGetLastError();
+		G = (G + 1) / 2;
+		e = nj_alloc(b, n, G);
+	}
 	return e;
 }
 
@@ -372,22 +396,9 @@ int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const size_t nrec = n == 2 ? 1 : n - 2;
-	// the group: as many replicates as GROUP_BYTES hold (at least one), as a grid's second dimension takes, as there are
-	size_t G = GROUP_BYTES / replicate_bytes(n);
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing
-		const long long f = atoll(v);
-		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
-	}
-	if (G > count) G = count;
 	NjBuffers b;
-	hipError_t e = nj_alloc(b, n, G);
-	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix andi_hip_nj needs too
-		nj_free(b);
-		(void)hipGetLastError();
-		G = (G + 1) / 2;
-		e = nj_alloc(b, n, G);
-	}
+	size_t G = 0;
+	hipError_t e = nj_alloc_group(b, n, count, G);
 	std::vector<unsigned long long> hb(G);
 	for (size_t first = 0; e == hipSuccess && first < count; first += G) {
 		const size_t g = count - first < G ? count - first : G;
@@ -401,5 +412,50 @@ int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count
 	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
 	nj_free(b);
 	if (e != hipSuccess) return fail(ctx, "andi_hip_nj_batch", e);
+	return 0;
+}
+
+// Draw, estimate and join on the device (include/andi_hip.h): the summed counts of every pair once (k_pair_sums; M's
+// device copy goes before the groups' buffers come), then per group of replicates k_bootstrap_dist into the group's D
+// and andi_hip_nj_batch's steps on it.  No replicate exists as models, and none as doubles on the host unless D asks.
+int andi_hip_bootstrap_nj(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, int model, uint64_t seed, size_t first,
+						  size_t count, andi_hip_nj_join *joins, int64_t *bad, double *D) {
+	if (!ctx || !M || !joins || !bad || count == 0 || n < 2 || n > 65535 || model < 0 || model > 4 || first > 0xffffffffull ||
+		count > 0xffffffffull || first + count > 0xffffffffull) {
+		if (ctx)
+			ctx->err = "andi_hip_bootstrap_nj: bad arguments (ctx, M, joins and bad must be given, count >= 1, 2 <= n <= 65535, "
+					   "0 <= model <= 4, first + count < 2^32)";
+		return 1;
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const size_t nrec = n == 2 ? 1 : n - 2, pairs = n * (n - 1) / 2;
+	hipStream_t st = ctx->stream;
+	andi_hip_model *dM = nullptr;
+	uint32_t *S = nullptr;
+	hipError_t e = dmalloc(&S, pairs * 16);
+	if (e == hipSuccess) e = dmalloc(&dM, n * n);
+	if (e == hipSuccess) e = hipMemcpyAsync(dM, M, n * n * sizeof *M, hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = andi_launch_pair_sums(dM, S, (uint32_t)n, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	else (void)hipStreamSynchronize(st);
+	(void)andi_arena::dev_free(dM, false);
+	NjBuffers b;
+	size_t G = 0;
+	if (e == hipSuccess) e = nj_alloc_group(b, n, count, G);
+	std::vector<unsigned long long> hb(G);
+	for (size_t done = 0; e == hipSuccess && done < count; done += G) {
+		const size_t g = count - done < G ? count - done : G;
+		andi_hip_nj_join *J = joins + done * nrec;
+		e = andi_launch_bootstrap_dist(S, b.D, (uint32_t)n, model, (uint32_t)(first + done), (uint32_t)g, seed, st);
+		if (e == hipSuccess) e = nj_group(ctx, b, nullptr, (uint32_t)n, (uint32_t)g, J, hb.data(), D ? D + done * n * n : nullptr);
+		for (size_t k = 0; e == hipSuccess && k < g; ++k) {
+			bad[done + k] = hb[k] == NOT_BAD ? -1 : (int64_t)hb[k];
+			if (hb[k] != NOT_BAD) memset(J + k * nrec, 0, nrec * sizeof *J);
+		}
+	}
+	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
+	nj_free(b);
+	(void)andi_arena::dev_free(S, false);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_bootstrap_nj", e);
 	return 0;
 }

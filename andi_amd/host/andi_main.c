@@ -373,6 +373,11 @@ static void usage(int status) {
 		"                       each inner branch labelled with the number of those trees that have it\n"
 		"      --transfer=FILE  With -b: write the tree of the first matrix to FILE, each inner branch labelled with its\n"
 		"                       transfer bootstrap expectation (TBE, between 0 and 1) over the bootstrap matrices' trees\n"
+		"      --trees-only     With -b and at least one of --tree, --support, --consensus, --transfer: do not print the\n"
+		"                       bootstrap matrices; their trees are drawn, estimated and joined on the GPU, for any number\n"
+		"                       of replicates.  These trees come from the portable estimator (its own logarithm, within\n"
+		"                       an ulp of the C library's); in a rare tie they can differ from those of a run that\n"
+		"                       prints the matrices\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -539,110 +544,162 @@ static void put_consensus(FILE *f, const char *path, const andi_hip_cons_node *n
  * joined once whichever of the four files are asked for; all chunks' records are kept (40 bytes each) and go through one
  * andi_hip_nj_splits call behind the loop.
  * --transfer (tf): the point estimate's tree again, labelled with the transfer bootstrap expectation: per chunk one
- * andi_hip_nj_transfer call next to the support count's, on the same records; the chunks' sums add up. */
-static void write_support(FILE *f, const char *path, FILE *cf, const char *cpath, FILE *tf, const char *tpath, tree_out *t, andi_hip_ctx *ctx,
-						  const andi_hip_model *M, const andi_hip_model *B, unsigned long replicates, const genome *g, size_t n,
-						  int model, int truncate) {
-	const size_t nrec = n == 2 ? 1 : n - 2, nsup = n > 3 ? n - 3 : 1;
-	size_t chunk = ((size_t)1 << 30) / (n * n * sizeof(double)); /* at most 1 GiB of doubles at a time */
+ * andi_hip_nj_transfer call next to the support count's, on the same records; the chunks' sums add up.
+ *
+ * One state over the run: support_begin (the point estimate's tree), support_chunk for every chunk of replicates main
+ * draws -- as matrices B, or, under --trees-only, as nothing: andi_hip_bootstrap_nj draws, estimates and joins them on the
+ * device and the records are all that comes back -- and support_end (the files). */
+typedef struct {
+	FILE *f, *cf, *tf;
+	const char *path, *cpath, *tpath;
+	tree_out *t;
+	andi_hip_ctx *ctx;
+	const genome *g;
+	size_t n, nrec, nsup, cap; /* cap: the replicates of one andi_hip_nj_batch / andi_hip_bootstrap_nj call, at most */
+	unsigned long replicates, counted;
+	int model, truncate, trees_only;
+	uint64_t seed;
+	double *D;
+	andi_hip_nj_join *J, *Rall;
+	int64_t *bad;
+	uint8_t *skipall;
+	uint32_t *total, *part, *depth;
+	uint64_t *ttotal, *tpart;
+	int point_ok, trans_ok, cons_ok, stopped;
+} support_state;
+
+static void support_begin(support_state *s, FILE *f, const char *path, FILE *cf, const char *cpath, FILE *tf, const char *tpath, tree_out *t,
+						  andi_hip_ctx *ctx, const andi_hip_model *M, unsigned long replicates, const genome *g, size_t n, int model,
+						  int truncate, int trees_only, uint64_t seed) {
+	memset(s, 0, sizeof *s);
+	s->f = f, s->path = path, s->cf = cf, s->cpath = cpath, s->tf = tf, s->tpath = tpath, s->t = t, s->ctx = ctx, s->g = g, s->n = n;
+	s->replicates = replicates, s->model = model, s->truncate = truncate, s->trees_only = trees_only, s->seed = seed;
+	const size_t nrec = s->nrec = n == 2 ? 1 : n - 2, nsup = s->nsup = n > 3 ? n - 3 : 1;
+	/* at most 1 GiB at a time: of doubles, or -- the replicates never being matrices -- of the records kept on the host */
+	size_t chunk = ((size_t)1 << 30) / (trees_only ? nrec * sizeof(andi_hip_nj_join) : n * n * sizeof(double));
 	chunk = chunk < 1 ? 1 : chunk > replicates ? replicates : chunk;
+	s->cap = chunk;
 	const size_t kept = cf ? replicates : chunk; /* the replicates whose records and skip flags stay */
-	double *D = malloc(chunk * n * n * sizeof *D);
-	andi_hip_nj_join *J = malloc(nrec * sizeof *J), *Rall = malloc(kept * nrec * sizeof *Rall);
-	int64_t *bad = malloc(chunk * sizeof *bad);
-	uint8_t *skipall = malloc(kept);
-	uint32_t *total = calloc(nsup, sizeof *total), *part = calloc(nsup, sizeof *part), *depth = calloc(nsup, sizeof *depth);
-	uint64_t *ttotal = calloc(nsup, sizeof *ttotal), *tpart = calloc(nsup, sizeof *tpart);
-	if (!D || !J || !Rall || !bad || !skipall || !total || !part || !depth || !ttotal || !tpart ||
+	double *D = s->D = malloc((trees_only ? 1 : chunk) * n * n * sizeof *D);
+	s->J = malloc(nrec * sizeof *s->J), s->Rall = malloc(kept * nrec * sizeof *s->Rall);
+	s->bad = malloc(chunk * sizeof *s->bad);
+	s->skipall = malloc(kept);
+	s->total = calloc(nsup, sizeof *s->total), s->part = calloc(nsup, sizeof *s->part), s->depth = calloc(nsup, sizeof *s->depth);
+	s->ttotal = calloc(nsup, sizeof *s->ttotal), s->tpart = calloc(nsup, sizeof *s->tpart);
+	if (!D || !s->J || !s->Rall || !s->bad || !s->skipall || !s->total || !s->part || !s->depth || !s->ttotal || !s->tpart ||
 		((f || tf) && andi_hip_distances(M, n, model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
-	int point_ok = f != NULL, trans_ok = tf != NULL, cons_ok = cf != NULL;
-	for (size_t i = 0; i < n && (point_ok || trans_ok); i++)
+	s->point_ok = f != NULL, s->trans_ok = tf != NULL, s->cons_ok = cf != NULL;
+	for (size_t i = 0; i < n && (s->point_ok || s->trans_ok); i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
 				if (f) soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
 				if (tf) soft_warnx("No transfer support: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
-				point_ok = trans_ok = 0;
+				s->point_ok = s->trans_ok = 0;
 				break;
 			}
-	if ((point_ok || trans_ok) && andi_hip_nj(ctx, D, n, J)) {
+	if ((s->point_ok || s->trans_ok) && andi_hip_nj(ctx, D, n, s->J)) {
 		if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
 		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
-		point_ok = trans_ok = 0;
+		s->point_ok = s->trans_ok = 0;
 	}
-	unsigned long counted = 0;
-	for (unsigned long first = 0; first < replicates; first += chunk) {
-		const size_t c = replicates - first < chunk ? replicates - first : chunk;
-		andi_hip_nj_join *R = cf ? Rall + first * nrec : Rall;
-		uint8_t *skip = cf ? skipall + first : skipall;
-		for (size_t k = 0; k < c; k++)
-			if (andi_hip_distances(B + (first + k) * n * n, n, model, D + k * n * n))
-				err(errno, "Could not allocate enough memory for the support values.");
-		if (andi_hip_nj_batch(ctx, D, n, c, R, bad)) {
-			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-			if (cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
-			if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
-			point_ok = cons_ok = trans_ok = 0;
+}
+
+/* replicates start ... start + count - 1: their matrices B (count * n * n models), or NULL under --trees-only */
+static void support_chunk(support_state *s, unsigned long start, size_t count, const andi_hip_model *B, const andi_hip_model *M) {
+	const size_t n = s->n, nrec = s->nrec;
+	const genome *g = s->g;
+	andi_hip_ctx *ctx = s->ctx;
+	for (unsigned long first = start; first < start + count && !s->stopped; first += s->cap) {
+		const size_t c = start + count - first < s->cap ? start + count - first : s->cap;
+		andi_hip_nj_join *R = s->cf ? s->Rall + first * nrec : s->Rall;
+		uint8_t *skip = s->cf ? s->skipall + first : s->skipall;
+		int failed;
+		if (s->trees_only) {
+			failed = andi_hip_bootstrap_nj(ctx, M, n, s->model, s->seed, first, c, R, s->bad, NULL);
+		} else {
+			for (size_t k = 0; k < c; k++)
+				if (andi_hip_distances(B + (first - start + k) * n * n, n, s->model, s->D + k * n * n))
+					err(errno, "Could not allocate enough memory for the support values.");
+			failed = andi_hip_nj_batch(ctx, s->D, n, c, R, s->bad);
+		}
+		if (failed) {
+			if (s->f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+			if (s->cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
+			if (s->tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+			if (!s->f && !s->cf && !s->tf) soft_warnx("No trees: %s", andi_hip_last_error(ctx));
+			s->point_ok = s->cons_ok = s->trans_ok = 0;
+			s->stopped = 1;
 			break;
 		}
 		for (size_t k = 0; k < c; k++) {
-			skip[k] = bad[k] >= 0;
+			skip[k] = s->bad[k] >= 0;
 			if (skip[k])
 				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s' is not finite.", first + (unsigned long)k + 2,
-						   g[bad[k] / (int64_t)n].name, g[bad[k] % (int64_t)n].name);
-			else if (t->f) put_tree(t->f, t->path, R + k * nrec, NULL, g, n, truncate);
-			counted += !skip[k];
+						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name);
+			else if (s->t->f) put_tree(s->t->f, s->t->path, R + k * nrec, NULL, g, n, s->truncate);
+			s->counted += !skip[k];
 		}
 		/* (whatever fails below, the replicates' lines of --tree are still written) */
-		if (point_ok) {
-			if (andi_hip_nj_support(ctx, J, R, n, c, skip, part)) {
+		if (s->point_ok) {
+			if (andi_hip_nj_support(ctx, s->J, R, n, c, skip, s->part)) {
 				soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-				point_ok = 0;
+				s->point_ok = 0;
 			} else
-				for (size_t s = 0; s + 3 < n; s++) total[s] += part[s];
+				for (size_t k = 0; k + 3 < n; k++) s->total[k] += s->part[k];
 		}
-		if (trans_ok) {
-			if (andi_hip_nj_transfer(ctx, J, R, n, c, skip, depth, tpart, NULL)) {
+		if (s->trans_ok) {
+			if (andi_hip_nj_transfer(ctx, s->J, R, n, c, skip, s->depth, s->tpart, NULL)) {
 				soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
-				trans_ok = 0;
+				s->trans_ok = 0;
 			} else
-				for (size_t s = 0; s + 3 < n; s++) ttotal[s] += tpart[s];
+				for (size_t k = 0; k + 3 < n; k++) s->ttotal[k] += s->tpart[k];
 		}
 	}
-	if (point_ok) {
+}
+
+/* the files; complete = 0: the replicates were not all drawn, nothing is written */
+static void support_end(support_state *s, int complete) {
+	const size_t n = s->n;
+	const genome *g = s->g;
+	andi_hip_ctx *ctx = s->ctx;
+	const unsigned long counted = s->counted, replicates = s->replicates;
+	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = 0;
+	if (s->point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_tree(f, path, J, total, g, n, truncate);
+		put_tree(s->f, s->path, s->J, s->total, g, n, s->truncate);
 	}
-	if (trans_ok && counted == 0) {
+	if (s->trans_ok && counted == 0) {
 		soft_warnx("No transfer support: no bootstrap matrix has a tree.");
-		trans_ok = 0;
+		s->trans_ok = 0;
 	}
-	if (trans_ok) {
+	if (s->trans_ok) {
 		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_transfer_tree(tf, tpath, J, depth, ttotal, counted, g, n, truncate);
+		put_transfer_tree(s->tf, s->tpath, s->J, s->depth, s->ttotal, counted, g, n, s->truncate);
 	}
-	if (cons_ok && counted == 0) {
+	if (s->cons_ok && counted == 0) {
 		soft_warnx("No consensus tree: no bootstrap matrix has a tree.");
-		cons_ok = 0;
+		s->cons_ok = 0;
 	}
-	if (cons_ok) {
-		uint32_t *ids = malloc(replicates * nsup * sizeof *ids), *freq = NULL;
+	if (s->cons_ok) {
+		uint32_t *ids = malloc(replicates * s->nsup * sizeof *ids), *freq = NULL;
 		uint64_t *sets = NULL;
 		size_t nsplits = 0, ninner = 0;
 		andi_hip_cons_node *nodes = malloc((2 * n - 1) * sizeof *nodes);
 		if (!ids || !nodes) err(errno, "Could not allocate enough memory for the consensus tree.");
-		if (andi_hip_nj_splits(ctx, Rall, n, replicates, skipall, ids, &nsplits, &freq, &sets)) {
+		if (andi_hip_nj_splits(ctx, s->Rall, n, replicates, s->skipall, ids, &nsplits, &freq, &sets)) {
 			soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
-		} else if (andi_hip_consensus(Rall, n, replicates, skipall, ids, nsplits, freq, sets, nodes, &ninner)) {
+		} else if (andi_hip_consensus(s->Rall, n, replicates, s->skipall, ids, nsplits, freq, sets, nodes, &ninner)) {
 			soft_warnx("No consensus tree: the bootstrap matrices' trees are inconsistent.");
 		} else {
 			if (counted < replicates) soft_warnx("Consensus tree from %lu of %lu bootstrap matrices.", counted, replicates);
-			put_consensus(cf, cpath, nodes, ninner, g, n, truncate);
+			put_consensus(s->cf, s->cpath, nodes, ninner, g, n, s->truncate);
 		}
 		andi_hip_free(freq), andi_hip_free(sets);
 		free(ids), free(nodes);
 	}
-	free(D), free(J), free(Rall), free(bad), free(skipall), free(total), free(part), free(depth), free(ttotal), free(tpart);
+	free(s->D), free(s->J), free(s->Rall), free(s->bad), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
+		free(s->tpart);
 }
 
 /* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
@@ -722,6 +779,7 @@ int main(int argc, char *argv[]) {
 												 {"support", required_argument, NULL, 0},
 												 {"consensus", required_argument, NULL, 0},
 												 {"transfer", required_argument, NULL, 0},
+												 {"trees-only", no_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -748,7 +806,7 @@ int main(int argc, char *argv[]) {
 	size_t nfiles = 0, files_cap = 0;
 	char **ref_files = NULL; /* --reference, --reference-list: the query-versus-reference mode */
 	size_t nref_files = 0, ref_cap = 0;
-	int rect = 0, bootstrap_given = 0;
+	int rect = 0, bootstrap_given = 0, trees_only = 0;
 	tree_out tree = {0};
 	const char *support_path = NULL; /* --support */
 	FILE *support_f = NULL;
@@ -771,6 +829,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "support")) support_path = optarg;
 				if (!strcmp(o, "consensus")) consensus_path = optarg;
 				if (!strcmp(o, "transfer")) transfer_path = optarg;
+				if (!strcmp(o, "trees-only")) trees_only = 1;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
 				if (!strcmp(o, "reference")) {
 					rect = 1;
@@ -864,6 +923,9 @@ int main(int argc, char *argv[]) {
 	if (consensus_path && !bootstrap) errx(1, "A consensus tree (--consensus) needs bootstrap matrices: give -b N with N of at least 2.");
 	if (rect && transfer_path) errx(1, "Transfer support (--transfer) is not available together with --reference or --reference-list.");
 	if (transfer_path && !bootstrap) errx(1, "Transfer support (--transfer) needs bootstrap matrices: give -b N with N of at least 2.");
+	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
+	if (trees_only && !tree.path && !support_path && !consensus_path && !transfer_path)
+		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
 	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
 	if (support_path && !(support_f = fopen(support_path, "w"))) err(1, "%s", support_path);
 	if (consensus_path && !(consensus_f = fopen(consensus_path, "w"))) err(1, "%s", consensus_path);
@@ -947,21 +1009,42 @@ int main(int argc, char *argv[]) {
 	}
 	if (bootstrap) { /* calculate_bootstrap, src/process.c:289-321 */
 		andi_hip_ctx *ctx = NULL;
-		andi_hip_model *B = malloc(bootstrap * n * n * sizeof *B);
+		/* the replicates are drawn, printed and handed to the trees in chunks of at most 1 GiB of models (at least one
+		 * replicate): a draw depends on (seed, replicate, i, j) alone, so the output does not depend on the chunks.
+		 * ANDI_HIP_BOOT_CHUNK=k: chunks of k replicates (the tests').  Under --trees-only nothing is drawn here at all. */
+		size_t chunk = ((size_t)1 << 30) / (n * n * sizeof(andi_hip_model));
+		if (trees_only) chunk = bootstrap;
+		if (getenv("ANDI_HIP_BOOT_CHUNK") && strtoull(getenv("ANDI_HIP_BOOT_CHUNK"), NULL, 10) > 0)
+			chunk = strtoull(getenv("ANDI_HIP_BOOT_CHUNK"), NULL, 10);
+		chunk = chunk < 1 ? 1 : chunk > bootstrap ? bootstrap : chunk;
+		andi_hip_model *B = trees_only ? NULL : malloc(chunk * n * n * sizeof *B);
 		/* the reference seeds its generator from the clock; ANDI_HIP_SEED=k draws the same matrices on every run */
 		const uint64_t seed = getenv("ANDI_HIP_SEED") ? strtoull(getenv("ANDI_HIP_SEED"), NULL, 10) : (uint64_t)time(NULL);
-		if (!B || andi_hip_ctx_create(&ctx, opts.device, msg, sizeof msg) ||
-			andi_hip_bootstrap(ctx, M, n, seed, bootstrap, B)) {
-			soft_warnx("Bootstrapping failed.");
-		} else {
-			for (unsigned long b = 0; b < bootstrap; b++) {
-				print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
-				if (tree.f && !support_f && !consensus_f && !transfer_f) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)b + 2);
+		const int trees = support_f || consensus_f || transfer_f || trees_only;
+		support_state st;
+		int begun = 0, ok = 1;
+		if ((!trees_only && !B) || andi_hip_ctx_create(&ctx, opts.device, msg, sizeof msg)) ok = 0;
+		for (unsigned long first = 0; ok && first < bootstrap; first += chunk) {
+			const size_t c = bootstrap - first < chunk ? bootstrap - first : chunk;
+			if (!trees_only) {
+				if (andi_hip_bootstrap_range(ctx, M, n, seed, first, c, B)) {
+					ok = 0;
+					break;
+				}
+				for (size_t b = 0; b < c; b++) {
+					print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
+					if (tree.f && !trees) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)(first + b) + 2);
+				}
 			}
-			if (support_f || consensus_f || transfer_f)
-				write_support(support_f, support_path, consensus_f, consensus_path, transfer_f, transfer_path, &tree, ctx, M, B, bootstrap, all.v, n, opts.model,
-							  truncate);
+			if (!trees) continue;
+			if (!begun)
+				support_begin(&st, support_f, support_path, consensus_f, consensus_path, transfer_f, transfer_path, &tree, ctx, M, bootstrap,
+							  all.v, n, opts.model, truncate, trees_only, seed);
+			begun = 1;
+			support_chunk(&st, first, c, B, M);
 		}
+		if (!ok) soft_warnx("Bootstrapping failed.");
+		if (begun) support_end(&st, ok);
 		if (ctx) andi_hip_ctx_destroy(ctx);
 		free(B);
 	}

@@ -147,6 +147,9 @@ SYMBOLS = {
     "andi_hip_scan_rows": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64), C.c_size_t, _P, C.c_int,
                                      C.c_uint32, _P]),
     "andi_hip_bootstrap": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_size_t, _P]),
+    "andi_hip_bootstrap_range": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_size_t, C.c_size_t, _P]),
+    "andi_hip_bootstrap_nj": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "andi_hip_estimate_portable": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "andi_hip_dev_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "andi_hip_dev_free": (None, [_P, _P]),
     "andi_hip_copy_to_host": (C.c_int, [_P, _P, _P, C.c_size_t]),
@@ -675,6 +678,44 @@ def bootstrap(ctx: Context, M, replicates, seed=0):
     B = np.empty((replicates, n, n, 17), np.uint32)
     ctx._check(load().andi_hip_bootstrap(ctx._h, M.ctypes.data, n, seed, replicates, B.ctypes.data), "bootstrap")
     return B
+
+
+def bootstrap_range(ctx: Context, M, first, count, seed=0):
+    """Replicates first ... first + count - 1 of bootstrap's stream (andi_hip_bootstrap_range): (count, n, n, 17) uint32,
+    bit for bit bootstrap(ctx, M, first + count, seed)[first:]."""
+    M = np.ascontiguousarray(M, dtype=np.uint32)
+    n = M.shape[0]
+    assert M.shape == (n, n, 17)
+    B = np.empty((count, n, n, 17), np.uint32)
+    ctx._check(load().andi_hip_bootstrap_range(ctx._h, M.ctypes.data, n, seed, first, count, B.ctypes.data),
+               "bootstrap_range")
+    return B
+
+
+def estimate_portable(models, model=M_JC):
+    """The portable estimator (andi_hip_estimate_portable) of every model of `models` (..., 17) uint32: float64 of
+    shape models.shape[:-1].  The function the device computes in bootstrap_nj; no GPU is touched."""
+    m = np.ascontiguousarray(models, dtype=np.uint32)
+    assert m.ndim >= 1 and m.shape[-1] == 17
+    out = np.empty(m.shape[:-1], np.float64)
+    if load().andi_hip_estimate_portable(m.ctypes.data, out.size, model, out.ctypes.data):
+        raise AndiHipError("andi_hip_estimate_portable: bad arguments")
+    return out
+
+
+def bootstrap_nj(ctx: Context, M, count, model=M_JC, seed=0, first=0, distances=False):
+    """Draw, estimate and join on the device (andi_hip_bootstrap_nj): the trees of replicates first ... first + count - 1
+    of bootstrap's stream, as nj_batch's (J, bad) -- and, with distances=True, the (count, n, n) float64 matrices the
+    joins started from as a third value.  The replicates never exist as models."""
+    M = np.ascontiguousarray(M, dtype=np.uint32)
+    n = M.shape[0]
+    assert M.shape == (n, n, 17)
+    J = np.zeros((count, 1 if n == 2 else max(n - 2, 0)), NJ_JOIN)
+    bad = np.zeros(count, np.int64)
+    D = np.empty((count, n, n), np.float64) if distances else None
+    ctx._check(load().andi_hip_bootstrap_nj(ctx._h, M.ctypes.data, n, model, seed, first, count, J.ctypes.data,
+                                            bad.ctypes.data, D.ctypes.data if distances else None), "bootstrap_nj")
+    return (J, bad, D) if distances else (J, bad)
 
 
 def nj(ctx: Context, D):

@@ -19,7 +19,8 @@
  * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well); and bootstrap support on that
  * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only); and the majority-rule
  * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only);
- * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only).
+ * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only); and bootstrap
+ * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -344,6 +345,37 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects,
 int andi_hip_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uint64_t seed,
 					   size_t replicates, andi_hip_model *B);
 
+/* Replicates first ... first + count - 1 of the stream andi_hip_bootstrap draws, into B (host, count*n*n): bit for bit
+ * B[first : first + count] of a call of andi_hip_bootstrap for first + count replicates, so a caller can work in pieces
+ * that fit.  andi_hip_bootstrap is the range from 0.  first + count must be below 2^32; that, a NULL pointer or n outside
+ * 1 ... 65535 fail with 1 before any HIP call; count == 0 does nothing. */
+int andi_hip_bootstrap_range(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, uint64_t seed, size_t first,
+							 size_t count, andi_hip_model *B);
+
+/* The PORTABLE estimator: out[k] = the portable estimate of m[k], k < count.  No GPU is touched; returns 1 on a NULL
+ * pointer (with count > 0) or a model outside 0 ... 4.  It is, operation for operation, andi_hip_estimate -- the same
+ * sums, divisions, term order of LogDet's determinant, nucl <= 3 -> NaN, d <= 0.0 ? 0.0 : d -- with every operation an
+ * IEEE double operation rounded on its own (no a*b+c contracted into an FMA) and libm's log replaced by andi_log, which
+ * is made of + - * /, comparisons and moves of bits only.  The device computes the same function from the same text
+ * (andi_amd/csrc/andi_estimate.h), so andi_hip_bootstrap_nj's distances equal this function's bit for bit; RAW and ANI
+ * take no logarithm and equal andi_hip_estimate bit for bit; the others differ from it by what andi_log differs from the
+ * host's log (at most 1 ulp of the logarithm measured against glibc; DESIGN.md 10.6 has the distances' figures).
+ *
+ * andi_log(x), the contract (tests/estimate_model.py restates it in NumPy):
+ *  - x is NaN or x < 0: the quiet NaN 0x7ff8000000000000; x == 0.0 (either sign): -inf; x == +inf: +inf;
+ *  - k = 0; a subnormal x (exponent field 0) is first multiplied by 2^54 (exact) and k = -54;
+ *  - k += (exponent field of x) - 1023; m = x with its exponent field set to 1023, in [1, 2);
+ *    if m > 1.4142135623730951 (0x3ff6a09e667f3bcd): m = m * 0.5, k += 1;
+ *  - f = m - 1.0 (exact); s = f / (2.0 + f); z = s * s;
+ *  - p = 0.0; for i = 27, 25, ..., 3: p = p * z + 1.0 / i   (thirteen steps; 1.0 / i is the rounded quotient);
+ *  - hfsq = (0.5 * f) * f; R = (2.0 * z) * p; t = s * (hfsq + R);
+ *  - k == 0: the result is f - (hfsq - t);
+ *  - otherwise, dk = (double)k, ln2_hi = 6.93147180369123816490e-01 (0x3fe62e42fee00000), ln2_lo =
+ *    1.90821492927058770002e-10 (0x3dea39ef35793c76): the result is dk * ln2_hi - ((hfsq - (t + dk * ln2_lo)) - f);
+ *  every operation rounded to double, in the order the parentheses give.  (x = 2^k m, log m = 2 atanh(s) = 2s + 2s z
+ *  (1/3 + z/5 + ... + z^12/27), in fdlibm's arrangement.) */
+int andi_hip_estimate_portable(const andi_hip_model *m, size_t count, int model, double *out);
+
 /* Neighbor-joining (Saitou & Nei 1987, as PHYLIP's neighbor) of the n x n distance matrix D (host memory, row-major) on
  * the context's device.  Only D[i][j] with i < j is read; those entries are mirrored, the diagonal and the lower
  * triangle are ignored.  Writes n - 2 records for n >= 3 -- n - 3 pair joins, then the final three -- and one for n = 2.
@@ -375,6 +407,25 @@ int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *
  * count * n * n * 8 bytes do not fit the device (or count > 65535) the matrices are taken in groups; the results do not
  * depend on the grouping, and the call does not fail on size while one matrix fits.  Synchronous. */
 int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, andi_hip_nj_join *joins, int64_t *bad);
+/* Bootstrap trees without matrices: draw, estimate and join on the device.  For k < count, replicate first + k of the
+ * stream andi_hip_bootstrap draws from M (host, n*n) is turned into distances and joined; joins (count * nrec records)
+ * and bad (count) are those of andi_hip_nj_batch.  No replicate exists as models anywhere, nor as doubles on the host
+ * unless D is given.  The contract, for replicate first + k and every pair i < j:
+ *  - the sixteen counts are those andi_hip_bootstrap_range draws for that replicate and pair;
+ *  - the distance is the portable estimate (andi_hip_estimate_portable) of the model whose counts[c] is
+ *    (uint32_t)(draw[c] + draw[c]) -- what andi_hip_model_average makes of the mirrored replicate, which is what
+ *    andi_hip_distances sees; seq_len enters no estimator;
+ *  - the records are what andi_hip_nj_batch writes for those matrices, bit for bit; a replicate with a non-finite distance
+ *    gets bad[k] = i*n + j of the first one and all-zero records, and the others are not affected;
+ *  - D, if not NULL, receives the count matrices (n x n, mirrored, diagonal +0.0) as the joins start from them, copied
+ *    out before the first join step; it costs a copy only when asked for.
+ * model is 0 ... 4 (ANDI_M_*).  A NULL ctx, M, joins or bad, count == 0, n outside 2 ... 65535, a model outside 0 ... 4 or
+ * first + count of 2^32 or more fail with 1 before any HIP call.  On the device: the summed counts of every pair, 64
+ * bytes each (n(n-1)/2 of them), and a group of replicates sized as andi_hip_nj_batch's; the results depend neither on the
+ * grouping nor on how a range is split over calls, and the call does not fail on size while one replicate fits.
+ * Synchronous. */
+int andi_hip_bootstrap_nj(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, int model, uint64_t seed, size_t first,
+						  size_t count, andi_hip_nj_join *joins, int64_t *bad, double *D);
 /* Bootstrap support of the branches of `tree` (n - 2 records) among the `count` replicate trees `reps` (count * (n - 2)
  * records, replicate k's from reps + k*(n - 2) on).  Pair record s of a tree, 0 <= s < n - 3, defines the bipartition
  * {L, leaves \ L} with L the leaves below node n + s; an unrooted binary tree has exactly these n - 3 non-trivial
