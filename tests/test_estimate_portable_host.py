@@ -52,6 +52,24 @@ def test_sample_covers_the_edges(sample):
     assert (c.max(axis=1) >= 10 ** 8).sum() >= 1000                            # counts of 10^8
 
 
+def test_edge_matrix_reaches_the_edges_under_the_oracles_draw(orc):
+    """the design of tests/test_bootstrap_edges_gpu.py, verified without a GPU: forty replicates of edge_matrix drawn by
+    the oracle -- another generator, the same multinomial law -- meet every coverage condition the GPU test asserts on the
+    device's draw, and the host's estimate of them is the NumPy model bit for bit"""
+    from andi_amd import lib
+    M = em.edge_matrix(20240917)
+    assert M.shape == (em.EDGE_N, em.EDGE_N, 17) and M.dtype == np.uint32
+    summed = M[..., :16].astype(np.uint64) + M.transpose(1, 0, 2)[..., :16]
+    assert summed.max() < 2 ** 31
+    B = orc.bootstrap(M, em.EDGE_REPS, seed=20240917)
+    fig = em.edge_coverage(B)
+    print(fig)
+    iu = np.triu_indices(em.EDGE_N, 1)
+    m = em.doubled(B[:, iu[0], iu[1]])
+    for model in range(5):
+        assert em.same_bits(lib.estimate_portable(m, model), em.estimate_portable(m, model)).all(), model
+
+
 @pytest.mark.parametrize("model", range(5))
 def test_portable_estimate_is_the_numpy_model_bit_for_bit(sample, model):
     from andi_amd import lib
