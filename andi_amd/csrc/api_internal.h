@@ -1,5 +1,6 @@
-// api_internal.h — what the library's host translation units share (api.hip, scan_call.hip, seam.hip): the objects
-// behind the C-ABI's handles, the error helpers, and the helpers the scan call and the seam take from api.hip.
+// api_internal.h — what the library's host translation units share (api.hip, scan_call.hip, seam.hip, nj.hip and the
+// calls on nj_sets.h): the objects behind the C-ABI's handles, the error helpers, the scope of a call's device buffers
+// (DevScope), the size of a group of replicates (nj_group_size), and the helpers the scan call and the seam take from api.hip.
 // Private: no kernel code, nothing of it is exported (the functions declared here are hidden).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -151,6 +152,37 @@ int fail(andi_hip_ctx *ctx, const char *what, hipError_t e) {
 template <typename T>
 hipError_t dmalloc(T **p, size_t count) {
 	return andi_arena::dev_malloc((void **)p, count * sizeof(T)); // (out of large chunks: dev_arena.h)
+}
+
+// The device buffers of one call.  alloc() is dmalloc() that remembers what it handed out and does nothing once an
+// allocation has failed (err keeps the first failure, so a run of allocs is checked once, behind it).  The scope's end
+// waits for the stream -- nothing in flight uses the buffers then, also on an error exit -- and gives them all back.
+struct DevScope {
+	hipStream_t stream;
+	hipError_t err = hipSuccess;
+	std::vector<void *> held;
+	explicit DevScope(hipStream_t st) : stream(st) {}
+	template <typename T>
+	void alloc(T **p, size_t count) {
+		if (err == hipSuccess && (err = dmalloc(p, count)) == hipSuccess) held.push_back(*p);
+	}
+	~DevScope() {
+		(void)hipStreamSynchronize(stream);
+		for (void *p : held) (void)andi_arena::dev_free(p, false);
+	}
+	DevScope(const DevScope &) = delete;
+	DevScope &operator=(const DevScope &) = delete;
+};
+
+// The replicates of one group, for every call that takes replicates as its grids' second dimension (nj.hip, nj_sets.h):
+// as many as `budget` bytes of device memory hold at `each` bytes per replicate -- at least one, at most what that
+// dimension takes.  Test hook ANDI_NJ_GROUP: a size of the test's choosing, within the same bounds.
+size_t nj_group_size(size_t budget, size_t each) {
+	constexpr size_t MAX_GROUP = 65535;
+	size_t G = budget / each;
+	if (const char *v = andi_knob(KNOB_NJ_GROUP))
+		if (atoll(v) >= 1) G = (size_t)atoll(v);
+	return G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
 }
 
 void resolve_events(andi_hip_ctx *ctx) {

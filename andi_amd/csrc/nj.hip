@@ -260,7 +260,6 @@ uint64_t tiles_of(uint32_t r) {
 }
 
 constexpr unsigned long long NOT_BAD = ~0ull;
-constexpr size_t MAX_GROUP = 65535;             // a grid's second dimension
 constexpr size_t GROUP_BYTES = (size_t)4 << 30; // andi_hip_nj_batch: device memory of a group of replicates, at most (one always fits)
 
 // device bytes of one replicate: D, R, the lists, the tile results, the records, the bad word
@@ -344,15 +343,10 @@ hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint
 	return e;
 }
 
-// The buffers of andi_hip_nj_batch's group: as many replicates as GROUP_BYTES hold (at least one), as a grid's second
-// dimension takes, as there are; G receives the group's size.
+// The buffers of andi_hip_nj_batch's group: as many replicates as GROUP_BYTES hold (nj_group_size, api_internal.h), as
+// there are; G receives the group's size.
 hipError_t nj_alloc_group(NjBuffers &b, size_t n, size_t count, size_t &G) {
-	G = GROUP_BYTES / replicate_bytes(n);
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing
-		const long long f = atoll(v);
-		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
-	}
+	G = nj_group_size(GROUP_BYTES, replicate_bytes(n));
 	if (G > count) G = count;
 	hipError_t e = nj_alloc(b, n, G);
 	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix andi_hip_nj needs too

@@ -1,6 +1,6 @@
-// nj_sets.h — the leaf sets of neighbor-joining trees on the device, shared by nj_support.hip (andi_hip_nj_support) and
-// nj_splits.hip (andi_hip_nj_splits): the host's validation of the records, the kernels that build a tree's sets and hash
-// them, and the canonical side of a set.  Private; every translation unit that includes it gets its own copy of the
+// nj_sets.h — the leaf sets of neighbor-joining trees on the device, and the one driver of the three calls that work on
+// the sets of a bootstrap's replicate trees: andi_hip_nj_support (nj_support.hip), andi_hip_nj_transfer (nj_transfer.hip)
+// and andi_hip_nj_splits (nj_splits.hip).  Private; every translation unit that includes it gets its own copy of the
 // kernels (they are small), but there is one source.
 //
 // A tree's leaf sets are bitsets of W = ceil(n / 64) words, set s below node n + s:
@@ -9,13 +9,28 @@
 //            barrier and no recursion: a caterpillar 65535 deep is a loop of 65532 trips);
 //   k_hash   one wavefront per set: a 64-bit hash of the set on its canonical side -- the side without leaf 0, so a set
 //            that holds leaf 0 counts as its complement.  The sets in memory stay as built; the side is taken on the fly.
+//
+// The driver, in the order a call uses it:
+//   sets_prepare     on the host, before any HIP call: the records are validated (records_ok: every child a leaf or an
+//                    earlier record's node, every node a child exactly once) -- the point tree's first, if the call has
+//                    one, then those of the replicates that skip leaves in, in ascending order -- and only the two
+//                    children of every pair record are kept for the device; and the group's size is fixed: the used
+//                    replicates are taken SETS_GROUP_BYTES of device memory at a time (nj_group_size, api_internal.h;
+//                    one tree's sets are 537 MB at 65535 leaves, and one tree always fits);
+//   sets_for_groups  per group: its children go up, k_sets builds its sets, and the call's own body launches what it
+//                    does with them.  The groups follow one another on the context's stream; nothing waits for the host.
+// What differs between the three calls stays in their files: the bytes a set costs beside its words, whether there is a
+// point tree, the body, and what a call does when every replicate is skipped.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
+#include <string>
+#include <vector>
 
-#include "andi_hip.h"
+#include "api_internal.h"
 
 namespace {
 
@@ -80,6 +95,59 @@ inline bool records_ok(const andi_hip_nj_join *J, size_t n, uint8_t *seen, int2 
 		if (s < pairs) kids[s] = make_int2(ch[0], ch[1]);
 	}
 	return true; // (2 * pairs + 3 = n + pairs children, none twice: every node once)
+}
+
+constexpr size_t SETS_GROUP_BYTES = (size_t)2 << 30; // device memory of a group of replicates' sets, at most
+
+// what sets_prepare leaves of a call's arguments
+struct SetsPlan {
+	size_t nsets, W, G;            // sets per tree, words per set, replicates per group (1 <= G <= max(used.size(), 1))
+	std::vector<size_t> used;      // the replicates that count, ascending
+	std::vector<int2> kids, tkids; // their pair records' children, in used's order; the point tree's, if there is one
+};
+
+// n >= 4; tree may be null (no point tree); set_bytes: the device bytes one set costs the caller beside its W words.
+// false: some records are not andi_hip_nj's, and ctx->err says whose, in fn's name.
+inline bool sets_prepare(andi_hip_ctx *ctx, const char *fn, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps,
+						 size_t n, size_t count, const uint8_t *skip, size_t set_bytes, SetsPlan &p) {
+	const size_t nsets = p.nsets = n - 3, nrec = n - 2, W = p.W = (n + 63) / 64;
+	std::vector<uint8_t> seen(2 * n);
+	if (tree) {
+		p.tkids.resize(nsets);
+		if (!records_ok(tree, n, seen.data(), p.tkids.data())) {
+			ctx->err = std::string(fn) + ": the tree's records are not those of andi_hip_nj";
+			return false;
+		}
+	}
+	for (size_t k = 0; k < count; ++k)
+		if (!skip || !skip[k]) p.used.push_back(k);
+	p.kids.resize(p.used.size() * nsets);
+	for (size_t u = 0; u < p.used.size(); ++u)
+		if (!records_ok(reps + p.used[u] * nrec, n, seen.data(), p.kids.data() + u * nsets)) {
+			char msg[160];
+			snprintf(msg, sizeof msg, "%s: the records of replicate %zu are not those of andi_hip_nj", fn, p.used[u]);
+			ctx->err = msg;
+			return false;
+		}
+	p.G = nj_group_size(SETS_GROUP_BYTES, nsets * (W * sizeof(uint64_t) + set_bytes));
+	if (p.G > p.used.size()) p.G = p.used.empty() ? 1 : p.used.size();
+	return true;
+}
+
+// The used replicates, p.G at a time: the children of the group that starts at used[first] go to dkids (room for p.G
+// trees), k_sets builds the g trees' sets in rsets (room for p.G trees' too), then body(first, g) launches the caller's
+// kernels on them and returns their status.  Ends at the first HIP error and returns it.
+template <typename Body>
+hipError_t sets_for_groups(const SetsPlan &p, size_t n, int2 *dkids, uint64_t *rsets, hipStream_t st, Body body) {
+	hipError_t e = hipSuccess;
+	for (size_t first = 0; e == hipSuccess && first < p.used.size(); first += p.G) {
+		const uint32_t g = (uint32_t)(p.used.size() - first < p.G ? p.used.size() - first : p.G);
+		e = hipMemcpyAsync(dkids, p.kids.data() + first * p.nsets, (size_t)g * p.nsets * sizeof(int2), hipMemcpyHostToDevice, st);
+		if (e != hipSuccess) break;
+		k_sets<<<dim3(((uint32_t)p.W + 63) / 64, g), 64, 0, st>>>(dkids, (uint32_t)n, (uint32_t)p.nsets, (uint32_t)p.W, rsets);
+		e = body(first, g);
+	}
+	return e;
 }
 
 } // namespace

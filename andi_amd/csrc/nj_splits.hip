@@ -1,9 +1,10 @@
 // nj_splits.hip — every distinct bipartition among the trees of a bootstrap, with its frequency (andi_hip_nj_splits,
 // include/andi_hip.h): what a majority-rule consensus tree is made of (host_model.c: andi_hip_consensus).
 //
-// The host validates the records and hands the device the two children of every pair record (nj_sets.h, shared with
-// nj_support.hip).  The used replicates are taken in groups of as many trees as GROUP_BYTES hold; a group's m = g x (n - 3)
-// sets are built and hashed on their canonical side (k_sets, k_hash) and then grouped EXACTLY:
+// The host's validation of the records, the replicates' groups and the kernels that build a tree's leaf sets (k_sets) and
+// hash them on their canonical side (k_hash) are nj_sets.h's, shared with nj_support.hip and nj_transfer.hip.  This call's
+// own: no point tree; with every replicate skipped it returns no split before any HIP call; a group is also no larger than
+// hipcub counts (MAX_ITEMS sets); and a group's m = g x (n - 3) sets are hashed and then grouped EXACTLY:
 //   k_keys    the sort keys: the hashes (cut to ANDI_SPLIT_HASH_BITS bits by the test hook) with the sets' indices as values;
 //             a stable radix sort (hipcub) brings equal hashes together, indices ascending within a run of equal hashes;
 //   k_heads   + an inclusive max scan: for every sorted position the start of its run;
@@ -32,13 +33,10 @@
 #include <cstring>
 #include <vector>
 
-#include "api_internal.h"
 #include "nj_sets.h"
 
 namespace {
 
-constexpr size_t GROUP_BYTES = (size_t)2 << 30; // device memory of a group of replicates' sets, at most (one tree always fits)
-constexpr size_t MAX_GROUP = 65535;             // a grid's second dimension
 constexpr size_t MAX_ITEMS = 0x7fffff00;        // hipcub counts with int
 constexpr uint32_t NONE = 0xffffffffu;
 
@@ -175,38 +173,22 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 	}
 	*nsplits = 0, *freq = nullptr, *sets = nullptr;
 	if (n < 4) return 0; // (no branch that is not a leaf's)
-	const size_t nsets = n - 3, nrec = n - 2, W = (n + 63) / 64;
-	// the group: the replicates that count, GROUP_BYTES of sets and of what sorts them at a time
-	const size_t tree_bytes = nsets * W * sizeof(uint64_t) + nsets * (sizeof(int2) + 3 * sizeof(uint64_t) + 8 * sizeof(uint32_t));
-	size_t G = GROUP_BYTES / tree_bytes;
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing (as andi_hip_nj_support)
-		const long long f = atoll(v);
-		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
-	}
+	// a set costs, beside its words: its record's children, three 64-bit and eight 32-bit words of what sorts and classes it
+	SetsPlan p;
+	if (!sets_prepare(ctx, "andi_hip_nj_splits", nullptr, reps, n, count, skip,
+					  sizeof(int2) + 3 * sizeof(uint64_t) + 8 * sizeof(uint32_t), p))
+		return 1;
+	const size_t nsets = p.nsets, W = p.W;
+	const std::vector<size_t> &used = p.used;
 	uint64_t mask = ~0ull;
 	if (const char *v = andi_knob(KNOB_SPLIT_HASH_BITS)) { // test hook: only the low bits of the hash, so that sets collide
 		const int b = atoi(v);
 		if (b >= 0 && b < 64) mask = (1ull << b) - 1;
 	}
-	std::vector<uint8_t> seen(2 * n);
-	std::vector<int2> kids;
-	std::vector<size_t> used; // the replicates that count, validated all before any HIP call
-	for (size_t k = 0; k < count; ++k)
-		if (!skip || !skip[k]) used.push_back(k);
-	kids.resize(used.size() * nsets);
-	for (size_t u = 0; u < used.size(); ++u)
-		if (!records_ok(reps + used[u] * nrec, n, seen.data(), kids.data() + u * nsets)) {
-			char msg[128];
-			snprintf(msg, sizeof msg, "andi_hip_nj_splits: the records of replicate %zu are not those of andi_hip_nj", used[u]);
-			ctx->err = msg;
-			return 1;
-		}
 	memset(ids, 0xff, count * nsets * sizeof *ids);
 	if (used.empty()) return 0; // (every replicate skipped: no split)
-	if (G > used.size()) G = used.size();
-	if (G * nsets > MAX_ITEMS) G = MAX_ITEMS / nsets;
-	const size_t all = used.size() * nsets, M = G * nsets;
+	if (p.G * nsets > MAX_ITEMS) p.G = MAX_ITEMS / nsets;
+	const size_t all = used.size() * nsets, M = p.G * nsets;
 
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const uint32_t N = (uint32_t)n, S = (uint32_t)nsets, Wd = (uint32_t)W;
@@ -219,18 +201,14 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 	uint64_t *tsets = nullptr, *thash = nullptr, *shash = nullptr;
 	uint32_t *iota = nullptr, *sslot = nullptr, *tfreq = nullptr, *slot = nullptr;
 	unsigned long long *dT = nullptr, hT = 0;
-	void *tmp = nullptr;
+	uint8_t *tmp = nullptr;
 	size_t cap = 0, tmp_bytes = 0;
 	const size_t split_bytes = W * sizeof(uint64_t) + 2 * sizeof(uint64_t) + 3 * sizeof(uint32_t); // a slot of the table
-	hipError_t e = dmalloc(&dkids, M);
-	if (e == hipSuccess) e = dmalloc(&rhash, M);
-	if (e == hipSuccess) e = dmalloc(&keys, M);
-	if (e == hipSuccess) e = dmalloc(&skeys, M);
-	for (uint32_t **p : {&vals, &svals, &start, &run, &rep, &pslot, &isnew, &newrank})
-		if (e == hipSuccess) e = dmalloc(p, M);
-	if (e == hipSuccess) e = dmalloc(&rsets, M * W);
-	if (e == hipSuccess) e = dmalloc(&slot, all);
-	if (e == hipSuccess) e = dmalloc(&dT, 1);
+	DevScope dev(st);
+	dev.alloc(&dkids, M), dev.alloc(&rhash, M), dev.alloc(&keys, M), dev.alloc(&skeys, M);
+	for (uint32_t **q : {&vals, &svals, &start, &run, &rep, &pslot, &isnew, &newrank}) dev.alloc(q, M);
+	dev.alloc(&rsets, M * W), dev.alloc(&slot, all), dev.alloc(&dT, 1);
+	hipError_t e = dev.err;
 	if (e == hipSuccess) { // the table: room for every set, or for what half of the free memory holds (one tree's sets at least)
 		size_t free_b = 0, total_b = 0;
 		e = hipMemGetInfo(&free_b, &total_b);
@@ -239,12 +217,11 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 		cap = cap > all ? all : cap;
 		cap = cap > MAX_ITEMS ? MAX_ITEMS : cap;
 	}
-	if (e == hipSuccess) e = dmalloc(&tsets, cap * W);
-	if (e == hipSuccess) e = dmalloc(&thash, cap);
-	if (e == hipSuccess) e = dmalloc(&shash, cap);
-	if (e == hipSuccess) e = dmalloc(&iota, cap);
-	if (e == hipSuccess) e = dmalloc(&sslot, cap);
-	if (e == hipSuccess) e = dmalloc(&tfreq, cap);
+	if (e == hipSuccess) {
+		dev.alloc(&tsets, cap * W), dev.alloc(&thash, cap), dev.alloc(&shash, cap);
+		dev.alloc(&iota, cap), dev.alloc(&sslot, cap), dev.alloc(&tfreq, cap);
+		e = dev.err;
+	}
 	if (e == hipSuccess) { // hipcub's scratch, for the largest of its calls below
 		size_t a = 0, b = 0, c = 0, d = 0;
 		e = hipcub::DeviceRadixSort::SortPairs(nullptr, a, keys, skeys, vals, svals, (int)M, 0, 64, st);
@@ -254,7 +231,7 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 		tmp_bytes = a > b ? a : b;
 		tmp_bytes = tmp_bytes > c ? tmp_bytes : c;
 		tmp_bytes = tmp_bytes > d ? tmp_bytes : d;
-		if (e == hipSuccess) e = andi_arena::dev_malloc(&tmp, tmp_bytes ? tmp_bytes : 1);
+		if (e == hipSuccess) dev.alloc(&tmp, tmp_bytes ? tmp_bytes : 1), e = dev.err;
 	}
 	const uint32_t C = (uint32_t)cap;
 	if (e == hipSuccess) e = hipMemsetAsync(dT, 0, sizeof *dT, st);
@@ -264,30 +241,29 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 		k_iota<<<(C + 255) / 256, 256, 0, st>>>(C, iota);
 		e = hipGetLastError();
 	}
-	for (size_t first = 0; e == hipSuccess && first < used.size(); first += G) {
-		const uint32_t g = (uint32_t)(used.size() - first < G ? used.size() - first : G), m = g * S;
-		size_t tb = tmp_bytes;
-		e = hipMemcpyAsync(dkids, kids.data() + first * nsets, (size_t)m * sizeof(int2), hipMemcpyHostToDevice, st);
-		if (e != hipSuccess) break;
-		k_sets<<<dim3((Wd + 63) / 64, g), 64, 0, st>>>(dkids, N, S, Wd, rsets);
-		k_hash<<<dim3((S + 3) / 4, g), 256, 0, st>>>(rsets, N, S, Wd, rhash);
-		k_keys<<<(m + 255) / 256, 256, 0, st>>>(rhash, mask, m, keys, vals);
-		if ((e = hipGetLastError()) != hipSuccess) break;
-		if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, skeys, vals, svals, (int)m, 0, 64, st)) != hipSuccess) break;
-		k_heads<<<(m + 255) / 256, 256, 0, st>>>(skeys, m, start);
-		tb = tmp_bytes;
-		if ((e = hipcub::DeviceScan::InclusiveScan(tmp, tb, start, run, hipcub::Max(), (int)m, st)) != hipSuccess) break;
-		k_class<<<(m + 3) / 4, 256, 0, st>>>(rsets, svals, run, N, Wd, m, rep);
-		tb = tmp_bytes;
-		if ((e = hipcub::DeviceRadixSort::SortPairs(tmp, tb, thash, shash, iota, sslot, (int)C, 0, 64, st)) != hipSuccess) break;
-		k_lookup<<<(m + 3) / 4, 256, 0, st>>>(rsets, skeys, svals, rep, N, Wd, m, tsets, shash, sslot, dT, C, pslot, isnew);
-		tb = tmp_bytes;
-		if ((e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, isnew, newrank, (int)m, st)) != hipSuccess) break;
-		k_append<<<(m + 3) / 4, 256, 0, st>>>(rsets, skeys, svals, rep, isnew, newrank, N, Wd, m, tsets, thash, dT, C, pslot);
-		k_count<<<(m + 255) / 256, 256, 0, st>>>(svals, rep, pslot, m, slot + first * nsets, tfreq);
-		k_bump<<<1, 1, 0, st>>>(isnew, newrank, m, dT);
-		e = hipGetLastError();
-	}
+	if (e == hipSuccess)
+		e = sets_for_groups(p, n, dkids, rsets, st, [&](size_t first, uint32_t g) {
+			const uint32_t m = g * S;
+			size_t tb = tmp_bytes;
+			hipError_t le;
+			k_hash<<<dim3((S + 3) / 4, g), 256, 0, st>>>(rsets, N, S, Wd, rhash);
+			k_keys<<<(m + 255) / 256, 256, 0, st>>>(rhash, mask, m, keys, vals);
+			if ((le = hipGetLastError()) != hipSuccess) return le;
+			if ((le = hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, skeys, vals, svals, (int)m, 0, 64, st)) != hipSuccess) return le;
+			k_heads<<<(m + 255) / 256, 256, 0, st>>>(skeys, m, start);
+			tb = tmp_bytes;
+			if ((le = hipcub::DeviceScan::InclusiveScan(tmp, tb, start, run, hipcub::Max(), (int)m, st)) != hipSuccess) return le;
+			k_class<<<(m + 3) / 4, 256, 0, st>>>(rsets, svals, run, N, Wd, m, rep);
+			tb = tmp_bytes;
+			if ((le = hipcub::DeviceRadixSort::SortPairs(tmp, tb, thash, shash, iota, sslot, (int)C, 0, 64, st)) != hipSuccess) return le;
+			k_lookup<<<(m + 3) / 4, 256, 0, st>>>(rsets, skeys, svals, rep, N, Wd, m, tsets, shash, sslot, dT, C, pslot, isnew);
+			tb = tmp_bytes;
+			if ((le = hipcub::DeviceScan::ExclusiveSum(tmp, tb, isnew, newrank, (int)m, st)) != hipSuccess) return le;
+			k_append<<<(m + 3) / 4, 256, 0, st>>>(rsets, skeys, svals, rep, isnew, newrank, N, Wd, m, tsets, thash, dT, C, pslot);
+			k_count<<<(m + 255) / 256, 256, 0, st>>>(svals, rep, pslot, m, slot + first * nsets, tfreq);
+			k_bump<<<1, 1, 0, st>>>(isnew, newrank, m, dT);
+			return hipGetLastError();
+		});
 	if (e == hipSuccess) e = hipMemcpyAsync(&hT, dT, sizeof hT, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
 	bool fits = true;
@@ -308,12 +284,8 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
 		}
 		if (e == hipSuccess) e = hipStreamSynchronize(st);
 	}
-	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
-	for (void *p : {(void *)rsets, (void *)rhash, (void *)keys, (void *)skeys, (void *)dkids, (void *)vals, (void *)svals,
-					(void *)start, (void *)run, (void *)rep, (void *)pslot, (void *)isnew, (void *)newrank, (void *)tsets, (void *)thash,
-					(void *)shash, (void *)iota, (void *)sslot, (void *)tfreq, (void *)slot, (void *)dT, tmp})
-		if (p) (void)andi_arena::dev_free(p, false);
 	if (e != hipSuccess || !fits) {
+		(void)hipStreamSynchronize(st); // (an error exit: no copy in flight writes what is freed and reset here)
 		free(hfreq), free(hsets);
 		memset(ids, 0xff, count * nsets * sizeof *ids);
 		if (e != hipSuccess) return fail(ctx, "andi_hip_nj_splits", e);

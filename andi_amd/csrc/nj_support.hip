@@ -2,30 +2,22 @@
 // include/andi_hip.h): for every pair record of the point-estimate tree, the number of replicate trees that have the
 // same bipartition of the leaves.
 //
-// The host validates the records (every child a leaf or an earlier record's node, every node a child exactly once) and
-// hands the device only the two children of every pair record.  On the device a tree's leaf sets are bitsets of W =
-// ceil(n / 64) words, set s below node n + s, built by k_sets and hashed on their canonical side -- the side without
-// leaf 0 -- by k_hash (nj_sets.h, shared with nj_splits.hip); then
+// The host's validation of the records, the replicates' groups and the kernels that build a tree's leaf sets (k_sets)
+// and hash them on their canonical side (k_hash) are nj_sets.h's, shared with nj_transfer.hip and nj_splits.hip.  This
+// call's own: a set costs its hash and its record's two children beside its words, there is a point tree, and a group's
+// sets are hashed and then go through
 //   k_match  one block per set of the point tree: the hashes of all sets of the group's replicates are compared with its
 //            own, and where a hash agrees the canonical words themselves are compared, so the count is exact.  A valid
 //            tree has every bipartition once, so a replicate adds at most one; the block adds its total to support[s]
 //            (the only writer of that word: no atomics; groups run one after the other on the context's stream).
-// Replicates are taken in groups of as many trees as GROUP_BYTES hold (one tree's sets are 537 MB at 65535 leaves).
+// With every replicate skipped the point tree still goes through the device and the counts come back as zeros.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
-#include "api_internal.h"
 #include "nj_sets.h"
 
 namespace {
-
-constexpr size_t GROUP_BYTES = (size_t)2 << 30; // device memory of a group of replicates' sets, at most (one tree always fits)
-constexpr size_t MAX_GROUP = 65535;             // a grid's second dimension
 
 // Block s: support[s] += the number of sets among the g replicates' (g x nsets of them) that equal set s of the point tree
 // on the canonical side.
@@ -63,34 +55,9 @@ int andi_hip_nj_support(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const a
 		return 1;
 	}
 	if (n < 4) return 0; // (no branch that is not a leaf's)
-	const size_t nsets = n - 3, nrec = n - 2, W = (n + 63) / 64;
-	// the group: the replicates that count, GROUP_BYTES of sets at a time
-	const size_t tree_bytes = nsets * W * sizeof(uint64_t) + nsets * (sizeof(uint64_t) + sizeof(int2));
-	size_t G = GROUP_BYTES / tree_bytes;
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing (as andi_hip_nj_batch)
-		const long long f = atoll(v);
-		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
-	}
-	if (G > count) G = count;
-	std::vector<uint8_t> seen(2 * n);
-	std::vector<int2> tkids(nsets), kids;
-	if (!records_ok(tree, n, seen.data(), tkids.data())) {
-		ctx->err = "andi_hip_nj_support: the tree's records are not those of andi_hip_nj";
-		return 1;
-	}
-	std::vector<size_t> used; // the replicates that count, validated all before any HIP call
-	for (size_t k = 0; k < count; ++k)
-		if (!skip || !skip[k]) used.push_back(k);
-	kids.resize(used.size() * nsets);
-	for (size_t u = 0; u < used.size(); ++u)
-		if (!records_ok(reps + used[u] * nrec, n, seen.data(), kids.data() + u * nsets)) {
-			char msg[128];
-			snprintf(msg, sizeof msg, "andi_hip_nj_support: the records of replicate %zu are not those of andi_hip_nj", used[u]);
-			ctx->err = msg;
-			return 1;
-		}
-	if (G > used.size()) G = used.size() ? used.size() : 1;
+	SetsPlan p;
+	if (!sets_prepare(ctx, "andi_hip_nj_support", tree, reps, n, count, skip, sizeof(uint64_t) + sizeof(int2), p)) return 1;
+	const size_t nsets = p.nsets, W = p.W, G = p.G;
 
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const uint32_t N = (uint32_t)n, S = (uint32_t)nsets, Wd = (uint32_t)W;
@@ -98,34 +65,26 @@ int andi_hip_nj_support(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const a
 	int2 *dkids = nullptr;
 	uint32_t *dsup = nullptr;
 	hipStream_t st = ctx->stream;
-	hipError_t e = dmalloc(&tsets, nsets * W);
-	if (e == hipSuccess) e = dmalloc(&thash, nsets);
-	if (e == hipSuccess) e = dmalloc(&dsup, nsets);
-	if (e == hipSuccess) e = dmalloc(&dkids, (G > 1 ? G : 1) * nsets);
-	if (e == hipSuccess) e = dmalloc(&rhash, G * nsets);
-	if (e == hipSuccess) e = dmalloc(&rsets, G * nsets * W);
+	DevScope dev(st);
+	dev.alloc(&tsets, nsets * W), dev.alloc(&thash, nsets), dev.alloc(&dsup, nsets);
+	dev.alloc(&dkids, G * nsets), dev.alloc(&rhash, G * nsets), dev.alloc(&rsets, G * nsets * W);
+	hipError_t e = dev.err;
 	if (e == hipSuccess) e = hipMemsetAsync(dsup, 0, nsets * sizeof *dsup, st);
-	// the point tree's sets and hashes
-	if (e == hipSuccess) e = hipMemcpyAsync(dkids, tkids.data(), nsets * sizeof(int2), hipMemcpyHostToDevice, st);
+	// the point tree's sets and hashes (also when every replicate is skipped: the counts are zeros then)
+	if (e == hipSuccess) e = hipMemcpyAsync(dkids, p.tkids.data(), nsets * sizeof(int2), hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) {
 		k_sets<<<dim3((Wd + 63) / 64, 1), 64, 0, st>>>(dkids, N, S, Wd, tsets);
 		k_hash<<<dim3((S + 3) / 4, 1), 256, 0, st>>>(tsets, N, S, Wd, thash);
 		e = hipGetLastError();
 	}
-	for (size_t first = 0; e == hipSuccess && first < used.size(); first += G) {
-		const uint32_t g = (uint32_t)(used.size() - first < G ? used.size() - first : G);
-		e = hipMemcpyAsync(dkids, kids.data() + first * nsets, (size_t)g * nsets * sizeof(int2), hipMemcpyHostToDevice, st);
-		if (e != hipSuccess) break;
-		k_sets<<<dim3((Wd + 63) / 64, g), 64, 0, st>>>(dkids, N, S, Wd, rsets);
-		k_hash<<<dim3((S + 3) / 4, g), 256, 0, st>>>(rsets, N, S, Wd, rhash);
-		k_match<<<S, 256, 0, st>>>(tsets, thash, rsets, rhash, N, S, Wd, g, dsup);
-		e = hipGetLastError();
-	}
+	if (e == hipSuccess)
+		e = sets_for_groups(p, n, dkids, rsets, st, [&](size_t, uint32_t g) {
+			k_hash<<<dim3((S + 3) / 4, g), 256, 0, st>>>(rsets, N, S, Wd, rhash);
+			k_match<<<S, 256, 0, st>>>(tsets, thash, rsets, rhash, N, S, Wd, g, dsup);
+			return hipGetLastError();
+		});
 	if (e == hipSuccess) e = hipMemcpyAsync(support, dsup, nsets * sizeof *dsup, hipMemcpyDeviceToHost, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
-	for (void *p : {(void *)tsets, (void *)thash, (void *)rsets, (void *)rhash, (void *)dkids, (void *)dsup})
-		if (p) (void)andi_arena::dev_free(p, false);
 	if (e != hipSuccess) return fail(ctx, "andi_hip_nj_support", e);
 	return 0;
 }

@@ -3,9 +3,11 @@
 // the least number of leaves that have to move to turn a branch of the replicate's tree into branch s -- and its sum
 // over the replicates (Lemoine et al. 2018: the transfer bootstrap expectation is 1 - sum / (used * (depth - 1))).
 //
-// The host validates the records as andi_hip_nj_support does and hands the device the children of every pair record.
-// A tree's leaf sets are bitsets of W = ceil(n / 64) words (k_sets, nj_sets.h; the padding bits of the last word are
-// zero), so h(A, B) = |A xor B| is a sum of popcounts and the transfer distance is min(h, n - h).
+// The host's validation of the records, the replicates' groups and k_sets are nj_sets.h's, shared with nj_support.hip and
+// nj_splits.hip.  A tree's leaf sets are bitsets of W = ceil(n / 64) words (the padding bits of the last word are zero),
+// so h(A, B) = |A xor B| is a sum of popcounts and the transfer distance is min(h, n - h).  This call's own: a set costs
+// its record's two children and one index of per beside its words, there is a point tree, and a group's sets go through
+// k_transfer and, if per is asked for, one copy of the group's rows to the host:
 //   k_depth     one wavefront per set of the point tree: depth[s] = min(|L_s|, n - |L_s|);
 //   k_transfer  a block owns a tile of TS sets of the point tree and ONE replicate (blockIdx.y) and walks that
 //               replicate's sets in tiles of TT.  Both tiles go through LDS in chunks of WC words, word-major
@@ -17,23 +19,16 @@
 //               the 16 lanes that share a point set reduce their minima, the first of them applies the cap depth - 1
 //               (what the replicate's leaf branches contribute), writes per[k][s] -- its only writer -- and adds it to
 //               transfer[s] with a 64-bit integer atomic (exact in any order).
-// Replicates are taken in groups of as many trees as GROUP_BYTES hold, as in nj_support.hip; the groups' launches
-// follow one another on the context's stream without a host synchronisation in between.
+// With every replicate skipped the point tree still goes through the device: depth, zero sums, and per all 0xFFFFFFFF.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "api_internal.h"
 #include "nj_sets.h"
 
 namespace {
-
-constexpr size_t GROUP_BYTES = (size_t)2 << 30; // device memory of a group of replicates' sets, at most (one tree always fits)
-constexpr size_t MAX_GROUP = 65535;             // a grid's second dimension
 
 constexpr uint32_t TS = 128, TT = 128; // sets of the point tree / of the replicate per tile
 constexpr uint32_t WC = 8;             // words per chunk in LDS
@@ -156,34 +151,10 @@ int andi_hip_nj_transfer(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const 
 		return 1;
 	}
 	if (n < 4) return 0; // (no branch that is not a leaf's)
-	const size_t nsets = n - 3, nrec = n - 2, W = (n + 63) / 64;
-	// the group: the replicates that count, GROUP_BYTES of sets (and their children and indices) at a time
-	const size_t tree_bytes = nsets * W * sizeof(uint64_t) + nsets * (sizeof(int2) + sizeof(uint32_t));
-	size_t G = GROUP_BYTES / tree_bytes;
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP)) { // test hook: a group size of the test's choosing (as andi_hip_nj_support)
-		const long long f = atoll(v);
-		if (f >= 1) G = (size_t)f > MAX_GROUP ? MAX_GROUP : (size_t)f;
-	}
-	if (G > count) G = count;
-	std::vector<uint8_t> seen(2 * n);
-	std::vector<int2> tkids(nsets), kids;
-	if (!records_ok(tree, n, seen.data(), tkids.data())) {
-		ctx->err = "andi_hip_nj_transfer: the tree's records are not those of andi_hip_nj";
-		return 1;
-	}
-	std::vector<size_t> used; // the replicates that count, validated all before any HIP call
-	for (size_t k = 0; k < count; ++k)
-		if (!skip || !skip[k]) used.push_back(k);
-	kids.resize(used.size() * nsets);
-	for (size_t u = 0; u < used.size(); ++u)
-		if (!records_ok(reps + used[u] * nrec, n, seen.data(), kids.data() + u * nsets)) {
-			char msg[128];
-			snprintf(msg, sizeof msg, "andi_hip_nj_transfer: the records of replicate %zu are not those of andi_hip_nj", used[u]);
-			ctx->err = msg;
-			return 1;
-		}
-	if (G > used.size()) G = used.size() ? used.size() : 1;
+	SetsPlan p;
+	if (!sets_prepare(ctx, "andi_hip_nj_transfer", tree, reps, n, count, skip, sizeof(int2) + sizeof(uint32_t), p)) return 1;
+	const size_t nsets = p.nsets, W = p.W, G = p.G;
+	const std::vector<size_t> &used = p.used;
 	std::vector<uint32_t> hper(per ? used.size() * nsets : 0); // the used replicates' rows, as the groups deliver them
 
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -193,38 +164,33 @@ int andi_hip_nj_transfer(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const 
 	int2 *dkids = nullptr;
 	uint32_t *ddepth = nullptr, *dper = nullptr;
 	hipStream_t st = ctx->stream;
-	hipError_t e = dmalloc(&tsets, nsets * W);
-	if (e == hipSuccess) e = dmalloc(&ddepth, nsets);
-	if (e == hipSuccess) e = dmalloc(&dsum, nsets);
-	if (e == hipSuccess) e = dmalloc(&dkids, G * nsets);
-	if (e == hipSuccess && per) e = dmalloc(&dper, G * nsets);
-	if (e == hipSuccess) e = dmalloc(&rsets, G * nsets * W);
-	if (e == hipSuccess) e = hipMemsetAsync(dsum, 0, nsets * sizeof *dsum, st);
-	// the point tree's sets and depths
-	if (e == hipSuccess) e = hipMemcpyAsync(dkids, tkids.data(), nsets * sizeof(int2), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) {
-		k_sets<<<dim3((Wd + 63) / 64, 1), 64, 0, st>>>(dkids, N, S, Wd, tsets);
-		k_depth<<<(S + 3) / 4, 256, 0, st>>>(tsets, N, S, Wd, ddepth);
-		e = hipGetLastError();
+	{
+		DevScope dev(st);
+		dev.alloc(&tsets, nsets * W), dev.alloc(&ddepth, nsets), dev.alloc(&dsum, nsets), dev.alloc(&dkids, G * nsets);
+		if (per) dev.alloc(&dper, G * nsets);
+		dev.alloc(&rsets, G * nsets * W);
+		hipError_t e = dev.err;
+		if (e == hipSuccess) e = hipMemsetAsync(dsum, 0, nsets * sizeof *dsum, st);
+		// the point tree's sets and depths (also when every replicate is skipped: depth, and zero sums)
+		if (e == hipSuccess) e = hipMemcpyAsync(dkids, p.tkids.data(), nsets * sizeof(int2), hipMemcpyHostToDevice, st);
+		if (e == hipSuccess) {
+			k_sets<<<dim3((Wd + 63) / 64, 1), 64, 0, st>>>(dkids, N, S, Wd, tsets);
+			k_depth<<<(S + 3) / 4, 256, 0, st>>>(tsets, N, S, Wd, ddepth);
+			e = hipGetLastError();
+		}
+		if (e == hipSuccess)
+			e = sets_for_groups(p, n, dkids, rsets, st, [&](size_t first, uint32_t g) {
+				k_transfer<<<dim3((S + TS - 1) / TS, g), 256, 0, st>>>(tsets, rsets, ddepth, N, S, Wd, dper, dsum);
+				const hipError_t le = hipGetLastError();
+				if (le != hipSuccess || !per) return le;
+				return hipMemcpyAsync(hper.data() + first * nsets, dper, (size_t)g * nsets * sizeof *dper, hipMemcpyDeviceToHost, st);
+			});
+		static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums are copied as they are");
+		if (e == hipSuccess) e = hipMemcpyAsync(depth, ddepth, nsets * sizeof *ddepth, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipMemcpyAsync(transfer, dsum, nsets * sizeof *dsum, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e != hipSuccess) return fail(ctx, "andi_hip_nj_transfer", e);
 	}
-	for (size_t first = 0; e == hipSuccess && first < used.size(); first += G) {
-		const uint32_t g = (uint32_t)(used.size() - first < G ? used.size() - first : G);
-		e = hipMemcpyAsync(dkids, kids.data() + first * nsets, (size_t)g * nsets * sizeof(int2), hipMemcpyHostToDevice, st);
-		if (e != hipSuccess) break;
-		k_sets<<<dim3((Wd + 63) / 64, g), 64, 0, st>>>(dkids, N, S, Wd, rsets);
-		k_transfer<<<dim3((S + TS - 1) / TS, g), 256, 0, st>>>(tsets, rsets, ddepth, N, S, Wd, dper, dsum);
-		e = hipGetLastError();
-		if (e == hipSuccess && per)
-			e = hipMemcpyAsync(hper.data() + first * nsets, dper, (size_t)g * nsets * sizeof *dper, hipMemcpyDeviceToHost, st);
-	}
-	static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums are copied as they are");
-	if (e == hipSuccess) e = hipMemcpyAsync(depth, ddepth, nsets * sizeof *ddepth, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(transfer, dsum, nsets * sizeof *dsum, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
-	for (void *p : {(void *)tsets, (void *)rsets, (void *)dsum, (void *)dkids, (void *)ddepth, (void *)dper})
-		if (p) (void)andi_arena::dev_free(p, false);
-	if (e != hipSuccess) return fail(ctx, "andi_hip_nj_transfer", e);
 	if (per) {
 		memset(per, 0xFF, count * nsets * sizeof *per); // (a skipped replicate's row)
 		for (size_t u = 0; u < used.size(); ++u) memcpy(per + used[u] * nsets, hper.data() + u * nsets, nsets * sizeof *per);

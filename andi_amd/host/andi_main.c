@@ -322,8 +322,23 @@ static void read_all_files(char **files, size_t nfiles, int join, int threads, g
 	free(job.results);
 }
 
+/* file names, as the command line and the files of file names give them */
+typedef struct {
+	char **v;
+	size_t n, cap;
+} name_list;
+
+static void push_name(name_list *l, const char *name) {
+	if (l->n == l->cap) {
+		l->cap = l->cap ? l->cap * 2 : 16;
+		l->v = realloc(l->v, l->cap * sizeof *l->v);
+		if (!l->v) err(errno, "Out of memory");
+	}
+	l->v[l->n++] = strdup(name);
+}
+
 /* read_into_string_vector, src/io.c:103-144 */
-static void read_file_of_filenames(const char *file_name, char ***names, size_t *n, size_t *cap) {
+static void read_file_of_filenames(const char *file_name, name_list *names) {
 	FILE *f = strcmp(file_name, "-") ? fopen(file_name, "r") : stdin;
 	if (!f) {
 		soft_error = 1;
@@ -335,13 +350,7 @@ static void read_file_of_filenames(const char *file_name, char ***names, size_t 
 	while (getline(&line, &bufsz, f) != -1) {
 		char *nl = strchr(line, '\n');
 		if (nl) *nl = '\0';
-		if (!*line) continue;
-		if (*n == *cap) {
-			*cap = *cap ? *cap * 2 : 16;
-			*names = realloc(*names, *cap * sizeof **names);
-			if (!*names) err(errno, "Out of memory");
-		}
-		(*names)[(*n)++] = strdup(line);
+		if (*line) push_name(names, line);
 	}
 	free(line);
 	if (f != stdin) fclose(f);
@@ -405,17 +414,25 @@ static void progress_cb(size_t done, size_t total, void *ud) {
 			total ? 100.0 * (double)done / (double)total : 100.0, done, total);
 }
 
-static void print_matrix(const andi_hip_model *M, const genome *g, size_t n, int model, int vv,
-						 int truncate, int warnings) {
+static const char **name_array(const genome *g, size_t n) {
 	const char **names = xmalloc(n * sizeof *names);
 	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
+	return names;
+}
+
+/* The square matrix M of the nr sequences rn (qn == NULL), or the query-versus-reference table (--reference) of the two
+ * cross blocks M and MQR: one row per query qn, one column per reference rn.  To stdout, the warnings as soft warnings. */
+static void print_distances(const andi_hip_model *M, const andi_hip_model *MQR, const char **rn, size_t nr, const char **qn, size_t nq,
+							int model, int vv, int truncate, int warnings) {
 	/* the warnings' buffer grows on demand (a line per pair at worst -- n^2 x 512 bytes up front would be 4.9 GB for
 	 * BASELINE's 3085 genomes): a buffer that came back full is doubled and the call repeated */
-	size_t cap = 64 + n * (300 + 16 * n), wcap = (size_t)1 << 16;
+	size_t cap = 64 + (qn ? nq : nr) * (300 + 16 * nr), wcap = (size_t)1 << 16;
+	for (size_t i = 0; qn && i < nr; i++) cap += strlen(rn[i]) + 1;
 	char *out = xmalloc(cap), *wbuf = xmalloc(wcap);
 	int flags = 0;
 	for (;;) {
-		const size_t need = andi_hip_format_distances(M, names, n, model, vv, truncate, warnings, out, cap, wbuf, wcap, &flags);
+		const size_t need = qn ? andi_hip_format_distances_rect(M, MQR, rn, nr, qn, nq, model, vv, truncate, warnings, out, cap, wbuf, wcap, &flags)
+							   : andi_hip_format_distances(M, rn, nr, model, vv, truncate, warnings, out, cap, wbuf, wcap, &flags);
 		const int out_short = need >= cap, warn_short = strlen(wbuf) + 1 >= wcap; /* (long names: the call says how much it needs) */
 		if (!out_short && !warn_short) break;
 		if (out_short) free(out), cap = need + 1, out = xmalloc(cap);
@@ -425,76 +442,65 @@ static void print_matrix(const andi_hip_model *M, const genome *g, size_t n, int
 	fputs(out, stdout);
 	free(out);
 	free(wbuf);
-	free(names);
 }
 
-/* the query-versus-reference table (--reference): one row per query, one column per reference */
-static void print_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR, const genome *r, size_t nr, const genome *q,
-					   size_t nq, int model, int vv, int truncate) {
-	const char **rn = xmalloc(nr * sizeof *rn), **qn = xmalloc(nq * sizeof *qn);
-	for (size_t i = 0; i < nr; i++) rn[i] = r[i].name;
-	for (size_t i = 0; i < nq; i++) qn[i] = q[i].name;
-	size_t cap = 64, wcap = (size_t)1 << 16;
-	for (size_t i = 0; i < nr; i++) cap += strlen(rn[i]) + 1;
-	cap += nq * (300 + 16 * nr);
-	char *out = xmalloc(cap), *wbuf = xmalloc(wcap);
-	int flags = 0;
-	for (;;) {
-		const size_t need = andi_hip_format_distances_rect(MRQ, MQR, rn, nr, qn, nq, model, vv, truncate, 1, out, cap, wbuf, wcap, &flags);
-		const int out_short = need >= cap, warn_short = strlen(wbuf) + 1 >= wcap;
-		if (!out_short && !warn_short) break;
-		if (out_short) free(out), cap = need + 1, out = xmalloc(cap);
-		if (warn_short) free(wbuf), wcap *= 4, wbuf = xmalloc(wcap);
-	}
-	for (char *line = strtok(wbuf, "\n"); line; line = strtok(NULL, "\n")) soft_warnx("%s", line);
-	fputs(out, stdout);
-	free(out);
-	free(wbuf);
-	free(rn);
-	free(qn);
+/* The four files of trees.  Each is refused under --reference / --reference-list, and all but --tree without bootstrap
+ * matrices; main parses, refuses, opens and closes them in this order. */
+enum { OUT_TREE, OUT_SUPPORT, OUT_CONSENSUS, OUT_TRANSFER, OUT_COUNT };
+typedef struct {
+	const char *option, *with_reference, *without_bootstrap; /* the long option and its two refusals (NULL: none) */
+	const char *path;
+	FILE *f;
+} tree_file;
+#define WITH_REFERENCE " not available together with --reference or --reference-list."
+#define NEEDS_B " bootstrap matrices: give -b N with N of at least 2."
+static tree_file outs[OUT_COUNT] = {
+	{"tree", "A tree (--tree) is" WITH_REFERENCE, NULL, NULL, NULL},
+	{"support", "Support values (--support) are" WITH_REFERENCE, "Support values (--support) need" NEEDS_B, NULL, NULL},
+	{"consensus", "A consensus tree (--consensus) is" WITH_REFERENCE, "A consensus tree (--consensus) needs" NEEDS_B, NULL, NULL},
+	{"transfer", "Transfer support (--transfer) is" WITH_REFERENCE, "Transfer support (--transfer) needs" NEEDS_B, NULL, NULL},
+};
+
+/* what one Newick line is made of: the consensus tree's nodes; or the records J with the transfer bootstrap expectation
+ * (depth, transfer, used) or the support values (NULL: none) as inner labels */
+typedef struct {
+	const andi_hip_nj_join *J;
+	const uint32_t *support;
+	const uint32_t *depth;
+	const uint64_t *transfer;
+	size_t used;
+	const andi_hip_cons_node *nodes;
+	size_t ninner;
+} newick_src;
+
+static size_t format_newick(const newick_src *w, const char **names, size_t n, int truncate, char *text, size_t cap) {
+	if (w->nodes) return andi_hip_format_newick_consensus(w->nodes, n, w->ninner, names, truncate, text, cap);
+	if (w->depth) return andi_hip_format_newick_transfer(w->J, w->depth, w->transfer, w->used, n, names, truncate, text, cap);
+	return andi_hip_format_newick_support(w->J, w->support, n, names, truncate, text, cap);
+}
+
+/* one Newick line to the file o */
+static void put_newick(const tree_file *o, const newick_src *w, const char **names, size_t n, int truncate) {
+	size_t cap = 64 + n * (w->nodes ? 80 : w->depth ? 60 : 52);
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	const size_t need = format_newick(w, names, n, truncate, text, cap);
+	if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), format_newick(w, names, n, truncate, text, cap);
+	if (fputs(text, o->f) == EOF) err(1, "%s", o->path);
+	free(text);
 }
 
 /* --tree: the neighbor-joining tree of the K-th printed matrix (1 = the point estimate) as one Newick line, from the
  * averaged distances whatever -vv asks the matrix to print */
 typedef struct {
-	FILE *f;
-	const char *path;
+	const tree_file *o;
 	andi_hip_ctx *ctx; /* one for all trees, on opts.device */
 	int device_for_ctx;
 	int failed;        /* it could not be created: said once */
 } tree_out;
 
-/* one Newick line of the records J (with the support values as inner labels, if given) to f */
-static void put_tree(FILE *f, const char *path, const andi_hip_nj_join *J, const uint32_t *support, const genome *g, size_t n,
-					 int truncate) {
-	const char **names = xmalloc(n * sizeof *names);
-	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
-	size_t cap = 64 + n * 52;
-	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
-	char *text = xmalloc(cap);
-	const size_t need = andi_hip_format_newick_support(J, support, n, names, truncate, text, cap);
-	if (need >= cap)
-		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_support(J, support, n, names, truncate, text, cap);
-	if (fputs(text, f) == EOF) err(1, "%s", path);
-	free(text), free(names);
-}
-
-/* the same line with the transfer bootstrap expectation as inner labels */
-static void put_transfer_tree(FILE *f, const char *path, const andi_hip_nj_join *J, const uint32_t *depth, const uint64_t *transfer,
-							  size_t used, const genome *g, size_t n, int truncate) {
-	const char **names = xmalloc(n * sizeof *names);
-	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
-	size_t cap = 64 + n * 60;
-	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
-	char *text = xmalloc(cap);
-	const size_t need = andi_hip_format_newick_transfer(J, depth, transfer, used, n, names, truncate, text, cap);
-	if (need >= cap)
-		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_transfer(J, depth, transfer, used, n, names, truncate, text, cap);
-	if (fputs(text, f) == EOF) err(1, "%s", path);
-	free(text), free(names);
-}
-
-static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, size_t n, int model, int truncate, int k) {
+static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, const char **names, size_t n, int model, int truncate,
+					   int k) {
 	if (t->failed) return;
 	char msg[512];
 	if (!t->ctx && andi_hip_ctx_create(&t->ctx, t->device_for_ctx, msg, sizeof msg)) {
@@ -517,23 +523,8 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, si
 		free(D), free(J);
 		return;
 	}
-	put_tree(t->f, t->path, J, NULL, g, n, truncate);
+	put_newick(t->o, &(newick_src){.J = J}, names, n, truncate);
 	free(D), free(J);
-}
-
-/* the consensus tree's one Newick line to f */
-static void put_consensus(FILE *f, const char *path, const andi_hip_cons_node *nodes, size_t ninner, const genome *g, size_t n,
-						  int truncate) {
-	const char **names = xmalloc(n * sizeof *names);
-	for (size_t i = 0; i < n; i++) names[i] = g[i].name;
-	size_t cap = 64 + n * 80;
-	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
-	char *text = xmalloc(cap);
-	const size_t need = andi_hip_format_newick_consensus(nodes, n, ninner, names, truncate, text, cap);
-	if (need >= cap)
-		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_consensus(nodes, n, ninner, names, truncate, text, cap);
-	if (fputs(text, f) == EOF) err(1, "%s", path);
-	free(text), free(names);
 }
 
 /* --support (f): the tree of the point estimate with, on every inner branch, the number of bootstrap matrices whose tree has
@@ -549,16 +540,21 @@ static void put_consensus(FILE *f, const char *path, const andi_hip_cons_node *n
  * One state over the run: support_begin (the point estimate's tree), support_chunk for every chunk of replicates main
  * draws -- as matrices B, or, under --trees-only, as nothing: andi_hip_bootstrap_nj draws, estimates and joins them on the
  * device and the records are all that comes back -- and support_end (the files). */
-typedef struct {
-	FILE *f, *cf, *tf;
-	const char *path, *cpath, *tpath;
-	tree_out *t;
+typedef struct { /* what a run gives them */
 	andi_hip_ctx *ctx;
 	const genome *g;
-	size_t n, nrec, nsup, cap; /* cap: the replicates of one andi_hip_nj_batch / andi_hip_bootstrap_nj call, at most */
-	unsigned long replicates, counted;
+	const char **names;
+	size_t n;
+	unsigned long replicates;
 	int model, truncate, trees_only;
 	uint64_t seed;
+} boot_run;
+
+typedef struct {
+	boot_run r;
+	const tree_file *o; /* outs */
+	size_t nrec, nsup, cap; /* cap: the replicates of one andi_hip_nj_batch / andi_hip_bootstrap_nj call, at most */
+	unsigned long counted;
 	double *D;
 	andi_hip_nj_join *J, *Rall;
 	int64_t *bad;
@@ -568,12 +564,13 @@ typedef struct {
 	int point_ok, trans_ok, cons_ok, stopped;
 } support_state;
 
-static void support_begin(support_state *s, FILE *f, const char *path, FILE *cf, const char *cpath, FILE *tf, const char *tpath, tree_out *t,
-						  andi_hip_ctx *ctx, const andi_hip_model *M, unsigned long replicates, const genome *g, size_t n, int model,
-						  int truncate, int trees_only, uint64_t seed) {
+static void support_begin(support_state *s, const tree_file *o, const boot_run *r, const andi_hip_model *M) {
 	memset(s, 0, sizeof *s);
-	s->f = f, s->path = path, s->cf = cf, s->cpath = cpath, s->tf = tf, s->tpath = tpath, s->t = t, s->ctx = ctx, s->g = g, s->n = n;
-	s->replicates = replicates, s->model = model, s->truncate = truncate, s->trees_only = trees_only, s->seed = seed;
+	s->r = *r, s->o = o;
+	FILE *f = o[OUT_SUPPORT].f, *cf = o[OUT_CONSENSUS].f, *tf = o[OUT_TRANSFER].f;
+	const genome *g = r->g;
+	const size_t n = r->n, replicates = r->replicates;
+	const int trees_only = r->trees_only;
 	const size_t nrec = s->nrec = n == 2 ? 1 : n - 2, nsup = s->nsup = n > 3 ? n - 3 : 1;
 	/* at most 1 GiB at a time: of doubles, or -- the replicates never being matrices -- of the records kept on the host */
 	size_t chunk = ((size_t)1 << 30) / (trees_only ? nrec * sizeof(andi_hip_nj_join) : n * n * sizeof(double));
@@ -587,7 +584,7 @@ static void support_begin(support_state *s, FILE *f, const char *path, FILE *cf,
 	s->total = calloc(nsup, sizeof *s->total), s->part = calloc(nsup, sizeof *s->part), s->depth = calloc(nsup, sizeof *s->depth);
 	s->ttotal = calloc(nsup, sizeof *s->ttotal), s->tpart = calloc(nsup, sizeof *s->tpart);
 	if (!D || !s->J || !s->Rall || !s->bad || !s->skipall || !s->total || !s->part || !s->depth || !s->ttotal || !s->tpart ||
-		((f || tf) && andi_hip_distances(M, n, model, D)))
+		((f || tf) && andi_hip_distances(M, n, r->model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
 	s->point_ok = f != NULL, s->trans_ok = tf != NULL, s->cons_ok = cf != NULL;
 	for (size_t i = 0; i < n && (s->point_ok || s->trans_ok); i++)
@@ -598,36 +595,37 @@ static void support_begin(support_state *s, FILE *f, const char *path, FILE *cf,
 				s->point_ok = s->trans_ok = 0;
 				break;
 			}
-	if ((s->point_ok || s->trans_ok) && andi_hip_nj(ctx, D, n, s->J)) {
-		if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+	if ((s->point_ok || s->trans_ok) && andi_hip_nj(r->ctx, D, n, s->J)) {
+		if (f) soft_warnx("No support values: %s", andi_hip_last_error(r->ctx));
+		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(r->ctx));
 		s->point_ok = s->trans_ok = 0;
 	}
 }
 
 /* replicates start ... start + count - 1: their matrices B (count * n * n models), or NULL under --trees-only */
 static void support_chunk(support_state *s, unsigned long start, size_t count, const andi_hip_model *B, const andi_hip_model *M) {
-	const size_t n = s->n, nrec = s->nrec;
-	const genome *g = s->g;
-	andi_hip_ctx *ctx = s->ctx;
+	const size_t n = s->r.n, nrec = s->nrec;
+	const genome *g = s->r.g;
+	andi_hip_ctx *ctx = s->r.ctx;
+	FILE *f = s->o[OUT_SUPPORT].f, *cf = s->o[OUT_CONSENSUS].f, *tf = s->o[OUT_TRANSFER].f;
 	for (unsigned long first = start; first < start + count && !s->stopped; first += s->cap) {
 		const size_t c = start + count - first < s->cap ? start + count - first : s->cap;
-		andi_hip_nj_join *R = s->cf ? s->Rall + first * nrec : s->Rall;
-		uint8_t *skip = s->cf ? s->skipall + first : s->skipall;
+		andi_hip_nj_join *R = cf ? s->Rall + first * nrec : s->Rall;
+		uint8_t *skip = cf ? s->skipall + first : s->skipall;
 		int failed;
-		if (s->trees_only) {
-			failed = andi_hip_bootstrap_nj(ctx, M, n, s->model, s->seed, first, c, R, s->bad, NULL);
+		if (s->r.trees_only) {
+			failed = andi_hip_bootstrap_nj(ctx, M, n, s->r.model, s->r.seed, first, c, R, s->bad, NULL);
 		} else {
 			for (size_t k = 0; k < c; k++)
-				if (andi_hip_distances(B + (first - start + k) * n * n, n, s->model, s->D + k * n * n))
+				if (andi_hip_distances(B + (first - start + k) * n * n, n, s->r.model, s->D + k * n * n))
 					err(errno, "Could not allocate enough memory for the support values.");
 			failed = andi_hip_nj_batch(ctx, s->D, n, c, R, s->bad);
 		}
 		if (failed) {
-			if (s->f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
-			if (s->cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
-			if (s->tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
-			if (!s->f && !s->cf && !s->tf) soft_warnx("No trees: %s", andi_hip_last_error(ctx));
+			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
+			if (cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
+			if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
+			if (!f && !cf && !tf) soft_warnx("No trees: %s", andi_hip_last_error(ctx));
 			s->point_ok = s->cons_ok = s->trans_ok = 0;
 			s->stopped = 1;
 			break;
@@ -637,7 +635,7 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			if (skip[k])
 				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s' is not finite.", first + (unsigned long)k + 2,
 						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name);
-			else if (s->t->f) put_tree(s->t->f, s->t->path, R + k * nrec, NULL, g, n, s->truncate);
+			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec}, s->r.names, n, s->r.truncate);
 			s->counted += !skip[k];
 		}
 		/* (whatever fails below, the replicates' lines of --tree are still written) */
@@ -660,14 +658,14 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 
 /* the files; complete = 0: the replicates were not all drawn, nothing is written */
 static void support_end(support_state *s, int complete) {
-	const size_t n = s->n;
-	const genome *g = s->g;
-	andi_hip_ctx *ctx = s->ctx;
-	const unsigned long counted = s->counted, replicates = s->replicates;
+	const size_t n = s->r.n;
+	const char **names = s->r.names;
+	andi_hip_ctx *ctx = s->r.ctx;
+	const unsigned long counted = s->counted, replicates = s->r.replicates;
 	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = 0;
 	if (s->point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_tree(s->f, s->path, s->J, s->total, g, n, s->truncate);
+		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total}, names, n, s->r.truncate);
 	}
 	if (s->trans_ok && counted == 0) {
 		soft_warnx("No transfer support: no bootstrap matrix has a tree.");
@@ -675,7 +673,8 @@ static void support_end(support_state *s, int complete) {
 	}
 	if (s->trans_ok) {
 		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_transfer_tree(s->tf, s->tpath, s->J, s->depth, s->ttotal, counted, g, n, s->truncate);
+		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted}, names, n,
+				   s->r.truncate);
 	}
 	if (s->cons_ok && counted == 0) {
 		soft_warnx("No consensus tree: no bootstrap matrix has a tree.");
@@ -693,7 +692,7 @@ static void support_end(support_state *s, int complete) {
 			soft_warnx("No consensus tree: the bootstrap matrices' trees are inconsistent.");
 		} else {
 			if (counted < replicates) soft_warnx("Consensus tree from %lu of %lu bootstrap matrices.", counted, replicates);
-			put_consensus(s->cf, s->cpath, nodes, ninner, g, n, s->truncate);
+			put_newick(&s->o[OUT_CONSENSUS], &(newick_src){.nodes = nodes, .ninner = ninner}, names, n, s->r.truncate);
 		}
 		andi_hip_free(freq), andi_hip_free(sets);
 		free(ids), free(nodes);
@@ -702,20 +701,26 @@ static void support_end(support_state *s, int complete) {
 		free(s->tpart);
 }
 
-/* the checks and warnings every input sequence gets (src/andi.c:282-310); 1 if one is shorter than a thousand nucleotides */
-static int check_genomes(const genome_list *l, int truncate) {
+/* the checks and warnings the input gets (src/andi.c:282-310): the sequences of a, then those of b (may be NULL) */
+static void check_genomes(const genome_list *a, const genome_list *b, int truncate) {
+	if (saw_non_acgt)
+		warnx("The input sequences contained characters other than acgtACGT. These were automatically "
+			  "stripped to ensure correct results.");
 	int any_short = 0;
 	const size_t limit = (INT_MAX - 1) / 2;
-	for (size_t i = 0; i < l->n; i++) {
-		const genome *g = &l->v[i];
-		if (truncate && strlen(g->name) > 10)
-			warnx("The sequence name '%s' is longer than ten characters. It will be truncated in the output "
-				  "to '%.10s'.", g->name, g->name);
-		if (g->len > limit) errx(1, "The sequence %s is too long. The technical limit is %zu.", g->name, limit);
-		if (g->len == 0) errx(1, "The sequence %s is empty.", g->name);
-		if (g->len < 1000) any_short = 1;
-	}
-	return any_short;
+	for (const genome_list *l = a; l; l = l == a ? b : NULL)
+		for (size_t i = 0; i < l->n; i++) {
+			const genome *g = &l->v[i];
+			if (truncate && strlen(g->name) > 10)
+				warnx("The sequence name '%s' is longer than ten characters. It will be truncated in the output "
+					  "to '%.10s'.", g->name, g->name);
+			if (g->len > limit) errx(1, "The sequence %s is too long. The technical limit is %zu.", g->name, limit);
+			if (g->len == 0) errx(1, "The sequence %s is empty.", g->name);
+			if (g->len < 1000) any_short = 1;
+		}
+	if (any_short)
+		soft_warnx("One of the given input sequences is shorter than a thousand nucleotides. This may result "
+				   "in inaccurate distances. Try an alignment instead.");
 }
 
 static andi_hip_seq *seq_array(const genome_list *l) {
@@ -725,21 +730,14 @@ static andi_hip_seq *seq_array(const genome_list *l) {
 }
 
 /* --reference: the queries (the FILES) against the references, the two cross blocks of the square run over both sets */
-static int run_rect(char **ref_files, size_t nref_files, char **files, size_t nfiles, int join, int verbose, int truncate,
-					int show_progress, andi_hip_opts *opts) {
+static int run_rect(const name_list *ref_files, const name_list *files, int join, int verbose, int truncate, int show_progress,
+					andi_hip_opts *opts) {
 	genome_list refs = {0}, qs = {0};
-	read_all_files(ref_files, nref_files, join, opts->host_threads, &refs);
-	read_all_files(files, nfiles, join, opts->host_threads, &qs);
+	read_all_files(ref_files->v, ref_files->n, join, opts->host_threads, &refs);
+	read_all_files(files->v, files->n, join, opts->host_threads, &qs);
 	if (refs.n == 0) errx(1, "No reference sequences given: --reference and --reference-list name no readable sequence.");
 	if (qs.n == 0) errx(1, "No query sequences given: name at least one FASTA file besides the references.");
-	if (saw_non_acgt)
-		warnx("The input sequences contained characters other than acgtACGT. These were automatically "
-			  "stripped to ensure correct results.");
-	int any_short = check_genomes(&refs, truncate);
-	any_short |= check_genomes(&qs, truncate);
-	if (any_short)
-		soft_warnx("One of the given input sequences is shorter than a thousand nucleotides. This may result "
-				   "in inaccurate distances. Try an alignment instead.");
+	check_genomes(&refs, &qs, truncate);
 	const size_t nr = refs.n, nq = qs.n;
 	if (show_progress) {
 		progress_n = nr + nq;
@@ -753,7 +751,9 @@ static int run_rect(char **ref_files, size_t nref_files, char **files, size_t nf
 	char msg[512];
 	if (andi_hip_dist_rect(MRQ, MQR, rin, nr, qin, nq, opts, msg, sizeof msg)) errx(1, "%s", msg);
 	if (show_progress) fprintf(stderr, ", done.\n");
-	print_rect(MRQ, MQR, refs.v, nr, qs.v, nq, opts->model, verbose >= 2, truncate);
+	const char **rn = name_array(refs.v, nr), **qn = name_array(qs.v, nq);
+	print_distances(MRQ, MQR, rn, nr, qn, nq, opts->model, verbose >= 2, truncate, 1);
+	free(rn), free(qn);
 	if (verbose) { /* print_coverages, src/io.c:329-338, of the query rows */
 		printf("\nCoverage:\n");
 		for (size_t q = 0; q < nq; q++) {
@@ -802,18 +802,9 @@ int main(int argc, char *argv[]) {
 	int verbose = 0, join = 0, truncate = 0;
 	unsigned long bootstrap = 0;
 	enum { P_AUTO, P_NEVER, P_ALWAYS } progress = P_AUTO;
-	char **files = NULL;
-	size_t nfiles = 0, files_cap = 0;
-	char **ref_files = NULL; /* --reference, --reference-list: the query-versus-reference mode */
-	size_t nref_files = 0, ref_cap = 0;
+	name_list files = {0}, ref_files = {0}; /* ref_files: --reference, --reference-list, the query-versus-reference mode */
 	int rect = 0, bootstrap_given = 0, trees_only = 0;
-	tree_out tree = {0};
-	const char *support_path = NULL; /* --support */
-	FILE *support_f = NULL;
-	const char *consensus_path = NULL; /* --consensus */
-	FILE *consensus_f = NULL;
-	const char *transfer_path = NULL; /* --transfer */
-	FILE *transfer_f = NULL;
+	tree_out tree = {.o = &outs[OUT_TREE]};
 
 	for (;;) {
 		int idx = 0;
@@ -824,22 +815,12 @@ int main(int argc, char *argv[]) {
 				const char *o = long_options[idx].name;
 				if (!strcmp(o, "version")) version();
 				if (!strcmp(o, "truncate-names")) truncate = 1;
-				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files, &nfiles, &files_cap);
-				if (!strcmp(o, "tree")) tree.path = optarg;
-				if (!strcmp(o, "support")) support_path = optarg;
-				if (!strcmp(o, "consensus")) consensus_path = optarg;
-				if (!strcmp(o, "transfer")) transfer_path = optarg;
+				if (!strcmp(o, "file-of-filenames")) read_file_of_filenames(optarg, &files);
+				for (int k = 0; k < OUT_COUNT; k++)
+					if (!strcmp(o, outs[k].option)) outs[k].path = optarg;
 				if (!strcmp(o, "trees-only")) trees_only = 1;
-				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files, &nref_files, &ref_cap);
-				if (!strcmp(o, "reference")) {
-					rect = 1;
-					if (nref_files == ref_cap) {
-						ref_cap = ref_cap ? ref_cap * 2 : 16;
-						ref_files = realloc(ref_files, ref_cap * sizeof *ref_files);
-						if (!ref_files) err(errno, "Out of memory");
-					}
-					ref_files[nref_files++] = strdup(optarg);
-				}
+				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files);
+				if (!strcmp(o, "reference")) rect = 1, push_name(&ref_files, optarg);
 				if (!strcmp(o, "progress")) {
 					if (!optarg || !strcasecmp(optarg, "always")) progress = P_ALWAYS;
 					else if (!strcasecmp(optarg, "auto")) progress = P_AUTO;
@@ -907,66 +888,40 @@ int main(int argc, char *argv[]) {
 			default: usage(EXIT_FAILURE);
 		}
 	}
-	for (int i = optind; i < argc; i++) {
-		if (nfiles == files_cap) {
-			files_cap = files_cap ? files_cap * 2 : 16;
-			files = realloc(files, files_cap * sizeof *files);
-			if (!files) err(errno, "Out of memory");
-		}
-		files[nfiles++] = strdup(argv[i]);
-	}
+	for (int i = optind; i < argc; i++) push_name(&files, argv[i]);
 	if (rect && bootstrap_given) errx(1, "Bootstrapping (-b) is not available together with --reference or --reference-list.");
-	if (rect && tree.path) errx(1, "A tree (--tree) is not available together with --reference or --reference-list.");
-	if (rect && support_path) errx(1, "Support values (--support) are not available together with --reference or --reference-list.");
-	if (support_path && !bootstrap) errx(1, "Support values (--support) need bootstrap matrices: give -b N with N of at least 2.");
-	if (rect && consensus_path) errx(1, "A consensus tree (--consensus) is not available together with --reference or --reference-list.");
-	if (consensus_path && !bootstrap) errx(1, "A consensus tree (--consensus) needs bootstrap matrices: give -b N with N of at least 2.");
-	if (rect && transfer_path) errx(1, "Transfer support (--transfer) is not available together with --reference or --reference-list.");
-	if (transfer_path && !bootstrap) errx(1, "Transfer support (--transfer) needs bootstrap matrices: give -b N with N of at least 2.");
+	int any_out = 0;
+	for (int k = 0; k < OUT_COUNT; k++) {
+		if (!outs[k].path) continue;
+		any_out = 1;
+		if (rect) errx(1, "%s", outs[k].with_reference);
+		if (!bootstrap && outs[k].without_bootstrap) errx(1, "%s", outs[k].without_bootstrap);
+	}
 	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
-	if (trees_only && !tree.path && !support_path && !consensus_path && !transfer_path)
+	if (trees_only && !any_out)
 		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
-	if (tree.path && !(tree.f = fopen(tree.path, "w"))) err(1, "%s", tree.path);
-	if (support_path && !(support_f = fopen(support_path, "w"))) err(1, "%s", support_path);
-	if (consensus_path && !(consensus_f = fopen(consensus_path, "w"))) err(1, "%s", consensus_path);
-	if (transfer_path && !(transfer_f = fopen(transfer_path, "w"))) err(1, "%s", transfer_path);
+	for (int k = 0; k < OUT_COUNT; k++)
+		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
 	tree.device_for_ctx = opts.device;
-	if (join && nfiles == 0) errx(1, "In join mode at least one filename needs to be supplied.");
-	if (nfiles < (size_t)(join && !rect ? 2 : 1)) {
+	if (join && files.n == 0) errx(1, "In join mode at least one filename needs to be supplied.");
+	if (files.n < (size_t)(join && !rect ? 2 : 1)) {
 		if (isatty(STDIN_FILENO)) usage(EXIT_FAILURE);
-		files = realloc(files, (nfiles + 1) * sizeof *files);
-		files[nfiles++] = strdup("-");
+		push_name(&files, "-");
 	}
 
 	/* ANDI_HIP_CLI_TRACE=1: where the wall time goes -- reading the input, the matrix, printing it (stderr; scripts/full_size.py --cli) */
 	if (progress == P_AUTO && rect) progress = isatty(STDERR_FILENO) ? P_ALWAYS : P_NEVER;
-	if (rect) return run_rect(ref_files, nref_files, files, nfiles, join, verbose, truncate, progress == P_ALWAYS, &opts);
+	if (rect) return run_rect(&ref_files, &files, join, verbose, truncate, progress == P_ALWAYS, &opts);
 	const int cli_trace = getenv("ANDI_HIP_CLI_TRACE") != NULL;
 	struct timespec ts0, ts1, ts2, ts3;
 	clock_gettime(CLOCK_MONOTONIC, &ts0);
 	genome_list all = {0};
-	read_all_files(files, nfiles, join, opts.host_threads, &all);
+	read_all_files(files.v, files.n, join, opts.host_threads, &all);
 	clock_gettime(CLOCK_MONOTONIC, &ts1);
 	const size_t n = all.n;
 	if (n < 2)
 		errx(1, "I am truly sorry, but with less than two sequences (%zu given) there is nothing to compare.", n);
-	if (saw_non_acgt)
-		warnx("The input sequences contained characters other than acgtACGT. These were automatically "
-			  "stripped to ensure correct results.");
-	int any_short = 0;
-	const size_t limit = (INT_MAX - 1) / 2;
-	for (size_t i = 0; i < n; i++) {
-		const genome *g = &all.v[i];
-		if (truncate && strlen(g->name) > 10)
-			warnx("The sequence name '%s' is longer than ten characters. It will be truncated in the output "
-				  "to '%.10s'.", g->name, g->name);
-		if (g->len > limit) errx(1, "The sequence %s is too long. The technical limit is %zu.", g->name, limit);
-		if (g->len == 0) errx(1, "The sequence %s is empty.", g->name);
-		if (g->len < 1000) any_short = 1;
-	}
-	if (any_short)
-		soft_warnx("One of the given input sequences is shorter than a thousand nucleotides. This may result "
-				   "in inaccurate distances. Try an alignment instead.");
+	check_genomes(&all, NULL, truncate);
 
 	if (progress == P_AUTO) progress = isatty(STDERR_FILENO) ? P_ALWAYS : P_NEVER;
 	if (progress == P_ALWAYS) {
@@ -979,18 +934,15 @@ int main(int argc, char *argv[]) {
 	if (SIZE_MAX / sizeof(andi_hip_model) / n < n) errx(1, "Comparison is limited to fewer sequences (%zu given).", n);
 	andi_hip_model *M = malloc(n * n * sizeof *M);
 	if (!M) err(errno, "Could not allocate enough memory for the comparison matrix. Try using --join or --low-memory.");
-	andi_hip_seq *in = xmalloc(n * sizeof *in);
-	for (size_t i = 0; i < n; i++) {
-		in[i].seq = all.v[i].seq;
-		in[i].len = all.v[i].len;
-	}
+	andi_hip_seq *in = seq_array(&all);
 	char msg[512];
 	if (andi_hip_dist_matrix(M, in, n, &opts, msg, sizeof msg)) errx(1, "%s", msg);
 	if (progress == P_ALWAYS) fprintf(stderr, ", done.\n");
 	clock_gettime(CLOCK_MONOTONIC, &ts2);
 
-	print_matrix(M, all.v, n, opts.model, verbose >= 2, truncate, 1);
-	if (tree.f) write_tree(&tree, M, all.v, n, opts.model, truncate, 1);
+	const char **names = name_array(all.v, n);
+	print_distances(M, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 1);
+	if (tree.o->f) write_tree(&tree, M, all.v, names, n, opts.model, truncate, 1);
 	if (cli_trace) {
 		fflush(stdout);
 		clock_gettime(CLOCK_MONOTONIC, &ts3);
@@ -998,7 +950,7 @@ int main(int argc, char *argv[]) {
 		size_t nt_total = 0;
 		for (size_t i = 0; i < n; i++) nt_total += all.v[i].len;
 		fprintf(stderr, "andi-hip trace: %zu sequences, %zu nucleotides from %zu files: ingest %.3f s, matrix %.3f s, print %.3f s\n", n, nt_total,
-				nfiles, SECS(ts0, ts1), SECS(ts1, ts2), SECS(ts2, ts3));
+				files.n, SECS(ts0, ts1), SECS(ts1, ts2), SECS(ts2, ts3));
 	}
 	if (verbose) { /* print_coverages, src/io.c:329-338 */
 		printf("\nCoverage:\n");
@@ -1020,7 +972,7 @@ int main(int argc, char *argv[]) {
 		andi_hip_model *B = trees_only ? NULL : malloc(chunk * n * n * sizeof *B);
 		/* the reference seeds its generator from the clock; ANDI_HIP_SEED=k draws the same matrices on every run */
 		const uint64_t seed = getenv("ANDI_HIP_SEED") ? strtoull(getenv("ANDI_HIP_SEED"), NULL, 10) : (uint64_t)time(NULL);
-		const int trees = support_f || consensus_f || transfer_f || trees_only;
+		const int trees = outs[OUT_SUPPORT].f || outs[OUT_CONSENSUS].f || outs[OUT_TRANSFER].f || trees_only;
 		support_state st;
 		int begun = 0, ok = 1;
 		if ((!trees_only && !B) || andi_hip_ctx_create(&ctx, opts.device, msg, sizeof msg)) ok = 0;
@@ -1032,14 +984,15 @@ int main(int argc, char *argv[]) {
 					break;
 				}
 				for (size_t b = 0; b < c; b++) {
-					print_matrix(B + b * n * n, all.v, n, opts.model, verbose >= 2, truncate, 0);
-					if (tree.f && !trees) write_tree(&tree, B + b * n * n, all.v, n, opts.model, truncate, (int)(first + b) + 2);
+					print_distances(B + b * n * n, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 0);
+					if (tree.o->f && !trees) write_tree(&tree, B + b * n * n, all.v, names, n, opts.model, truncate, (int)(first + b) + 2);
 				}
 			}
 			if (!trees) continue;
-			if (!begun)
-				support_begin(&st, support_f, support_path, consensus_f, consensus_path, transfer_f, transfer_path, &tree, ctx, M, bootstrap,
-							  all.v, n, opts.model, truncate, trees_only, seed);
+			if (!begun) {
+				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed};
+				support_begin(&st, outs, &run, M);
+			}
 			begun = 1;
 			support_chunk(&st, first, c, B, M);
 		}
@@ -1049,11 +1002,10 @@ int main(int argc, char *argv[]) {
 		free(B);
 	}
 	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
-	if (tree.f && fclose(tree.f)) err(1, "%s", tree.path);
-	if (support_f && fclose(support_f)) err(1, "%s", support_path);
-	if (consensus_f && fclose(consensus_f)) err(1, "%s", consensus_path);
-	if (transfer_f && fclose(transfer_f)) err(1, "%s", transfer_path);
+	for (int k = 0; k < OUT_COUNT; k++)
+		if (outs[k].f && fclose(outs[k].f)) err(1, "%s", outs[k].path);
 	free(M);
 	free(in);
+	free(names);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;
 }

@@ -191,6 +191,42 @@ def test_cli_refuses_a_tree_of_the_reference_table(tmp_path):
     assert "Bootstrapping (-b) is not available together with --reference" in p.stderr.decode()
 
 
+_WITH_REFERENCE = " not available together with --reference or --reference-list."
+_NEEDS_B = " bootstrap matrices: give -b N with N of at least 2."
+_REFUSALS = [  # (options beside the two FASTA files, with a reference?, the line on stderr behind "andi-hip: ")
+    (["-b", "2"], True, "Bootstrapping (-b) is" + _WITH_REFERENCE),
+    (["--tree=T"], True, "A tree (--tree) is" + _WITH_REFERENCE),
+    (["--support=S"], True, "Support values (--support) are" + _WITH_REFERENCE),
+    (["--support=S"], False, "Support values (--support) need" + _NEEDS_B),
+    (["--consensus=C"], True, "A consensus tree (--consensus) is" + _WITH_REFERENCE),
+    (["--consensus=C"], False, "A consensus tree (--consensus) needs" + _NEEDS_B),
+    (["--transfer=X"], True, "Transfer support (--transfer) is" + _WITH_REFERENCE),
+    (["--transfer=X"], False, "Transfer support (--transfer) needs" + _NEEDS_B),
+    (["--trees-only", "--tree=T"], False,
+     "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2."),
+    (["--trees-only", "-b", "2"], False, "Trees without matrices (--trees-only) need somewhere to go: give at least one of "
+                                         "--tree, --support, --consensus, --transfer."),
+    # more than one violation: the first of the order above is the one reported
+    (["--support=S", "--consensus=C"], True, "Support values (--support) are" + _WITH_REFERENCE),
+    (["--consensus=C", "--support=S"], False, "Support values (--support) need" + _NEEDS_B),
+    (["-b", "2", "--transfer=X", "--tree=T"], True, "Bootstrapping (-b) is" + _WITH_REFERENCE),
+    (["--transfer=X", "--tree=T"], True, "A tree (--tree) is" + _WITH_REFERENCE),
+    (["--trees-only", "--transfer=X"], False, "Transfer support (--transfer) needs" + _NEEDS_B),
+]
+
+
+@pytest.mark.parametrize("options,reference,line", _REFUSALS)
+def test_cli_refuses_with_these_words_and_in_this_order(tmp_path, options, reference, line):
+    a = _fasta(tmp_path / "a.fa", "a", "ACGT" * 400)
+    b = _fasta(tmp_path / "b.fa", "b", "ACGA" * 400)
+    args = [o[:o.index("=") + 1] + str(tmp_path / o[o.index("=") + 1:]) if "=" in o else o for o in options]
+    args += ["--reference=" + a, b] if reference else [a, b]
+    p = subprocess.run([CLI] + args, capture_output=True, timeout=60)
+    # the whole line and the exit status; nothing printed, no file made (the refusals come before any file is opened)
+    assert (p.returncode, p.stdout, p.stderr.decode()) == (1, b"", "andi-hip: " + line + "\n")
+    assert sorted(os.listdir(tmp_path)) == ["a.fa", "b.fa"]
+
+
 def test_cli_fails_on_an_unwritable_tree_file(tmp_path):
     a = _fasta(tmp_path / "a.fa", "a", "ACGT" * 400)
     b = _fasta(tmp_path / "b.fa", "b", "ACGA" * 400)
