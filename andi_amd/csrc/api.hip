@@ -715,7 +715,7 @@ int andi_hip_esa_build_index_batch(andi_hip_ctx *ctx, andi_hip_esa *const *esas,
 		HIP_TRY(ctx, hipEventSynchronize(ctx->ib_done)); // the previous batch's items have been copied
 	}
 	auto *items = (AndiIndexBatchItem *)ctx->ib_host;
-	int32_t max_n = 0;
+	int32_t max_n = 0, max_n_shallow = 0; // (shallow: a table of K < ANDI_CLOSED_RUN_K, andi_launch_index_build_batch)
 	for (size_t k = 0; k < count; ++k) {
 		andi_hip_esa *e = esas[k];
 		if (!e) {
@@ -728,11 +728,12 @@ int andi_hip_esa_build_index_batch(andi_hip_ctx *ctx, andi_hip_esa *const *esas,
 		items[k].rec2 = e->rec_valid ? e->rec2 : nullptr;
 		items[k].single_ext = andi_index_single_ext(ctx->queries_hint, e->rec_valid);
 		max_n = std::max(max_n, e->n);
+		if (e->deepK < ANDI_CLOSED_RUN_K) max_n_shallow = std::max(max_n_shallow, e->n);
 	}
 	Timed t(ctx, 0);
 	hipError_t err = hipMemcpyAsync(ctx->ib_dev, ctx->ib_host, count * sizeof(AndiIndexBatchItem), hipMemcpyHostToDevice, ctx->stream);
 	if (err == hipSuccess) err = hipEventRecord(ctx->ib_done, ctx->stream);
-	if (err == hipSuccess) err = andi_launch_index_build_batch((const AndiIndexBatchItem *)ctx->ib_dev, (uint32_t)count, max_n, ctx->stream);
+	if (err == hipSuccess) err = andi_launch_index_build_batch((const AndiIndexBatchItem *)ctx->ib_dev, (uint32_t)count, max_n, max_n_shallow, ctx->stream);
 	t.stop();
 	if (err == hipSuccess) err = hipEventRecord(ctx->built, ctx->stream);
 	if (err != hipSuccess) return fail(ctx, "andi_hip_esa_build_index_batch", err);

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #define ANDI_MIN_LEVELS 6 /* 64^5 > 2^30 covers every int32-indexable text */
+#define ANDI_CLOSED_RUN_K 9 /* a probe table at least this deep sees every closed run of words of up to 8 nucleotides in its own build; a shallower one takes k_closed_runs besides */
 
 // 64-ary pyramid of minima over LCP[0..n]; lv[0] is LCP itself.
 struct MinTree {
@@ -49,8 +50,9 @@ size_t andi_min_tree_entries(int32_t n);
 // 0 plain, 1 extended (13 symbols behind the occurrence, gathered from the text), 2 short extended (up to 4, from the
 // device sorter's keys: no gather; subjects whose suffix array came from the host get plain entries)
 int andi_index_single_ext(size_t queries, bool sorted_on_device);
-// the scan indexes of `count` subjects (device array of items) in two launches; max_n = the longest text
-hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, hipStream_t st);
+// the scan indexes of `count` subjects (device array of items) in two launches; max_n = the longest text; max_n_shallow = the
+// longest text among the items with deepK < ANDI_CLOSED_RUN_K (0: none), whose closed runs take a third, small launch (esa_build.hip: k_closed_runs)
+hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, int32_t max_n_shallow, hipStream_t st);
 // (scan_lane.hip) packed symbols of the items' texts, `bytes` source bytes each at most (shorter texts stop at their own end)
 hipError_t andi_launch_pack_symbols_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t bytes, hipStream_t st);
 hipError_t andi_launch_pack_planes_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t max_n, hipStream_t st); // N0 -> P of every item

@@ -326,9 +326,12 @@ __device__ __forceinline__ uint32_t rec_lcp_code(uint32_t code, uint32_t a, int 
 //      match is the longer of its common prefixes with the two neighbours,
 //      FINAL(l, unique, SA index);
 //  (c) it detects what can make the reference's 10-mer table differ from the true
-//      longest match: a prefix w (1..8 ACGT characters) whose every occurrence is
-//      followed by the same separator, at least twice (SURVEY.md appendix C.11;
-//      this test is a superset of the exact condition) -> flags[0].
+//      longest match: a word w (1..8 ACGT characters) that occurs at least twice and
+//      whose every occurrence is followed by the same separator, '!' or ';' (SURVEY.md
+//      appendix C.11; this test is a superset of the exact condition) -> flags[0].
+//      A record says what follows its suffix's nucleotides only where there are fewer
+//      than K of them, so the gaps see the words shorter than K: all of them from
+//      K = 9 on; for a shallower table k_closed_runs below looks for the rest.
 // The codes owned by consecutive gaps are consecutive ranges (absent codes of gap r,
 // then the K-mer of suffix r), so a block of 256 gaps owns one contiguous piece of the
 // table.  The block writes that piece together, entry t by thread t mod 256 (coalesced,
@@ -590,6 +593,44 @@ __global__ __launch_bounds__(PT_BLOCK) void k_probe_table_batch(const AndiIndexB
 	probe_table_block(it.N0, it.SA, it.rec, it.rec2, it.deep, it.flags, it.n, it.deepK, it.single_ext, blockIdx.x);
 }
 
+// (c) for a table shallower than CR_K: the closed runs of words of K..8 nucleotides, which records capped at K cannot show.
+// One thread per suffix makes records CR_K deep (suffix_rec: its 8-byte read holds 15 symbols) for itself and its
+// neighbours and applies the gaps' test: the first suffix that starts with w is "w <sep>", so are all that follow it as far
+// as they start with w, and there are at least two.  Only texts of up to 4^8 characters get such tables (test hooks aside):
+// n threads, two or three gathers each.
+#define CR_K ANDI_CLOSED_RUN_K
+__device__ __forceinline__ void closed_runs(const uint8_t *__restrict__ N0, const int32_t *__restrict__ SA, int32_t *__restrict__ flags,
+											int32_t n, int32_t r) {
+	const uint32_t R = suffix_rec(N0, SA, r, CR_K);
+	const uint32_t k = REC_V(R), sp = REC_SEP(R);
+	if (k < 1 || k > 8 || (sp != 1 && sp != 2)) return;
+	if (r > 0 && rec_lcp(suffix_rec(N0, SA, r - 1, CR_K), R, CR_K) >= k) return; // not the first suffix that starts with w
+	int32_t j = r;
+	uint32_t X = 0;
+	bool behind = false; // X is the record of a suffix behind the run
+	while (j + 1 < n) {
+		X = suffix_rec(N0, SA, j + 1, CR_K);
+		if (REC_V(X) == k && REC_SEP(X) == sp && rec_lcp(R, X, CR_K) == k) {
+			++j;
+		} else {
+			behind = true;
+			break;
+		}
+	}
+	if (j > r && (!behind || rec_lcp(R, X, CR_K) < k)) flags[0] = 1; // (pinned host memory: plain idempotent store)
+}
+
+__global__ __launch_bounds__(256) void k_closed_runs(const uint8_t *__restrict__ N0, const int32_t *__restrict__ SA, int32_t *__restrict__ flags, int32_t n) {
+	const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (r < n) closed_runs(N0, SA, flags, n, (int32_t)r);
+}
+
+__global__ __launch_bounds__(256) void k_closed_runs_batch(const AndiIndexBatchItem *__restrict__ items) {
+	const AndiIndexBatchItem it = items[blockIdx.y];
+	const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+	if (it.deepK < CR_K && r < it.n) closed_runs(it.N0, it.SA, it.flags, it.n, (int32_t)r);
+}
+
 // ---------------------------------------------------------------- host side
 size_t andi_min_tree_entries(int32_t n) {
 	size_t total = 0;
@@ -629,10 +670,14 @@ hipError_t andi_launch_index_build(const EsaBuildArgs &a, int single_ext, hipStr
 	k_probe_table<<<(unsigned)(((int64_t)n + 1 + PT_TILE - 1) / PT_TILE), PT_BLOCK, 0, st>>>(a.N0, a.SA, a.rec, a.rec2, a.deep, a.flags, n,
 																				  a.deepK, single_ext);
 	CHECK_LAUNCH();
+	if (a.deepK < CR_K) { // (tables of K >= 9 -- texts of more than 4^8 characters -- launch nothing more: their gaps see every word of up to 8)
+		k_closed_runs<<<(unsigned)(((int64_t)n + 255) / 256), 256, 0, st>>>(a.N0, a.SA, a.flags, n);
+		CHECK_LAUNCH();
+	}
 	return hipSuccess;
 }
 
-hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, hipStream_t st) {
+hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, int32_t max_n_shallow, hipStream_t st) {
 	if (count == 0) return hipSuccess;
 	hipError_t e = andi_launch_pack_symbols_batch(d_items, count, (size_t)max_n + 1 + 64, st);
 	if (e != hipSuccess) return e;
@@ -641,6 +686,10 @@ hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint
 	const dim3 grid((unsigned)(((int64_t)max_n + 1 + PT_TILE - 1) / PT_TILE), count);
 	k_probe_table_batch<<<grid, PT_BLOCK, 0, st>>>(d_items);
 	CHECK_LAUNCH();
+	if (max_n_shallow > 0) { // some tables are shallower than CR_K: their closed runs (a batch without such a table launches nothing more)
+		k_closed_runs_batch<<<dim3((unsigned)(((int64_t)max_n_shallow + 255) / 256), count), 256, 0, st>>>(d_items);
+		CHECK_LAUNCH();
+	}
 	return hipSuccess;
 }
 

@@ -220,65 +220,17 @@ def test_probe_table_entries_against_brute_force(ctx, name, seq):
     does, whether exactly one suffix starts with that prefix, and which.  The expectation is made from the text
     alone by counting, per length, how many positions start with each prefix."""
     import andi_amd
+    import probe_table_model as ptm
     E = andi_amd.Esa(ctx, seq, sa="device")
     K, table = E.download_index()
-    rs = np.frombuffer(E.RS, np.uint8)
-    n = len(rs)
-    SA = E.SA
-    rank = np.empty(n, np.int64)
-    rank[SA] = np.arange(n)
-    code = np.full(256, 4, np.int64)
-    code[list(b"ACGT")] = [0, 1, 2, 3]
-    t = np.concatenate([code[rs], np.full(K, 4, np.int64)])
-    # count[l][c], where[l][c]: positions that start with the l-mer c (ACGT only), and one of them
-    count, where = [None], [None]
-    pref = np.zeros(n, np.int64)
-    ok = np.ones(n, bool)
-    for l in range(1, K + 1):
-        ok &= t[l - 1:l - 1 + n] < 4
-        pref = pref * 4 + np.minimum(t[l - 1:l - 1 + n], 3)
-        count.append(np.bincount(pref[ok], minlength=4 ** l))
-        w = np.zeros(4 ** l, np.int64)
-        w[pref[ok]] = np.nonzero(ok)[0]
-        where.append(w)
-    codes = np.arange(4 ** K)
-    x, y = table[:, 0].astype(np.int64), table[:, 1].astype(np.int64)
-    kind = y & 3
-    occurs = count[K]
-    assert ((kind == 1) == (occurs == 1)).all() and ((kind == 2) == (occurs > 1)).all() and (kind != 3).all()
-    once = occurs == 1
-    assert (x[once] == where[K][once]).all()
-    form = E.single_form()
-    if form:  # the nucleotides behind the one occurrence, as many as the entry's form holds (andi_dev.h: DEEP_SINGLE)
-        room = 13 if form == 1 else min(4, 16 - K)
-        pos = x[once]
-        nval, ext = (y[once] >> 2) & 15, y[once] >> 6
-        want_n = np.zeros(len(pos), np.int64)
-        want_e = np.zeros(len(pos), np.int64)
-        alive = np.ones(len(pos), bool)
-        tt = np.concatenate([t, np.full(16, 4, np.int64)])
-        for j in range(room):
-            sym = tt[pos + K + j]
-            alive &= sym < 4
-            want_n += alive
-            want_e |= np.where(alive, sym, 0) << (2 * j)
-        assert (nval == want_n).all() and (ext == want_e).all(), name
-    many = occurs > 1
-    assert ((y[many] >> 8) + 1 == occurs[many]).all()
-    first = np.full(4 ** K, n, np.int64)  # smallest suffix-array index among the positions of each K-mer
-    full = np.nonzero(ok)[0]
-    np.minimum.at(first, pref[full], rank[full])
-    assert (x[many] == first[many]).all()
-    absent = occurs == 0
-    best = np.zeros(4 ** K, np.int64)
-    cnt = np.full(4 ** K, n, np.int64)  # (the empty prefix: every suffix shares it)
-    one = np.zeros(4 ** K, np.int64)
-    for l in range(1, K):
-        c = codes >> (2 * (K - l))
-        hit = count[l][c] > 0
-        best[hit], cnt[hit], one[hit] = l, count[l][c][hit], where[l][c][hit]
-    assert ((y[absent] >> 8) == best[absent]).all()
-    uniq = (cnt == 1) & absent
-    assert ((((y >> 2) & 1) == 1)[absent] == uniq[absent]).all()
-    assert (x[uniq] == rank[one[uniq]]).all()
+    M = ptm.entries(E.RS, K)  # (tests/probe_table_model.py; tests/test_probe_table_gpu.py has every depth, form and launch path)
+    x, y, x_defined = ptm.table(E.RS, M, E.single_form())
+    assert ((table[:, 1] & 3) == M.kind).all() and not (M.kind == 3).any()
+    # the whole second word: a K-mer that occurs once -- what its form holds of the nucleotides behind it (andi_dev.h:
+    # DEEP_SINGLE); several times -- occurrences - 1; an absent one -- the length of its longest prefix that occurs and
+    # whether one suffix alone has it
+    assert (table[:, 1] == y).all(), name
+    # the first word: the position, the first suffix-array index, the index of the one suffix (an absent K-mer whose
+    # longest prefix several suffixes share: not read by the scan)
+    assert (table[:, 0] == x)[x_defined].all(), name
     E.close()
