@@ -4,7 +4,7 @@
 // Layout in HBM per subject (all hipMalloc'ed, see api.hip):
 //   S    uint8[n+1+PAD]  RS, NUL at n, zero padding so wide loads never fault
 //   SA   int32[n]        suffix array (host-built, src/esa.c:294-304)
-// scan index (what the anchor scan uses; built by k_pack_symbols + k_probe_table):
+// scan index (what the anchor scan uses; built by k_pack_text + k_probe_table):
 //   deep uint2[4^K]      probe table: for every ACGT K-mer the outcome of the
 //                        longest-match search as far as the K-mer alone decides
 //                        it, so most probes cost one random access

@@ -781,6 +781,33 @@ int andi_hip_esa_download_index(andi_hip_ctx *ctx, const andi_hip_esa *e, uint32
 	return 0;
 }
 
+#ifdef ANDI_TEST_HOOKS
+// Test hooks (the suite's library only; not part of include/andi_hip.h).
+// The packed text of a subject as it lies on the device: the first nib_bytes of N0 and of N1, and p_words words of the
+// bit-sliced text from the block of padding in front of P on (P itself starts at word 3).  Any pointer may be NULL.
+extern "C" int andi_hip_test_download_text(andi_hip_ctx *ctx, const andi_hip_esa *e, uint8_t *N0, uint8_t *N1, size_t nib_bytes, uint32_t *P,
+										   size_t p_words) {
+	if (!ctx || !e) return 1;
+	if (nib_bytes > e->cap / 2 + 1 + ANDI_NIB_BACK || p_words > 3 * ((e->cap + 1 + 4096) / 32 + 4)) {
+		ctx->err = "andi_hip_test_download_text: more than the buffers hold";
+		return 1;
+	}
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (N0) HIP_TRY(ctx, hipMemcpy(N0, e->N0, nib_bytes, hipMemcpyDeviceToHost));
+	if (N1) HIP_TRY(ctx, hipMemcpy(N1, e->N1, nib_bytes, hipMemcpyDeviceToHost));
+	if (P) HIP_TRY(ctx, hipMemcpy(P, e->Praw, p_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+// The index build's pack kernel alone on a staged subject (no table: the text may be any bytes); forms: bit 0 with N1, bit 1 with P
+extern "C" int andi_hip_test_pack_text(andi_hip_ctx *ctx, andi_hip_esa *e, int forms) {
+	if (!ctx || !e) return 1;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, andi_launch_pack_text(e->S, (size_t)e->n + 1 + 64, e->N0, (forms & 1) ? e->N1 : nullptr, (forms & 2) ? e->P : nullptr, e->flags + 1,
+									   ctx->stream));
+	return 0;
+}
+#endif
+
 int andi_hip_esa_single_form(const andi_hip_esa *e) { return e && e->index_built ? e->deep_ext : 0; }
 
 void andi_hip_esa_free(andi_hip_ctx *ctx, andi_hip_esa *e) {

@@ -33,7 +33,7 @@ struct EsaBuildArgs {
 
 // one subject of a batched scan-index build
 struct AndiIndexBatchItem {
-	const uint8_t *S;  // text (pack_symbols' source)
+	const uint8_t *S;  // text (the pack kernel's source)
 	const int32_t *SA;
 	uint2 *deep;
 	uint8_t *N0, *N1;
@@ -53,9 +53,10 @@ int andi_index_single_ext(size_t queries, bool sorted_on_device);
 // the scan indexes of `count` subjects (device array of items) in two launches; max_n = the longest text; max_n_shallow = the
 // longest text among the items with deepK < ANDI_CLOSED_RUN_K (0: none), whose closed runs take a third, small launch (esa_build.hip: k_closed_runs)
 hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, int32_t max_n_shallow, hipStream_t st);
-// (scan_lane.hip) packed symbols of the items' texts, `bytes` source bytes each at most (shorter texts stop at their own end)
-hipError_t andi_launch_pack_symbols_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t bytes, hipStream_t st);
-hipError_t andi_launch_pack_planes_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t max_n, hipStream_t st); // N0 -> P of every item
+// (scan_lane.hip) a text in one pass as 4-bit symbols in both alignments and bit-sliced: symbols = n + 1 + 64 (the text, its
+// NUL, 64 bytes of the zero padding behind it); N1 and P may be null.  _batch: every item's, the grid sized by the longest
+hipError_t andi_launch_pack_text(const uint8_t *src, size_t symbols, uint8_t *N0, uint8_t *N1, uint32_t *P, int32_t *foreign, hipStream_t st);
+hipError_t andi_launch_pack_text_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t max_n, hipStream_t st);
 // reference arrays LCP, CLD, FVC, tab (esa_init_LCP/_CLD/_FVC/_cache)
 hipError_t andi_launch_esa_build(const EsaBuildArgs &a, hipStream_t st);
 // scan index: deep, side, flags from S and SA alone

@@ -14,7 +14,7 @@
 //   K2b child_table   CLD from nearest-smaller-value searches  (src/esa.c:312-363)
 //   K4  kmer_table    4^10 interval table, one thread per 10-mer (src/esa.c:73-215)
 // and the scan index (see "scan index" below), built from RS and SA alone:
-//   pack_symbols (scan_lane.hip)  the text as 4-bit symbols in two alignments (N0, N1)
+//   pack_text (scan_lane.hip)     the text as 4-bit symbols in two alignments (N0, N1) and bit-sliced (P)
 //   probe_table                   4^K outcome table: a block takes 512 suffix-array gaps, makes the suffixes'
 //                                 records itself (one 8-byte gather each) and writes the table piece it owns
 // (the suffix array itself comes from the host or from sa_device.hip)
@@ -341,7 +341,7 @@ __device__ __forceinline__ uint32_t rec_lcp_code(uint32_t code, uint32_t a, int 
 #define PT_BLOCK 256
 #endif
 #ifndef PT_GAPS
-#define PT_GAPS 3 /* gaps per thread (independent loads in flight): bench set 2.91 / 2.33 / 2.24 / 2.54 ms at 1 / 2 / 3 / 4 (round 6; LDS 20.6 KB per block at 3) */
+#define PT_GAPS 3 /* gaps per thread (independent loads in flight): bench set 2.91 / 2.33 / 2.24 / 2.54 ms at 1 / 2 / 3 / 4 (round 6; LDS 18.4 KB per block at 3: 8 blocks per CU) */
 #endif
 #define PT_TILE (PT_BLOCK * PT_GAPS)
 #define PT_WORDS (PT_TILE / 64) /* 64-bit ballots that cover the tile: gap i = u * PT_BLOCK + thread is bit i & 63 of word i >> 6 */
@@ -371,7 +371,7 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 												  int32_t *__restrict__ flags, int32_t n, int K, int single_ext, uint32_t block) {
 	__shared__ uint32_t s_first[PT_TILE];   // first code a gap owns (one that owns nothing: its successor's)
 	__shared__ uint32_t s_absent[PT_TILE];  // number of absent codes it owns (they come first)
-	__shared__ uint32_t s_h[PT_TILE + 2];   // s_h[k + 1]: characters the suffixes r0 + k - 1 and r0 + k share
+	__shared__ uint8_t s_h[PT_TILE + 2];    // s_h[k + 1]: characters the suffixes r0 + k - 1 and r0 + k share (<= K <= 13: bytes -- as words the block's LDS, 21 136 bytes, kept it at 7 blocks per CU; 18 832 allow 8, all 32 wave slots)
 	__shared__ uint2 s_present[PT_TILE];    // entry of the K-mer of suffix r, if the gap owns it
 	__shared__ uint32_t s_rec[PT_TILE + 5]; // rec of the suffixes r0 - 2 .. r0 + PT_TILE (two more words: the run test below reads ahead of what it uses)
 	__shared__ uint64_t s_some[PT_WORDS];   // gap i owns entries
@@ -404,8 +404,8 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 		return k < PT_TILE + 3 ? s_rec[k] : make_rec(j);
 	};
 	const uint32_t full = (uint32_t)K;
-	if (threadIdx.x == 0) s_h[0] = r0 >= 2 ? rec_lcp(s_rec[0], s_rec[1], K) : 0u;
-	if (threadIdx.x == 1) s_h[PT_TILE + 1] = r0 + PT_TILE < (uint32_t)n ? rec_lcp(s_rec[PT_TILE + 1], s_rec[PT_TILE + 2], K) : 0u;
+	if (threadIdx.x == 0) s_h[0] = (uint8_t)(r0 >= 2 ? rec_lcp(s_rec[0], s_rec[1], K) : 0u);
+	if (threadIdx.x == 1) s_h[PT_TILE + 1] = (uint8_t)(r0 + PT_TILE < (uint32_t)n ? rec_lcp(s_rec[PT_TILE + 1], s_rec[PT_TILE + 2], K) : 0u);
 
 	uint32_t counts[PT_GAPS], firsts[PT_GAPS];
 #pragma unroll
@@ -421,7 +421,7 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 		const uint32_t L = hasL ? Lr : 0u, R = hasR ? Rr : 0u;
 		const uint32_t sa_r = hasR ? (uint32_t)SA[r] : 0u;
 		const uint32_t h = (hasL && hasR) ? rec_lcp(L, R, K) : 0u;
-		s_h[i + 1] = h;
+		s_h[i + 1] = (uint8_t)h;
 		uint32_t absent = 0, first = 1u << (2 * K), owns_present = 0; // (gaps beyond the text: behind every code)
 		uint2 present = make_uint2(0, 0);
 
@@ -661,11 +661,9 @@ int andi_index_single_ext(size_t queries, bool sorted_on_device) { // queries: h
 hipError_t andi_launch_index_build(const EsaBuildArgs &a, int single_ext, hipStream_t st) {
 	const int32_t n = a.n;
 	hipError_t e;
-	// symbols for the lane scan: the text, its NUL and 64 bytes of the zero padding behind it
-	e = andi_launch_pack_symbols(a.S, (size_t)n + 1 + 64, a.N0, a.N1, a.flags + 1, st);
-	if (e != hipSuccess) return e;
-	// ... and bit-sliced, for the wavefront kernels' streams (round 6: once per subject here, not in front of every launch of theirs)
-	if (a.P) e = andi_launch_pack_planes(a.N0, (size_t)n + 1 + 64, a.P, st);
+	// symbols for the lane scan -- the text, its NUL and 64 bytes of the zero padding behind it -- and, from the same read of
+	// the text, bit-sliced for the wavefront kernels' streams (round 6: once per subject here, not in front of every launch of theirs)
+	e = andi_launch_pack_text(a.S, (size_t)n + 1 + 64, a.N0, a.N1, a.P, a.flags + 1, st);
 	if (e != hipSuccess) return e;
 	k_probe_table<<<(unsigned)(((int64_t)n + 1 + PT_TILE - 1) / PT_TILE), PT_BLOCK, 0, st>>>(a.N0, a.SA, a.rec, a.rec2, a.deep, a.flags, n,
 																				  a.deepK, single_ext);
@@ -679,9 +677,7 @@ hipError_t andi_launch_index_build(const EsaBuildArgs &a, int single_ext, hipStr
 
 hipError_t andi_launch_index_build_batch(const AndiIndexBatchItem *d_items, uint32_t count, int32_t max_n, int32_t max_n_shallow, hipStream_t st) {
 	if (count == 0) return hipSuccess;
-	hipError_t e = andi_launch_pack_symbols_batch(d_items, count, (size_t)max_n + 1 + 64, st);
-	if (e != hipSuccess) return e;
-	e = andi_launch_pack_planes_batch(d_items, count, (size_t)max_n, st);
+	hipError_t e = andi_launch_pack_text_batch(d_items, count, (size_t)max_n, st);
 	if (e != hipSuccess) return e;
 	const dim3 grid((unsigned)(((int64_t)max_n + 1 + PT_TILE - 1) / PT_TILE), count);
 	k_probe_table_batch<<<grid, PT_BLOCK, 0, st>>>(d_items);

@@ -1180,19 +1180,55 @@ __global__ __launch_bounds__(256) void k_pack_planes(const uint4 *__restrict__ N
 	planes[3 * j] = o[0], planes[3 * j + 1] = o[1], planes[3 * j + 2] = o[2];
 }
 
-__global__ __launch_bounds__(256) void k_pack_planes_batch(const AndiIndexBatchItem *__restrict__ items) {
-	const AndiIndexBatchItem it = items[blockIdx.y];
-	if (!it.P || !it.N0) return;
-	const int64_t blocks = ((int64_t)it.n + 1 + 64 + 31) / 32, j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= blocks) return;
-	uint32_t o[3];
-	planes_of(((const uint4 *)it.N0)[j], o);
-	it.P[3 * j] = o[0], it.P[3 * j + 1] = o[1], it.P[3 * j + 2] = o[2];
+// The text of a subject in one pass (the index build): a thread reads 32 bytes once and writes them in all three forms --
+// two words of N0, two of N1 (word 0 takes its first nibble from the byte in front of the thread's 32) and the three
+// plane words of P.  Lengths as k_pack_symbols and k_pack_planes over `symbols` bytes give them: (symbols + 15) / 16 pairs
+// of words of N0 and N1, (symbols + 31) / 32 blocks of P; where the last block's second pair lies behind the pairs, N0 and
+// N1 keep what they hold there, and P takes those 16 symbols from the text's zero padding (NUL symbols, all ones: what
+// the buffers are filled with when they are allocated).  src is readable 31 bytes beyond `symbols` (ANDI_PAD).
+__device__ __forceinline__ void pack_text_block(const uint8_t *__restrict__ src, int64_t symbols, uint8_t *__restrict__ N0,
+												uint8_t *__restrict__ N1, uint32_t *__restrict__ P, int32_t *__restrict__ foreign) {
+	__shared__ uint8_t lut[256]; // symbol | 0x80 if the byte is outside the alphabet
+	lut[threadIdx.x] = (uint8_t)(symbol_of((uint8_t)threadIdx.x) | (in_alphabet((uint8_t)threadIdx.x) ? 0u : 0x80u));
+	__syncthreads();
+	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (32 * j >= symbols) return;
+	const bool whole = 32 * j + 16 < symbols; // the second pair of words is one of the (symbols + 15) / 16
+	const uint4 lo = ld_u128_unaligned((g_u8p)src + 32 * j), hi = ld_u128_unaligned((g_u8p)src + 32 * j + 16);
+	const uint32_t in[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+	uint32_t w[4] = {0, 0, 0, 0}, bad = 0, bad_hi = 0;
+#pragma unroll
+	for (int k = 0; k < 32; ++k) {
+		const uint32_t e = lut[(in[k >> 2] >> (8 * (k & 3))) & 0xffu];
+		w[k >> 3] |= (e & 7u) << (4 * (k & 7));
+		if (k < 16) bad |= e; else bad_hi |= e;
+	}
+	if (whole) bad |= bad_hi;
+	if ((bad & 0x80u) && foreign) *foreign = 1; // a byte outside the alphabet: only the byte kernels are exact
+	const uint32_t prev = j ? (lut[src[32 * j - 1]] & 7u) : 7u;
+	const uint2 a0 = make_uint2(w[0], w[1]), a1 = make_uint2((w[0] << 4) | prev, (w[1] << 4) | (w[0] >> 28));
+	if (whole) {
+		((uint4 *)N0)[j] = make_uint4(a0.x, a0.y, w[2], w[3]);
+		if (N1) ((uint4 *)N1)[j] = make_uint4(a1.x, a1.y, (w[2] << 4) | (w[1] >> 28), (w[3] << 4) | (w[2] >> 28));
+	} else {
+		((uint2 *)N0)[2 * j] = a0;
+		if (N1) ((uint2 *)N1)[2 * j] = a1;
+	}
+	if (P) {
+		uint32_t o[3];
+		planes_of(make_uint4(w[0], w[1], w[2], w[3]), o);
+		P[3 * j] = o[0], P[3 * j + 1] = o[1], P[3 * j + 2] = o[2];
+	}
 }
 
-__global__ __launch_bounds__(256) void k_pack_symbols_batch(const AndiIndexBatchItem *__restrict__ items) {
+__global__ __launch_bounds__(256) void k_pack_text(const uint8_t *__restrict__ src, int64_t symbols, uint8_t *__restrict__ N0,
+												   uint8_t *__restrict__ N1, uint32_t *__restrict__ P, int32_t *__restrict__ foreign) {
+	pack_text_block(src, symbols, N0, N1, P, foreign);
+}
+
+__global__ __launch_bounds__(256) void k_pack_text_batch(const AndiIndexBatchItem *__restrict__ items) {
 	const AndiIndexBatchItem it = items[blockIdx.y];
-	pack_symbols_block(it.S, ((int64_t)it.n + 1 + 64 + 15) / 16, (uint2 *)it.N0, (uint2 *)it.N1, it.flags + 1);
+	pack_text_block(it.S, (int64_t)it.n + 1 + 64, it.N0, it.N1, it.P, it.flags + 1);
 }
 
 } // namespace
@@ -1214,10 +1250,19 @@ hipError_t andi_launch_lane_quad_small(const ScanArgs &a0, uint32_t count, hipSt
 }
 #else
 
-hipError_t andi_launch_pack_symbols_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t bytes, hipStream_t st) {
-	const int64_t pairs = (int64_t)((bytes + 15) / 16);
-	if (pairs == 0 || count == 0) return hipSuccess;
-	k_pack_symbols_batch<<<dim3((unsigned)((pairs + 255) / 256), count), 256, 0, st>>>(d_items);
+hipError_t andi_launch_pack_text_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t max_n, hipStream_t st) {
+	const int64_t blocks = (int64_t)((max_n + 1 + 64 + 31) / 32);
+	if (count == 0) return hipSuccess;
+	k_pack_text_batch<<<dim3((unsigned)((blocks + 255) / 256), count), 256, 0, st>>>(d_items);
+	CHECK_LAUNCH();
+	return hipSuccess;
+}
+
+hipError_t andi_launch_pack_text(const uint8_t *src, size_t symbols, uint8_t *N0, uint8_t *N1, uint32_t *P, int32_t *foreign,
+								 hipStream_t st) {
+	const int64_t blocks = (int64_t)((symbols + 31) / 32);
+	if (blocks == 0) return hipSuccess;
+	k_pack_text<<<(unsigned)((blocks + 255) / 256), 256, 0, st>>>(src, (int64_t)symbols, N0, N1, P, foreign);
 	CHECK_LAUNCH();
 	return hipSuccess;
 }
@@ -1234,14 +1279,6 @@ hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *
 	const int64_t blocks = (int64_t)((symbols + 31) / 32);
 	if (blocks == 0) return hipSuccess;
 	k_pack_planes<<<(unsigned)((blocks + 255) / 256), 256, 0, st>>>((const uint4 *)N0, blocks, planes);
-	CHECK_LAUNCH();
-	return hipSuccess;
-}
-
-hipError_t andi_launch_pack_planes_batch(const AndiIndexBatchItem *d_items, uint32_t count, size_t max_n, hipStream_t st) {
-	const int64_t blocks = (int64_t)((max_n + 1 + 64 + 31) / 32);
-	if (blocks == 0 || count == 0) return hipSuccess;
-	k_pack_planes_batch<<<dim3((unsigned)((blocks + 255) / 256), count), 256, 0, st>>>(d_items);
 	CHECK_LAUNCH();
 	return hipSuccess;
 }

@@ -157,6 +157,12 @@ SYMBOLS = {
     "andi_hip_timings_reset": (None, [_P]),
 }
 
+# test hooks only the suite's library exports (andi_amd/csrc/api.hip, -DANDI_TEST_HOOKS): set up where the library has them
+HOOK_SYMBOLS = {
+    "andi_hip_test_download_text": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
+    "andi_hip_test_pack_text": (C.c_int, [_P, _P, C.c_int]),
+}
+
 _lib = None
 
 
@@ -173,6 +179,11 @@ def load():
             fn = getattr(L, name)  # AttributeError if the symbol is missing
             fn.restype = res
             fn.argtypes = args
+        for name, (res, args) in HOOK_SYMBOLS.items():
+            fn = getattr(L, name, None)
+            if fn is not None:
+                fn.restype = res
+                fn.argtypes = args
         _lib = L
         import atexit
         atexit.register(L.andi_hip_trim)  # the arena's retained chunks go back before the interpreter is torn down
@@ -522,6 +533,21 @@ class Esa:
                         "esa_download_index")
         return K.value, table
 
+    def pack_text(self, forms=3):
+        """test hook: the index build's pack kernel alone on the staged text (forms: bit 0 with N1, bit 1 with P)"""
+        self.ctx._check(_hook("andi_hip_test_pack_text")(self.ctx._h, self._h, forms), "test_pack_text")
+
+    def download_text(self, beyond=16):
+        """(N0, N1, P): the text as the scan index keeps it (test hook) -- N0 and N1 as bytes: the n + 1 + 64 symbols
+        rounded up to pairs of words, and `beyond` bytes more; P as words from the block of padding in front of it on
+        (P proper starts at word 3): (n + 1 + 64 + 31) // 32 blocks of three, and beyond // 4 words more."""
+        nib = (self.n + 1 + 64 + 15) // 16 * 8 + beyond
+        N0, N1 = np.empty(nib, np.uint8), np.empty(nib, np.uint8)
+        P = np.empty(3 + 3 * ((self.n + 1 + 64 + 31) // 32) + beyond // 4, np.uint32)
+        self.ctx._check(_hook("andi_hip_test_download_text")(self.ctx._h, self._h, N0.ctypes.data, N1.ctypes.data, nib,
+                                                             P.ctypes.data, len(P)), "test_download_text")
+        return N0, N1, P
+
     def single_form(self):
         """form of the probe table's entries of K-mers that occur once: 0 plain, 1 extended, 2 short extended"""
         return load().andi_hip_esa_single_form(self._h)
@@ -599,6 +625,13 @@ def match_positions(esa: Esa, queries: Queries, qidx, first, count, cached=True)
     esa.ctx._check(load().andi_hip_match_positions(esa.ctx._h, esa._h, queries._h, qidx, first, count,
                                                    int(cached), out.ctypes.data), "match_positions")
     return out
+
+
+def _hook(name):
+    fn = getattr(load(), name, None)
+    if fn is None:
+        raise AndiHipError(name + ": a test hook, not in " + LIB_PATH)
+    return fn
 
 
 def build_indexes(ctx: Context, esas):
