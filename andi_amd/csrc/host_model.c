@@ -629,3 +629,174 @@ done:
 	free(first), free(kids), free(fill), free(stack), free(next), free(seen);
 	return need;
 }
+
+/* ------------------------------------------------------------------ */
+/* Linkage clustering: what the host makes of andi_hip_linkage's records (include/andi_hip.h) */
+/* ------------------------------------------------------------------ */
+
+/* the records are a tree over the leaves 0 .. n-1: every child a leaf or an earlier record's node, the two children
+ * differ, no node a child twice -- so node 2n - 2 is the one root and every walk from it ends */
+static int links_are_a_tree(const andi_hip_link *L, size_t n) {
+	uint8_t *child = calloc(2 * n, 1);
+	if (!child) return 0;
+	int ok = 1;
+	for (size_t s = 0; ok && s + 1 < n; s++) {
+		const int32_t ch[2] = {L[s].a, L[s].b};
+		for (int k = 0; k < 2; k++)
+			if (ch[k] < 0 || (size_t)ch[k] >= n + s || child[ch[k]]++) ok = 0;
+	}
+	free(child);
+	return ok;
+}
+
+int andi_hip_linkage_cut(const andi_hip_link *links, size_t n, double t, uint32_t *labels, size_t *nclusters) {
+	if (!links || !labels || !nclusters || n < 2 || n > 65535 || !links_are_a_tree(links, n)) return 1;
+	const size_t nodes = 2 * n - 1;
+	uint8_t *closed = calloc(nodes, 1);
+	uint32_t *top = malloc(nodes * sizeof *top), *label = malloc(nodes * sizeof *label);
+	if (!closed || !top || !label) {
+		free(closed), free(top), free(label);
+		return 1;
+	}
+	for (size_t s = 0; s + 1 < n; s++) { /* children come before their parents */
+		const size_t a = (size_t)links[s].a, b = (size_t)links[s].b;
+		closed[n + s] = links[s].height <= t && (a < n || closed[a]) && (b < n || closed[b]);
+	}
+	top[nodes - 1] = (uint32_t)(nodes - 1);
+	for (size_t s = n - 1; s-- > 0;) { /* parents before their children: top[v] is the maximal closed node above v, or v */
+		const size_t v = n + s, a = (size_t)links[s].a, b = (size_t)links[s].b;
+		top[a] = closed[v] ? top[v] : (uint32_t)a;
+		top[b] = closed[v] ? top[v] : (uint32_t)b;
+	}
+	memset(label, 0xff, nodes * sizeof *label);
+	uint32_t next = 0;
+	for (size_t i = 0; i < n; i++) {
+		if (label[top[i]] == 0xffffffffu) label[top[i]] = next++;
+		labels[i] = label[top[i]];
+	}
+	*nclusters = next;
+	free(closed), free(top), free(label);
+	return 0;
+}
+
+/* the members of every cluster in ascending leaf id: first[c] .. first[c + 1] of order (a counting sort); NULL on bad
+ * labels or an empty cluster */
+static uint32_t *cluster_members(const uint32_t *labels, size_t n, size_t nclusters, uint32_t **first_out) {
+	if (nclusters == 0 || nclusters > n) return NULL;
+	uint32_t *first = calloc(nclusters + 1, sizeof *first), *order = malloc(n * sizeof *order), *fill = malloc(nclusters * sizeof *fill);
+	int ok = first && order && fill;
+	for (size_t i = 0; ok && i < n; i++) {
+		if (labels[i] >= nclusters) ok = 0;
+		else first[labels[i] + 1]++;
+	}
+	for (size_t c = 0; ok && c < nclusters; c++) {
+		if (first[c + 1] == 0) ok = 0;
+		first[c + 1] += first[c], fill[c] = first[c];
+	}
+	for (size_t i = 0; ok && i < n; i++) order[fill[labels[i]]++] = (uint32_t)i;
+	free(fill);
+	if (!ok) {
+		free(first), free(order);
+		return NULL;
+	}
+	*first_out = first;
+	return order;
+}
+
+int andi_hip_cluster_medoids(const double *D, size_t n, const uint32_t *labels, size_t nclusters, uint32_t *medoid) {
+	if (!D || !labels || !medoid || n < 2 || n > 65535) return 1;
+	for (size_t i = 0; i < n; i++)
+		for (size_t j = i + 1; j < n; j++)
+			if (D[i * n + j] == -INFINITY) return 1;
+	uint32_t *first = NULL, *order = cluster_members(labels, n, nclusters, &first);
+	if (!order) return 1;
+	for (size_t c = 0; c < nclusters; c++) {
+		double best = NAN;
+		for (uint32_t p = first[c]; p < first[c + 1]; p++) {
+			const size_t i = order[p];
+			double sum = 0.0;
+			for (uint32_t q = first[c]; q < first[c + 1]; q++) {
+				const size_t j = order[q];
+				const double d = i == j ? 0.0 : i < j ? D[i * n + j] : D[j * n + i];
+				sum += isnan(d) ? INFINITY : d;
+			}
+			if (p == first[c] || (isnan(best) && !isnan(sum)) || sum < best) best = sum, medoid[c] = (uint32_t)i;
+		}
+	}
+	free(first), free(order);
+	return 0;
+}
+
+int andi_hip_cluster_stability(const uint32_t *labels, size_t nclusters, const uint32_t *rep_labels, size_t n, size_t count,
+							   uint32_t *stability) {
+	if (!labels || !rep_labels || !stability || n < 2 || n > 65535) return 1;
+	uint32_t *first = NULL, *order = cluster_members(labels, n, nclusters, &first);
+	uint32_t *members = malloc(n * sizeof *members); /* of every cluster of one replicate */
+	int bad = !order || !members;
+	for (size_t c = 0; !bad && c < nclusters; c++) stability[c] = 0;
+	for (size_t k = 0; !bad && k < count; k++) {
+		const uint32_t *R = rep_labels + k * n;
+		memset(members, 0, n * sizeof *members);
+		for (size_t i = 0; i < n; i++) {
+			if (R[i] >= n) {
+				bad = 1;
+				break;
+			}
+			members[R[i]]++;
+		}
+		for (size_t c = 0; !bad && c < nclusters; c++) {
+			const uint32_t l = R[order[first[c]]];
+			int same = members[l] == first[c + 1] - first[c];
+			for (uint32_t p = first[c] + 1; same && p < first[c + 1]; p++) same = R[order[p]] == l;
+			stability[c] += (uint32_t)same;
+		}
+	}
+	free(first), free(order), free(members);
+	return bad;
+}
+
+size_t andi_hip_format_newick_linkage(const andi_hip_link *links, size_t n, const char *const *names, int truncate_names,
+									  char *out, size_t cap) {
+	sink o = {out, cap, 0};
+	if (out && cap) out[0] = '\0';
+	if (!links || !names || n < 2 || n > 65535 || !links_are_a_tree(links, n)) return 0;
+#define LINK_HEIGHT(v) ((size_t)(v) < n ? 0.0 : links[(size_t)(v) - n].height)
+	for (size_t s = 0; s + 1 < n; s++) /* every branch: the parent's height less the child's */
+		if (!isfinite(links[s].height - LINK_HEIGHT(links[s].a)) || !isfinite(links[s].height - LINK_HEIGHT(links[s].b))) return 0;
+	typedef struct {
+		uint32_t rec; /* record of this node */
+		int next;     /* its next child */
+		double len;   /* its own branch length */
+	} frame;
+	frame *stack = malloc(n * sizeof *stack);
+	if (!stack) return 0;
+	size_t top = 0;
+	stack[top++] = (frame){(uint32_t)(n - 2), 0, 0.0};
+	put(&o, "(");
+	while (top) {
+		frame *f = &stack[top - 1];
+		const andi_hip_link *r = &links[f->rec];
+		if (f->next == 2) {
+			const double len = f->len;
+			top--;
+			if (top) put(&o, "):%.8g", len);
+			else put(&o, ");\n");
+			continue;
+		}
+		const int k = f->next++;
+		if (k) put(&o, ",");
+		const size_t child = (size_t)(k == 0 ? r->a : r->b);
+		const double len = r->height - LINK_HEIGHT(child);
+		if (child < n) {
+			put_leaf(&o, names[child], truncate_names);
+			put(&o, ":%.8g", len);
+		} else {
+			stack[top++] = (frame){(uint32_t)(child - n), 0, len};
+			put(&o, "(");
+		}
+	}
+#undef LINK_HEIGHT
+	free(stack);
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
+	return o.len;
+}

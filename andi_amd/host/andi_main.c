@@ -387,6 +387,13 @@ static void usage(int status) {
 		"                       of replicates.  These trees come from the portable estimator (its own logarithm, within\n"
 		"                       an ulp of the C library's); in a rare tie they can differ from those of a run that\n"
 		"                       prints the matrices\n"
+		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
+		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
+		"                       matrix); a pair without a distance counts as farther apart than any other\n"
+		"      --clusters=FILE  With --threshold: write the clusters of the first matrix to FILE, one line per sequence:\n"
+		"                       name, cluster, the cluster's representative (its medoid) and, with -b, the number of\n"
+		"                       bootstrap matrices whose clustering has exactly this cluster\n"
+		"      --threshold=T    The distance up to which --clusters joins, in the units of the printed matrix\n"
 		"      --truncate-names Truncate names to ten characters\n"
 		"  -v, --verbose        Prints additional information\n"
 		"  -h, --help           Display this help and exit\n"
@@ -701,6 +708,133 @@ static void support_end(support_state *s, int complete) {
 		free(s->tpart);
 }
 
+/* --dendrogram, --clusters: agglomerative clustering (andi_hip_linkage) of every printed matrix, from the averaged distances
+ * whatever -vv asks the matrix to print.  A pair without a distance does not stop it: it is the pair farthest apart.
+ * cluster_point takes the point estimate (its dendrogram line, its clusters at the threshold and their medoids),
+ * cluster_chunk every chunk of bootstrap matrices main draws (one andi_hip_linkage_batch call: their dendrogram lines, and
+ * how many of their clusterings hold each cluster of the point estimate; the chunks' counts add up), cluster_end writes
+ * the clusters. */
+typedef struct {
+	const char *dendro_path, *clusters_path;
+	FILE *df, *cf;
+	int method, have_threshold;
+	double threshold;
+	andi_hip_ctx *ctx; /* one for all matrices, on opts.device */
+	int device_for_ctx;
+	int failed; /* it could not be created: said once */
+	uint32_t *labels, *medoid, *stability;
+	size_t nclusters;
+	int clusters_ok; /* the point estimate has clusters */
+	unsigned long counted; /* the bootstrap matrices behind the stability */
+} cluster_out;
+
+static int cluster_ctx(cluster_out *c) {
+	char msg[512];
+	if (c->failed) return 0;
+	if (!c->ctx && andi_hip_ctx_create(&c->ctx, c->device_for_ctx, msg, sizeof msg)) {
+		c->failed = 1, c->ctx = NULL;
+		soft_warnx("No clustering: %s", msg);
+		return 0;
+	}
+	return 1;
+}
+
+/* the dendrogram of the K-th printed matrix, one Newick line */
+static void put_dendrogram(const cluster_out *c, const andi_hip_link *Z, const char **names, size_t n, int truncate, unsigned long k) {
+	size_t cap = 64 + n * 40;
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
+	char *text = xmalloc(cap);
+	size_t need = andi_hip_format_newick_linkage(Z, n, names, truncate, text, cap);
+	if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), need = andi_hip_format_newick_linkage(Z, n, names, truncate, text, cap);
+	if (need == 0) soft_warnx("No dendrogram for matrix %lu: a branch is not finite (a pair of sequences has no distance).", k);
+	else if (fputs(text, c->df) == EOF) err(1, "%s", c->dendro_path);
+	free(text);
+}
+
+static void cluster_point(cluster_out *c, const andi_hip_model *M, const char **names, size_t n, int model, int truncate) {
+	if (!cluster_ctx(c)) return;
+	double *D = malloc(n * n * sizeof *D);
+	andi_hip_link *Z = malloc(n * sizeof *Z);
+	c->labels = malloc(n * sizeof *c->labels), c->medoid = malloc(n * sizeof *c->medoid), c->stability = calloc(n, sizeof *c->stability);
+	if (!D || !Z || !c->labels || !c->medoid || !c->stability || andi_hip_distances(M, n, model, D))
+		err(errno, "Could not allocate enough memory for the clustering.");
+	if (andi_hip_linkage(c->ctx, D, n, c->method, Z)) {
+		if (c->df) soft_warnx("No dendrogram for matrix 1: %s", andi_hip_last_error(c->ctx));
+		if (c->cf) soft_warnx("No clusters: %s", andi_hip_last_error(c->ctx));
+	} else {
+		if (c->df) put_dendrogram(c, Z, names, n, truncate, 1);
+		if (c->cf) {
+			if (andi_hip_linkage_cut(Z, n, c->threshold, c->labels, &c->nclusters) ||
+				andi_hip_cluster_medoids(D, n, c->labels, c->nclusters, c->medoid))
+				soft_warnx("No clusters: the linkage tree is inconsistent.");
+			else c->clusters_ok = 1;
+		}
+	}
+	free(D), free(Z);
+}
+
+/* bootstrap matrices first ... first + count - 1 (the printed matrices first + 2 ...) */
+static void cluster_chunk(cluster_out *c, const andi_hip_model *B, unsigned long first, size_t count, const genome *g, const char **names,
+						  size_t n, int model, int truncate) {
+	if (!cluster_ctx(c) || (!c->df && !c->clusters_ok)) return;
+	double *D = malloc(count * n * n * sizeof *D);
+	andi_hip_link *Z = malloc(count * n * sizeof *Z);
+	int64_t *bad = malloc(count * sizeof *bad);
+	uint32_t *rep = malloc(count * n * sizeof *rep), *part = malloc(n * sizeof *part);
+	if (!D || !Z || !bad || !rep || !part) err(errno, "Could not allocate enough memory for the clustering.");
+	for (size_t k = 0; k < count; k++)
+		if (andi_hip_distances(B + k * n * n, n, model, D + k * n * n)) err(errno, "Could not allocate enough memory for the clustering.");
+	if (andi_hip_linkage_batch(c->ctx, D, n, count, c->method, Z, bad)) {
+		soft_warnx("No clustering of the bootstrap matrices: %s", andi_hip_last_error(c->ctx));
+		c->failed = 1;
+	} else {
+		size_t used = 0;
+		for (size_t k = 0; k < count; k++) {
+			const andi_hip_link *Zk = Z + k * (n - 1);
+			size_t theirs = 0;
+			if (bad[k] >= 0) {
+				soft_warnx("No clustering of matrix %lu: the distance of '%s' and '%s' is -inf.", first + (unsigned long)k + 2,
+						   g[bad[k] / (int64_t)n].name, g[bad[k] % (int64_t)n].name);
+				continue;
+			}
+			if (c->df) put_dendrogram(c, Zk, names, n, truncate, first + (unsigned long)k + 2);
+			if (c->clusters_ok && !andi_hip_linkage_cut(Zk, n, c->threshold, rep + used * n, &theirs)) used++;
+		}
+		if (c->clusters_ok && used) {
+			if (andi_hip_cluster_stability(c->labels, c->nclusters, rep, n, used, part)) {
+				soft_warnx("No stability: the clusterings are inconsistent.");
+				c->failed = 1;
+			} else {
+				for (size_t k = 0; k < c->nclusters; k++) c->stability[k] += part[k];
+				c->counted += used;
+			}
+		}
+	}
+	free(D), free(Z), free(bad), free(rep), free(part);
+}
+
+/* the clusters file; replicates: the bootstrap matrices of the run (0: no stability column), complete: all were drawn */
+static void cluster_end(cluster_out *c, const char **names, size_t n, int truncate, unsigned long replicates, int complete) {
+	if (c->cf && c->clusters_ok) {
+		const int stab = replicates > 0 && complete && !c->failed;
+		if (replicates > 0 && !stab) soft_warnx("No stability: the bootstrap matrices were not all clustered.");
+		else if (stab && c->counted < replicates) soft_warnx("Stability from %lu of %lu bootstrap matrices.", c->counted, replicates);
+		const int w = truncate ? 10 : INT_MAX;
+		int bad = fprintf(c->cf, "#name\tcluster\trepresentative%s\n", stab ? "\tstability" : "") < 0;
+		for (size_t i = 0; i < n && !bad; i++) {
+			const uint32_t l = c->labels[i];
+			bad |= fprintf(c->cf, "%.*s\t%u\t%.*s", w, names[i], (unsigned)l + 1, w, names[c->medoid[l]]) < 0;
+			if (stab) bad |= fprintf(c->cf, "\t%u", (unsigned)c->stability[l]) < 0;
+			bad |= fputc('\n', c->cf) == EOF;
+		}
+		if (bad) err(1, "%s", c->clusters_path);
+	}
+	free(c->labels), free(c->medoid), free(c->stability);
+	if (c->ctx) andi_hip_ctx_destroy(c->ctx);
+	if (c->df && fclose(c->df)) err(1, "%s", c->dendro_path);
+	if (c->cf && fclose(c->cf)) err(1, "%s", c->clusters_path);
+}
+
 /* the checks and warnings the input gets (src/andi.c:282-310): the sequences of a, then those of b (may be NULL) */
 static void check_genomes(const genome_list *a, const genome_list *b, int truncate) {
 	if (saw_non_acgt)
@@ -780,6 +914,10 @@ int main(int argc, char *argv[]) {
 												 {"consensus", required_argument, NULL, 0},
 												 {"transfer", required_argument, NULL, 0},
 												 {"trees-only", no_argument, NULL, 0},
+												 {"linkage", required_argument, NULL, 0},
+												 {"dendrogram", required_argument, NULL, 0},
+												 {"clusters", required_argument, NULL, 0},
+												 {"threshold", required_argument, NULL, 0},
 												 {"help", no_argument, NULL, 'h'},
 												 {"verbose", no_argument, NULL, 'v'},
 												 {"join", no_argument, NULL, 'j'},
@@ -805,6 +943,7 @@ int main(int argc, char *argv[]) {
 	name_list files = {0}, ref_files = {0}; /* ref_files: --reference, --reference-list, the query-versus-reference mode */
 	int rect = 0, bootstrap_given = 0, trees_only = 0;
 	tree_out tree = {.o = &outs[OUT_TREE]};
+	cluster_out clus = {.method = ANDI_LINK_AVERAGE};
 
 	for (;;) {
 		int idx = 0;
@@ -819,6 +958,22 @@ int main(int argc, char *argv[]) {
 				for (int k = 0; k < OUT_COUNT; k++)
 					if (!strcmp(o, outs[k].option)) outs[k].path = optarg;
 				if (!strcmp(o, "trees-only")) trees_only = 1;
+				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
+				if (!strcmp(o, "clusters")) clus.clusters_path = optarg;
+				if (!strcmp(o, "linkage")) {
+					if (!strcasecmp(optarg, "single")) clus.method = ANDI_LINK_SINGLE;
+					else if (!strcasecmp(optarg, "complete")) clus.method = ANDI_LINK_COMPLETE;
+					else if (!strcasecmp(optarg, "average")) clus.method = ANDI_LINK_AVERAGE;
+					else errx(1, "Expected one of 'single', 'complete' or 'average' for --linkage, but '%s' was given.", optarg);
+				}
+				if (!strcmp(o, "threshold")) {
+					errno = 0;
+					char *end;
+					clus.threshold = strtod(optarg, &end);
+					if (errno || end == optarg || *end || !isfinite(clus.threshold) || clus.threshold < 0.0)
+						errx(1, "Expected a finite number of at least 0 for --threshold, but '%s' was given.", optarg);
+					clus.have_threshold = 1;
+				}
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files);
 				if (!strcmp(o, "reference")) rect = 1, push_name(&ref_files, optarg);
 				if (!strcmp(o, "progress")) {
@@ -897,12 +1052,20 @@ int main(int argc, char *argv[]) {
 		if (rect) errx(1, "%s", outs[k].with_reference);
 		if (!bootstrap && outs[k].without_bootstrap) errx(1, "%s", outs[k].without_bootstrap);
 	}
+	if (clus.dendro_path && rect) errx(1, "A dendrogram (--dendrogram) is" WITH_REFERENCE);
+	if (clus.clusters_path && rect) errx(1, "Clusters (--clusters) are" WITH_REFERENCE);
+	if (clus.dendro_path && trees_only) errx(1, "A dendrogram (--dendrogram) is not available together with --trees-only: there are no matrices to cluster.");
+	if (clus.clusters_path && trees_only) errx(1, "Clusters (--clusters) are not available together with --trees-only: there are no matrices to cluster.");
+	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
+	if (clus.have_threshold && !clus.clusters_path) errx(1, "A threshold (--threshold) needs somewhere to go: give --clusters=FILE.");
 	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
 	if (trees_only && !any_out)
 		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
-	tree.device_for_ctx = opts.device;
+	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
+	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
+	tree.device_for_ctx = clus.device_for_ctx = opts.device;
 	if (join && files.n == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (files.n < (size_t)(join && !rect ? 2 : 1)) {
 		if (isatty(STDIN_FILENO)) usage(EXIT_FAILURE);
@@ -943,6 +1106,7 @@ int main(int argc, char *argv[]) {
 	const char **names = name_array(all.v, n);
 	print_distances(M, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 1);
 	if (tree.o->f) write_tree(&tree, M, all.v, names, n, opts.model, truncate, 1);
+	if (clus.df || clus.cf) cluster_point(&clus, M, names, n, opts.model, truncate);
 	if (cli_trace) {
 		fflush(stdout);
 		clock_gettime(CLOCK_MONOTONIC, &ts3);
@@ -988,6 +1152,7 @@ int main(int argc, char *argv[]) {
 					if (tree.o->f && !trees) write_tree(&tree, B + b * n * n, all.v, names, n, opts.model, truncate, (int)(first + b) + 2);
 				}
 			}
+			if (clus.df || clus.cf) cluster_chunk(&clus, B, first, c, all.v, names, n, opts.model, truncate);
 			if (!trees) continue;
 			if (!begun) {
 				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed};
@@ -998,9 +1163,11 @@ int main(int argc, char *argv[]) {
 		}
 		if (!ok) soft_warnx("Bootstrapping failed.");
 		if (begun) support_end(&st, ok);
+		if (clus.df || clus.cf) cluster_end(&clus, names, n, truncate, bootstrap, ok);
 		if (ctx) andi_hip_ctx_destroy(ctx);
 		free(B);
 	}
+	if (!bootstrap && (clus.df || clus.cf)) cluster_end(&clus, names, n, truncate, 0, 1);
 	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].f && fclose(outs[k].f)) err(1, "%s", outs[k].path);

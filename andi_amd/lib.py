@@ -121,6 +121,12 @@ SYMBOLS = {
     "andi_hip_nj_splits": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_size_t), C.POINTER(_P),
                                      C.POINTER(_P)]),
     "andi_hip_nj_transfer": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, _P]),
+    "andi_hip_linkage": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "andi_hip_linkage_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P]),
+    "andi_hip_linkage_cut": (C.c_int, [_P, C.c_size_t, C.c_double, _P, C.POINTER(C.c_size_t)]),
+    "andi_hip_cluster_medoids": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
+    "andi_hip_cluster_stability": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P]),
+    "andi_hip_format_newick_linkage": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -406,6 +412,75 @@ def newick_consensus(nodes, names, truncate_names=False):
         out = C.create_string_buffer(cap)
         need = load().andi_hip_format_newick_consensus(nodes.ctypes.data, n, ninner, cn, int(truncate_names),
                                                        C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
+
+
+# andi_hip_link: a record of a linkage tree (SciPy's Z: the two node ids, the leaves below the new node, its height)
+LINK = np.dtype([("a", "<i4"), ("b", "<i4"), ("size", "<u4"), ("pad", "<u4"), ("height", "<f8")])
+LINKAGE_METHODS = {"single": 0, "complete": 1, "average": 2}
+
+
+def _method(method):
+    if method not in LINKAGE_METHODS:
+        raise ValueError("linkage method %r: expected single, complete or average" % (method,))
+    return LINKAGE_METHODS[method]
+
+
+def linkage_cut(Z, t):
+    """Flat clusters of linkage's records at threshold t (andi_hip_linkage_cut): uint32[n] labels, 0-based, numbered by
+    first appearance in ascending leaf id.  No GPU is touched."""
+    Z = np.ascontiguousarray(Z, dtype=LINK)
+    n = len(Z) + 1
+    labels = np.zeros(n, np.uint32)
+    k = C.c_size_t(0)
+    if load().andi_hip_linkage_cut(Z.ctypes.data, n, float(t), labels.ctypes.data, C.byref(k)):
+        raise AndiHipError("andi_hip_linkage_cut: malformed records")
+    return labels
+
+
+def cluster_medoids(D, labels):
+    """One representative per cluster (andi_hip_cluster_medoids): uint32[nclusters], the member with the least summed
+    distance to its cluster.  No GPU is touched."""
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    n = D.shape[0]
+    assert D.shape == (n, n) and labels.shape == (n,)
+    k = int(labels.max()) + 1
+    medoid = np.zeros(k, np.uint32)
+    if load().andi_hip_cluster_medoids(D.ctypes.data, n, labels.ctypes.data, k, medoid.ctypes.data):
+        raise AndiHipError("andi_hip_cluster_medoids: bad arguments")
+    return medoid
+
+
+def cluster_stability(labels, rep_labels):
+    """In how many of the replicates' clusterings rep_labels (count, n) every cluster of `labels` recurs exactly
+    (andi_hip_cluster_stability): uint32[nclusters].  No GPU is touched."""
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    rep_labels = np.ascontiguousarray(rep_labels, dtype=np.uint32)
+    n = len(labels)
+    assert rep_labels.ndim == 2 and rep_labels.shape[1] == n
+    k = int(labels.max()) + 1
+    stability = np.zeros(k, np.uint32)
+    if load().andi_hip_cluster_stability(labels.ctypes.data, k, rep_labels.ctypes.data, n, rep_labels.shape[0],
+                                         stability.ctypes.data):
+        raise AndiHipError("andi_hip_cluster_stability: bad arguments")
+    return stability
+
+
+def newick_linkage(Z, names, truncate_names=False):
+    """The Newick line (ending in ";\n") of linkage's records for the leaves `names`, a rooted dendrogram; "" for malformed
+    records and for a branch that is not finite (a height of +inf)."""
+    Z = np.ascontiguousarray(Z, dtype=LINK)
+    n = len(names)
+    assert len(Z) == n - 1
+    cn = _names(names)
+    cap = 64 + 40 * n + sum(len(x) for x in names)
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_newick_linkage(Z.ctypes.data, n, cn, int(truncate_names), C.cast(out, _P), cap)
         if need < cap:
             break
         cap = need + 1
@@ -773,6 +848,33 @@ def nj_batch(ctx: Context, Ds):
     bad = np.zeros(count, np.int64)
     ctx._check(load().andi_hip_nj_batch(ctx._h, Ds.ctypes.data, n, count, J.ctypes.data, bad.ctypes.data), "nj_batch")
     return J, bad
+
+
+def linkage(ctx: Context, D, method="average"):
+    """Agglomerative clustering of the (n, n) distances D on the device (andi_hip_linkage; only the upper triangle is
+    read, a NaN is a pair without a distance): the n - 1 records as a structured array of dtype LINK."""
+    method = _method(method)
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    Z = np.zeros(max(n - 1, 0), LINK)
+    ctx._check(load().andi_hip_linkage(ctx._h, D.ctypes.data, n, method, Z.ctypes.data), "linkage")
+    return Z
+
+
+def linkage_batch(ctx: Context, Ds, method="average"):
+    """The clustering of the (count, n, n) distances Ds in shared launches (andi_hip_linkage_batch): (Z, bad) -- Z[k] the
+    records linkage(ctx, Ds[k], method) gives, bit for bit, as a (count, n - 1) array of dtype LINK; bad[k] = -1, or
+    i * n + j of matrix k's first -inf entry, and then Z[k] is all zero."""
+    method = _method(method)
+    Ds = np.ascontiguousarray(Ds, dtype=np.float64)
+    assert Ds.ndim == 3 and Ds.shape[1] == Ds.shape[2]
+    count, n = Ds.shape[0], Ds.shape[1]
+    Z = np.zeros((count, max(n - 1, 0)), LINK)
+    bad = np.zeros(count, np.int64)
+    ctx._check(load().andi_hip_linkage_batch(ctx._h, Ds.ctypes.data, n, count, method, Z.ctypes.data,
+                                             bad.ctypes.data), "linkage_batch")
+    return Z, bad
 
 
 def nj_support(ctx: Context, J, reps, skip=None):

@@ -20,7 +20,9 @@
  * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only); and the majority-rule
  * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only);
  * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only); and bootstrap
- * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only).
+ * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only); and linkage
+ * clustering: andi_hip_linkage, andi_hip_linkage_batch, andi_hip_linkage_cut, andi_hip_cluster_medoids,
+ * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -484,6 +486,76 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
  * does not fail on size while one tree's sets fit.  Work: (n - 3)^2 * used * ceil(n / 64) word pairs.  Synchronous. */
 int andi_hip_nj_transfer(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
 						 size_t count, const uint8_t *skip, uint32_t *depth, uint64_t *transfer, uint32_t *per);
+
+/* Agglomerative (linkage) clustering of the n x n distance matrix D (host memory, row-major) on the context's device:
+ * single, complete or average linkage (UPGMA, the other mode of PHYLIP's neighbor).  Unlike neighbor-joining it takes a
+ * pair without a distance.  Writes n - 1 records.  2 <= n <= 65535; bad arguments (a NULL pointer, a method outside
+ * 0 ... 2, n out of range) fail with 1 before any HIP call.  Synchronous, on the context's stream.
+ *
+ * The result is bit-exact to this contract (tests/linkage_model.py restates it):
+ *  - input: only D[i][j] with i < j is read; those entries are mirrored, the diagonal is +0.0.  A NaN is taken as +inf
+ *    (the pair without a distance: farther than anything measurable); +inf, negative values and +-0.0 are used as they
+ *    are.  A -inf fails through the context's error, which names the first such D[i][j] in row-major order; nothing is
+ *    written then;
+ *  - leaf i has id i, size 1 and starts in slot i; step s (from 0) creates node n + s, which takes the lower slot of its
+ *    two children; the other slot leaves the active set.  These are the ids of SciPy's Z;
+ *  - a step: among the active pairs, with x the member of smaller id, the least D[x][y] by value (-0.0 == +0.0) is
+ *    joined, ties to the smaller id(x), then the smaller id(y).  A NaN (only from overflow in the average rule: inf - inf)
+ *    orders after every number, +inf included, and among NaNs the same id order decides.  With a = id(x), b = id(y):
+ *    record {a, b, n_a + n_b, 0, D[a][b]}, the height's bits those of that entry;
+ *  - the update, for every other active k, D[u][k] = D[k][u] =
+ *      single:   D[b][k] < D[a][k] ? D[b][k] : D[a][k]
+ *      complete: D[b][k] > D[a][k] ? D[b][k] : D[a][k]
+ *        (a's value on equality, which fixes the bits where +0.0 meets -0.0),
+ *      average:  ((double)n_a * D[a][k] + (double)n_b * D[b][k]) / (double)(n_a + n_b), each operation rounded, no FMA;
+ *    n_u = n_a + n_b.
+ * With ties the heights of the average rule need not ascend (nor do they under rounding): see andi_hip_linkage_cut. */
+enum { ANDI_LINK_SINGLE = 0, ANDI_LINK_COMPLETE = 1, ANDI_LINK_AVERAGE = 2 };
+/* One record of a linkage tree (andi_hip_linkage): node ids a, b (a the smaller), the leaves below the new node, the
+ * height at which it was made.  24 bytes. */
+typedef struct {
+	int32_t a, b;
+	uint32_t size, pad;
+	double height;
+} andi_hip_link;
+int andi_hip_linkage(andi_hip_ctx *ctx, const double *D, size_t n, int method, andi_hip_link *links);
+/* The clustering of `count` matrices of one n in shared launches: D is count row-major n x n matrices one after the other,
+ * links receives count * (n - 1) records, matrix k's from links + k * (n - 1) on -- bit for bit what the call above writes
+ * for D + k*n*n (the same kernels, the replicate as the grid's second dimension).  bad[k] = -1 for a usable matrix; else
+ * i*n + j of its first -inf D[i][j] (i < j, row-major order), its records are all-zero bytes, and the other matrices are
+ * not affected (andi_hip_nj_batch's rule).  Returns 0 when it ran, bad matrices or not; 1 through the context's error on
+ * a HIP error; 1 before any HIP call on bad arguments (a NULL pointer, count == 0, a method outside 0 ... 2, n outside
+ * 2 ... 65535).  The matrices are taken in groups that fit the device; the results do not depend on the grouping, and the
+ * call does not fail on size while one matrix fits.  Synchronous. */
+int andi_hip_linkage_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, int method, andi_hip_link *links,
+						   int64_t *bad);
+/* Flat clusters of a linkage tree at threshold t.  Node n + s is CLOSED iff height[s] <= t and each of its children is a
+ * leaf or closed -- so an inversion of the heights cannot split a subtree.  The clusters are the maximal closed nodes and
+ * the leaves below none; labels[i] (n values) is leaf i's cluster, 0-based, numbered by first appearance in ascending
+ * leaf id; *nclusters their number.  A NaN height or threshold closes nothing.  Returns 1 on a NULL pointer, n outside
+ * 2 ... 65535 and malformed records: a child must be a leaf or an earlier record's node, the two children differ, and no
+ * node is a child twice.  Not recursive.  No GPU is touched. */
+int andi_hip_linkage_cut(const andi_hip_link *links, size_t n, double t, uint32_t *labels, size_t *nclusters);
+/* One representative per cluster: medoid[c] = the member i of cluster c with the least sum of D'[i][j] over the cluster's
+ * members j, taken in ascending leaf id, sequentially from +0.0 (j = i included: +0.0); D' is D as andi_hip_linkage reads
+ * it (upper triangle, mirrored, a NaN as +inf).  Ties go to the smaller id; a NaN sum (inf - inf) orders last.  Returns 1
+ * on a NULL pointer, n outside 2 ... 65535, a label >= nclusters, a cluster without a member, or a -inf in the upper
+ * triangle.  No GPU is touched. */
+int andi_hip_cluster_medoids(const double *D, size_t n, const uint32_t *labels, size_t nclusters, uint32_t *medoid);
+/* How often a clustering's clusters recur: stability[c] = the number of replicates k < count in which the leaf set of
+ * cluster c of `labels` is exactly one cluster of rep_labels + k*n (labels of any numbering, each < n).  The counts of
+ * calls over disjoint chunks of replicates add up.  Returns 1 on a NULL pointer, n outside 2 ... 65535, a label >=
+ * nclusters, a replicate's label >= n, or a cluster without a member.  No GPU is touched. */
+int andi_hip_cluster_stability(const uint32_t *labels, size_t nclusters, const uint32_t *rep_labels, size_t n, size_t count,
+							   uint32_t *stability);
+/* The Newick text of andi_hip_linkage's records, a rooted tree (dendrogram) on one line ending in ";\n".  Leaves are
+ * quoted and truncated exactly as andi_hip_format_newick does; node n + s is "(" T(a) ":" L "," T(b) ":" L ")", children
+ * in record order; the branch above a child is height(parent) - height(child), a leaf's height +0.0, printed %.8g;
+ * negative lengths are kept; the root has no length.  Not recursive: a 65535-leaf caterpillar works.  Return value and
+ * cap as andi_hip_format_newick.  Malformed records (andi_hip_linkage_cut's rule) and a branch length that is not finite
+ * (a height of +inf: a pair without a distance) give 0 and an empty string. */
+size_t andi_hip_format_newick_linkage(const andi_hip_link *links, size_t n, const char *const *names, int truncate_names,
+									  char *out, size_t cap);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
