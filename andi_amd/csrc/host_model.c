@@ -378,10 +378,11 @@ static void put_leaf(sink *o, const char *name, int truncate) {
 
 /* andi_hip_nj's records as Newick text (include/andi_hip.h), depth first with a stack of its own instead of recursion;
  * the label behind the ")" of pair record s is support[s] if support is given, else the transfer bootstrap expectation
- * from depth, transfer and used if depth is given, else none */
+ * from depth, transfer and used if depth is given, else none; edge_nums: "{v}" behind the length of the branch above node
+ * v (jplace's edge numbers, andi_hip_format_jplace) */
 static size_t format_newick(const andi_hip_nj_join *J, const uint32_t *support, const uint32_t *depth,
 							const uint64_t *transfer, size_t used, size_t n, const char *const *names, int truncate_names,
-							char *out, size_t cap) {
+							int edge_nums, char *out, size_t cap) {
 	sink o = {out, cap, 0};
 	if (out && cap) out[0] = '\0';
 	if (!J || !names || n < 2) return 0;
@@ -415,6 +416,7 @@ static size_t format_newick(const andi_hip_nj_join *J, const uint32_t *support, 
 			else if (top && depth) put(&o, "%.6g", 1.0 - (double)transfer[rec] / ((double)used * (double)(depth[rec] - 1)));
 			if (top) put(&o, ":%.8g", len);
 			else put(&o, ";\n");
+			if (top && edge_nums) put(&o, "{%zu}", n + rec);
 			continue;
 		}
 		const int k = f->next++;
@@ -424,6 +426,7 @@ static size_t format_newick(const andi_hip_nj_join *J, const uint32_t *support, 
 		if (child < n) {
 			put_leaf(&o, names[child], truncate_names);
 			put(&o, ":%.8g", len);
+			if (edge_nums) put(&o, "{%zu}", child);
 		} else {
 			stack[top++] = (frame){child - n, 0, len};
 			put(&o, "(");
@@ -436,12 +439,12 @@ static size_t format_newick(const andi_hip_nj_join *J, const uint32_t *support, 
 
 size_t andi_hip_format_newick_support(const andi_hip_nj_join *J, const uint32_t *support, size_t n,
 									  const char *const *names, int truncate_names, char *out, size_t cap) {
-	return format_newick(J, support, NULL, NULL, 0, n, names, truncate_names, out, cap);
+	return format_newick(J, support, NULL, NULL, 0, n, names, truncate_names, 0, out, cap);
 }
 
 size_t andi_hip_format_newick(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
 							  char *out, size_t cap) {
-	return format_newick(J, NULL, NULL, NULL, 0, n, names, truncate_names, out, cap);
+	return format_newick(J, NULL, NULL, NULL, 0, n, names, truncate_names, 0, out, cap);
 }
 
 size_t andi_hip_format_newick_transfer(const andi_hip_nj_join *J, const uint32_t *depth, const uint64_t *transfer,
@@ -451,7 +454,7 @@ size_t andi_hip_format_newick_transfer(const andi_hip_nj_join *J, const uint32_t
 	if (!depth || !transfer || used == 0) return 0;
 	for (size_t s = 0; s + 3 < n; s++)
 		if (depth[s] < 2) return 0;
-	return format_newick(J, NULL, depth, transfer, used, n, names, truncate_names, out, cap);
+	return format_newick(J, NULL, depth, transfer, used, n, names, truncate_names, 0, out, cap);
 }
 
 /* ------------------------------------------------------------------ */
@@ -797,6 +800,255 @@ size_t andi_hip_format_newick_linkage(const andi_hip_link *links, size_t n, cons
 	}
 #undef LINK_HEIGHT
 	free(stack);
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
+	return o.len;
+}
+
+/* ------------------------------------------------------------------ */
+/* Placement on a tree (include/andi_hip.h): the host's pieces          */
+/* ------------------------------------------------------------------ */
+
+/* andi_hip_distances_rect: the cells of andi_hip_format_distances_rect, blocks of query rows dealt to a pool of threads */
+typedef struct {
+	const andi_hip_model *MRQ, *MQR;
+	size_t nr, nq;
+	int model;
+	double *D;
+	size_t next; /* atomic: the next block of query rows */
+} rect_job;
+
+static void *rect_worker(void *arg) {
+	rect_job *job = arg;
+	for (;;) {
+		const size_t q0 = __atomic_fetch_add(&job->next, 4, __ATOMIC_RELAXED);
+		if (q0 >= job->nq) break;
+		for (size_t q = q0; q < q0 + 4 && q < job->nq; q++)
+			for (size_t r = 0; r < job->nr; r++) {
+				const andi_hip_model datum = andi_hip_model_average(&job->MQR[q * job->nr + r], &job->MRQ[r * job->nq + q]);
+				job->D[q * job->nr + r] = andi_hip_estimate(&datum, job->model);
+			}
+	}
+	return NULL;
+}
+
+int andi_hip_distances_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR, size_t nr, size_t nq, int model, double *D) {
+	if (!MRQ || !MQR || !D) return 1;
+	rect_job job = {MRQ, MQR, nr, nq, model, D, 0};
+	long procs = sysconf(_SC_NPROCESSORS_ONLN);
+	size_t nt = procs > 0 ? (size_t)procs : 1;
+	if (nt > 32) nt = 32;
+	if (nt > nq * nr / 4096 + 1) nt = nq * nr / 4096 + 1; /* (small tables: the calling thread alone) */
+	pthread_t tid[32];
+	size_t started = 0;
+	for (size_t t = 1; t < nt; t++)
+		if (pthread_create(&tid[started], NULL, rect_worker, &job) == 0) started++;
+	rect_worker(&job);
+	for (size_t t = 0; t < started; t++) pthread_join(tid[t], NULL);
+	return 0;
+}
+
+/* a name as the tree's text holds it (cut to ten characters under truncate_names), with its leaf */
+typedef struct {
+	const char *s;
+	size_t len;
+	uint32_t id;
+} nwk_name;
+
+static int nwk_cmp(const char *a, size_t la, const char *b, size_t lb) {
+	const int c = memcmp(a, b, la < lb ? la : lb);
+	return c ? c : la < lb ? -1 : la > lb;
+}
+
+static int nwk_cmp_names(const void *a, const void *b) {
+	const nwk_name *x = a, *y = b;
+	const int c = nwk_cmp(x->s, x->len, y->s, y->len);
+	return c ? c : x->id < y->id ? -1 : x->id > y->id; /* (names that agree: the first is the one found) */
+}
+
+/* an inner node of the text while it is open: its children so far, where its "(" is */
+typedef struct {
+	int32_t id[3];
+	double len[3];
+	int kids;
+} nwk_frame;
+
+static size_t nwk_blanks(const char *t, size_t pos) {
+	while (t[pos] == ' ' || t[pos] == '\t' || t[pos] == '\n' || t[pos] == '\r') pos++;
+	return pos;
+}
+
+/* a quoted string from its opening quote on: its text ('' undoubled) into buf; the position behind its closing quote, or
+ * 0 when the text ends first */
+static size_t nwk_quoted(const char *t, size_t pos, char *buf, size_t *len) {
+	size_t k = 0;
+	for (pos++;; pos++) {
+		if (!t[pos]) return 0;
+		if (t[pos] == '\'') {
+			if (t[pos + 1] != '\'') break;
+			pos++;
+		}
+		buf[k++] = t[pos];
+	}
+	*len = k;
+	return pos + 1;
+}
+
+int andi_hip_parse_newick(const char *text, const char *const *names, size_t n, int truncate_names, andi_hip_nj_join *joins,
+						  char *errbuf, size_t errlen) {
+#define NWK_FAIL(...)                                                                              \
+	do {                                                                                           \
+		if (errbuf && errlen) snprintf(errbuf, errlen, "andi_hip_parse_newick: " __VA_ARGS__);      \
+		goto fail;                                                                                 \
+	} while (0)
+	if (errbuf && errlen) errbuf[0] = '\0';
+	nwk_name *index = NULL;
+	nwk_frame *stack = NULL;
+	uint8_t *seen = NULL;
+	char *buf = NULL;
+	if (!text || !names || !joins || n < 3 || n > 65535) NWK_FAIL("bad arguments (text, names and joins must be given, 3 <= n <= 65535)");
+	index = malloc(n * sizeof *index), stack = malloc(n * sizeof *stack), seen = calloc(n, 1), buf = malloc(strlen(text) + 1);
+	if (!index || !stack || !seen || !buf) NWK_FAIL("out of memory");
+	for (size_t i = 0; i < n; i++) index[i] = (nwk_name){names[i], truncate_names ? strnlen(names[i], 10) : strlen(names[i]), (uint32_t)i};
+	qsort(index, n, sizeof *index, nwk_cmp_names);
+
+	size_t pos = nwk_blanks(text, 0), top = 0, pairs = 0, leaves = 0;
+	if (text[pos] != '(') NWK_FAIL("byte %zu: expected '(' at the start of the tree", pos);
+	for (;;) {
+		/* a subtree starts here */
+		pos = nwk_blanks(text, pos);
+		if (text[pos] == '(') {
+			if (top == n - 1) NWK_FAIL("byte %zu: nested deeper than a tree of %zu leaves can be", pos, n);
+			stack[top++].kids = 0;
+			pos++;
+			continue;
+		}
+		const size_t at = pos;
+		size_t len = 0;
+		if (text[pos] == '\'') {
+			pos = nwk_quoted(text, pos, buf, &len);
+			if (!pos) NWK_FAIL("byte %zu: a quoted name does not end", at);
+		} else {
+			while (text[pos] && !strchr(":,(); \t\n\r", text[pos])) buf[len++] = text[pos++];
+		}
+		if (truncate_names && len > 10) len = 10;
+		size_t lo = 0, hi = n; /* the first name not before the text */
+		while (lo < hi) {
+			const size_t mid = (lo + hi) / 2;
+			if (nwk_cmp(index[mid].s, index[mid].len, buf, len) < 0) lo = mid + 1;
+			else hi = mid;
+		}
+		if (lo == n || nwk_cmp(index[lo].s, index[lo].len, buf, len)) NWK_FAIL("byte %zu: unknown name '%.*s'", at, (int)len, buf);
+		int32_t child = (int32_t)index[lo].id;
+		if (seen[child]) NWK_FAIL("byte %zu: duplicate name '%.*s'", at, (int)len, buf);
+		seen[child] = 1, leaves++;
+		for (;;) { /* a child of the open node is complete but for its length */
+			pos = nwk_blanks(text, pos);
+			if (text[pos] != ':') NWK_FAIL("byte %zu: missing branch length", pos);
+			const size_t lat = pos + 1;
+			char *end;
+			const double l = strtod(text + lat, &end);
+			if (end == text + lat) NWK_FAIL("byte %zu: missing branch length", lat);
+			if (!isfinite(l)) NWK_FAIL("byte %zu: the branch length is not finite", lat);
+			pos = (size_t)(end - text);
+			nwk_frame *f = &stack[top - 1];
+			if (top == 1 && f->kids == 3) NWK_FAIL("byte %zu: the root has more than three subtrees", lat);
+			if (top > 1 && f->kids == 2) NWK_FAIL("byte %zu: an inner node has more than two children", lat);
+			f->id[f->kids] = child, f->len[f->kids] = l, f->kids++;
+			pos = nwk_blanks(text, pos);
+			if (text[pos] == ',') {
+				pos++;
+				break; /* the next subtree */
+			}
+			if (text[pos] != ')') NWK_FAIL("byte %zu: expected ',' or ')'", pos);
+			if (top == 1) goto root_closes;
+			if (f->kids != 2) NWK_FAIL("byte %zu: an inner node has %d child, not two", pos, f->kids);
+			if (pairs + 2 >= n) /* (one more than an unrooted tree has: a rooted text gets as far as its root, and fails there) */
+				NWK_FAIL("byte %zu: more inner nodes than a binary tree of %zu leaves has", pos, n);
+			const int lower = f->id[0] < f->id[1] ? 0 : 1;
+			joins[pairs] = (andi_hip_nj_join){f->id[lower], f->id[1 - lower], -1, 0, f->len[lower], f->len[1 - lower], 0.0};
+			child = (int32_t)(n + pairs++);
+			top--;
+			pos++; /* behind the ")": a label (support, TBE, consensus numbers) is not looked at */
+			if (text[pos] == '\'') {
+				const size_t q = nwk_quoted(text, pos, buf, &len);
+				if (!q) NWK_FAIL("byte %zu: a quoted label does not end", pos);
+				pos = q;
+			} else {
+				while (text[pos] && !strchr(":,(); \t\n\r", text[pos])) pos++;
+			}
+		}
+	}
+root_closes:;
+	const nwk_frame *f = &stack[0];
+	if (f->kids != 3) NWK_FAIL("byte %zu: the root has %d subtrees, not three", pos, f->kids);
+	pos++;
+	while (text[pos] && !strchr(":,(); \t\n\r", text[pos])) pos++; /* (a label) */
+	pos = nwk_blanks(text, pos);
+	if (text[pos] != ';') NWK_FAIL("byte %zu: expected ';' at the end of the tree", pos);
+	pos = nwk_blanks(text, pos + 1);
+	if (text[pos]) NWK_FAIL("byte %zu: trailing text behind the tree", pos);
+	if (leaves < n) {
+		size_t i = 0;
+		while (seen[i]) i++;
+		NWK_FAIL("byte %zu: the tree has %zu of the %zu names; missing name '%s'", pos, leaves, n, names[i]);
+	}
+	{ /* (all n names once, every inner node binary, the root ternary: n - 3 pair records) */
+		int o[3] = {0, 1, 2};
+		for (int a = 0; a < 3; a++)
+			for (int b = a + 1; b < 3; b++)
+				if (f->id[o[b]] < f->id[o[a]]) {
+					const int t = o[a];
+					o[a] = o[b], o[b] = t;
+				}
+		joins[n - 3] = (andi_hip_nj_join){f->id[o[0]], f->id[o[1]], f->id[o[2]], 0, f->len[o[0]], f->len[o[1]], f->len[o[2]]};
+	}
+	free(index), free(stack), free(seen), free(buf);
+	return 0;
+fail:
+	free(index), free(stack), free(seen), free(buf);
+	return 1;
+#undef NWK_FAIL
+}
+
+/* s as the inside of a JSON string */
+static void put_json(sink *o, const char *s, size_t len) {
+	for (size_t k = 0; k < len; k++) {
+		const unsigned char c = (unsigned char)s[k];
+		if (c == '"' || c == '\\') put(o, "\\%c", c);
+		else if (c < 0x20) put(o, "\\u%04x", c);
+		else put(o, "%c", c);
+	}
+}
+
+size_t andi_hip_format_jplace(const andi_hip_nj_join *tree, size_t n, const char *const *ref_names, int truncate_names,
+							  const andi_hip_placement *placements, size_t nq, const char *const *query_names, int method,
+							  char *out, size_t cap) {
+	sink o = {out, cap, 0};
+	if (out && cap) out[0] = '\0';
+	if (!tree || !ref_names || (nq && (!placements || !query_names)) || n < 3 || (method != ANDI_PLACE_OLS && method != ANDI_PLACE_FM))
+		return 0;
+	const size_t need = format_newick(tree, NULL, NULL, NULL, 0, n, ref_names, truncate_names, 1, NULL, 0);
+	if (!need) return 0;
+	char *text = malloc(need + 1);
+	if (!text) return 0;
+	format_newick(tree, NULL, NULL, NULL, 0, n, ref_names, truncate_names, 1, text, need + 1);
+	put(&o, "{\n\"tree\":\"");
+	put_json(&o, text, need - 1); /* (without the line's end) */
+	free(text);
+	put(&o, "\",\n\"placements\":[");
+	int first = 1;
+	for (size_t q = 0; q < nq; q++) {
+		const andi_hip_placement *p = &placements[q];
+		if (p->edge < 0) continue;
+		put(&o, first ? "\n" : ",\n");
+		first = 0;
+		put(&o, "{\"p\":[[%d,%.17g,1,%.17g,%.17g]],\"n\":[\"", (int)p->edge, p->err, p->distal, p->pendant);
+		put_json(&o, query_names[q], truncate_names ? strnlen(query_names[q], 10) : strlen(query_names[q]));
+		put(&o, "\"]}");
+	}
+	put(&o, "\n],\n\"metadata\":{\"program\":\"andi-hip\",\"placement\":\"least squares on anchor distances\",\"method\":\"%s\"},\n",
+		method == ANDI_PLACE_FM ? "fm" : "ols");
+	put(&o, "\"version\":3,\n\"fields\":[\"edge_num\",\"likelihood\",\"like_weight_ratio\",\"distal_length\",\"pendant_length\"]\n}\n");
 	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
 	return o.len;
 }

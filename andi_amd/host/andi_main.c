@@ -373,6 +373,13 @@ static void usage(int status) {
 		"      --reference=FILE  Compare FILES... against the sequences of FILE only (repeatable); prints one row\n"
 		"                       per query, one column per reference\n"
 		"      --reference-list=FILE  Read reference filenames from FILE; one per line\n"
+		"      --backbone=FILE  With --reference and --place: the tree of the references, as --tree wrote it for exactly\n"
+		"                       these references (Newick, unrooted, binary; support labels are ignored)\n"
+		"      --place=FILE     With --reference and --backbone: write to FILE (jplace) where on the backbone tree each\n"
+		"                       query sits -- the branch, the point on it and the length of the query's own branch that\n"
+		"                       fit its distances to the references best (least squares)\n"
+		"      --place-method=METHOD  Weigh the squared errors with 'fm' (1/d^2, Fitch-Margoliash) or 'ols' (all alike);\n"
+		"                       default: fm\n"
 		"  -t, --threads=INT    Set the number of host threads; by default, all processors are used\n"
 		"      --tree=FILE      Write a neighbor-joining tree of each printed matrix to FILE (Newick, one line per\n"
 		"                       matrix)\n"
@@ -863,9 +870,61 @@ static andi_hip_seq *seq_array(const genome_list *l) {
 	return in;
 }
 
+/* --place: where on the backbone tree (--backbone, a tree of the references) every query sits, as jplace text */
+typedef struct {
+	const char *path, *backbone_path;
+	FILE *f;
+	int method;
+	andi_hip_nj_join *J; /* the backbone's records, the references its leaves */
+} place_out;
+
+/* the backbone is read before anything is computed: a tree of other sequences ends the run with the parser's message */
+static void place_read_backbone(place_out *pl, const genome *refs, size_t nr, int truncate) {
+	if (nr < 3) errx(1, "Placement (--place) needs a tree: give at least three references.");
+	if (nr > 65535) errx(1, "Placement (--place) is limited to 65535 references (%zu given).", nr);
+	size_t len = 0;
+	read_buffer rb = {0};
+	char *text = slurp(pl->backbone_path, &len, &rb);
+	if (!text) err(1, "%s", pl->backbone_path);
+	const char **rn = name_array(refs, nr);
+	pl->J = xmalloc((nr - 2) * sizeof *pl->J);
+	char msg[512];
+	if (andi_hip_parse_newick(text, rn, nr, truncate, pl->J, msg, sizeof msg)) errx(1, "%s: %s", pl->backbone_path, msg);
+	free(rn), free(text);
+}
+
+static void place_queries(const place_out *pl, const andi_hip_model *MRQ, const andi_hip_model *MQR, const char **rn, size_t nr,
+						  const char **qn, size_t nq, int model, int truncate, int device) {
+	andi_hip_ctx *ctx = NULL;
+	char msg[512];
+	if (andi_hip_ctx_create(&ctx, device, msg, sizeof msg)) {
+		soft_warnx("No placements: %s", msg);
+		return;
+	}
+	double *D = malloc(nq * nr * sizeof *D);
+	andi_hip_placement *P = malloc(nq * sizeof *P);
+	if (!D || !P || andi_hip_distances_rect(MRQ, MQR, nr, nq, model, D)) err(errno, "Could not allocate enough memory for the placements.");
+	if (andi_hip_place(ctx, pl->J, nr, D, nq, pl->method, P, NULL, NULL, NULL)) {
+		soft_warnx("No placements: %s", andi_hip_last_error(ctx));
+	} else {
+		for (size_t q = 0; q < nq; q++)
+			if (P[q].edge < 0) soft_warnx("No placement for '%s': only %u of its distances to the references can be used.", qn[q], P[q].used);
+		size_t cap = 512 + nr * 64 + nq * 128;
+		for (size_t i = 0; i < nr; i++) cap += 2 * strlen(rn[i]);
+		for (size_t q = 0; q < nq; q++) cap += 6 * strlen(qn[q]);
+		char *text = xmalloc(cap);
+		const size_t need = andi_hip_format_jplace(pl->J, nr, rn, truncate, P, nq, qn, pl->method, text, cap);
+		if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_jplace(pl->J, nr, rn, truncate, P, nq, qn, pl->method, text, cap);
+		if (fputs(text, pl->f) == EOF) err(1, "%s", pl->path);
+		free(text);
+	}
+	free(D), free(P);
+	andi_hip_ctx_destroy(ctx);
+}
+
 /* --reference: the queries (the FILES) against the references, the two cross blocks of the square run over both sets */
 static int run_rect(const name_list *ref_files, const name_list *files, int join, int verbose, int truncate, int show_progress,
-					andi_hip_opts *opts) {
+					andi_hip_opts *opts, place_out *pl) {
 	genome_list refs = {0}, qs = {0};
 	read_all_files(ref_files->v, ref_files->n, join, opts->host_threads, &refs);
 	read_all_files(files->v, files->n, join, opts->host_threads, &qs);
@@ -873,6 +932,7 @@ static int run_rect(const name_list *ref_files, const name_list *files, int join
 	if (qs.n == 0) errx(1, "No query sequences given: name at least one FASTA file besides the references.");
 	check_genomes(&refs, &qs, truncate);
 	const size_t nr = refs.n, nq = qs.n;
+	if (pl->path) place_read_backbone(pl, refs.v, nr, truncate);
 	if (show_progress) {
 		progress_n = nr + nq;
 		opts->progress = progress_cb;
@@ -887,7 +947,6 @@ static int run_rect(const name_list *ref_files, const name_list *files, int join
 	if (show_progress) fprintf(stderr, ", done.\n");
 	const char **rn = name_array(refs.v, nr), **qn = name_array(qs.v, nq);
 	print_distances(MRQ, MQR, rn, nr, qn, nq, opts->model, verbose >= 2, truncate, 1);
-	free(rn), free(qn);
 	if (verbose) { /* print_coverages, src/io.c:329-338, of the query rows */
 		printf("\nCoverage:\n");
 		for (size_t q = 0; q < nq; q++) {
@@ -895,6 +954,12 @@ static int run_rect(const name_list *ref_files, const name_list *files, int join
 			printf("\n");
 		}
 	}
+	if (pl->path) {
+		place_queries(pl, MRQ, MQR, rn, nr, qn, nq, opts->model, truncate, opts->device);
+		if (fclose(pl->f)) err(1, "%s", pl->path);
+		free(pl->J);
+	}
+	free(rn), free(qn);
 	free(MRQ);
 	free(MQR);
 	free(rin);
@@ -909,6 +974,9 @@ int main(int argc, char *argv[]) {
 												 {"progress", optional_argument, NULL, 0},
 												 {"reference", required_argument, NULL, 0},
 												 {"reference-list", required_argument, NULL, 0},
+												 {"backbone", required_argument, NULL, 0},
+												 {"place", required_argument, NULL, 0},
+												 {"place-method", required_argument, NULL, 0},
 												 {"tree", required_argument, NULL, 0},
 												 {"support", required_argument, NULL, 0},
 												 {"consensus", required_argument, NULL, 0},
@@ -944,6 +1012,7 @@ int main(int argc, char *argv[]) {
 	int rect = 0, bootstrap_given = 0, trees_only = 0;
 	tree_out tree = {.o = &outs[OUT_TREE]};
 	cluster_out clus = {.method = ANDI_LINK_AVERAGE};
+	place_out place = {.method = ANDI_PLACE_FM};
 
 	for (;;) {
 		int idx = 0;
@@ -973,6 +1042,13 @@ int main(int argc, char *argv[]) {
 					if (errno || end == optarg || *end || !isfinite(clus.threshold) || clus.threshold < 0.0)
 						errx(1, "Expected a finite number of at least 0 for --threshold, but '%s' was given.", optarg);
 					clus.have_threshold = 1;
+				}
+				if (!strcmp(o, "backbone")) place.backbone_path = optarg;
+				if (!strcmp(o, "place")) place.path = optarg;
+				if (!strcmp(o, "place-method")) {
+					if (!strcasecmp(optarg, "fm")) place.method = ANDI_PLACE_FM;
+					else if (!strcasecmp(optarg, "ols")) place.method = ANDI_PLACE_OLS;
+					else errx(1, "Expected one of 'fm' or 'ols' for --place-method, but '%s' was given.", optarg);
 				}
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files);
 				if (!strcmp(o, "reference")) rect = 1, push_name(&ref_files, optarg);
@@ -1058,6 +1134,9 @@ int main(int argc, char *argv[]) {
 	if (clus.clusters_path && trees_only) errx(1, "Clusters (--clusters) are not available together with --trees-only: there are no matrices to cluster.");
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
 	if (clus.have_threshold && !clus.clusters_path) errx(1, "A threshold (--threshold) needs somewhere to go: give --clusters=FILE.");
+	if (place.path && !rect) errx(1, "Placement (--place) needs references to place on: give --reference=FILE or --reference-list=FILE.");
+	if (place.path && !place.backbone_path) errx(1, "Placement (--place) needs the tree of the references: give --backbone=FILE.");
+	if (place.backbone_path && !place.path) errx(1, "A backbone tree (--backbone) needs somewhere to go: give --place=FILE.");
 	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
 	if (trees_only && !any_out)
 		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
@@ -1065,6 +1144,7 @@ int main(int argc, char *argv[]) {
 		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
+	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
 	tree.device_for_ctx = clus.device_for_ctx = opts.device;
 	if (join && files.n == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (files.n < (size_t)(join && !rect ? 2 : 1)) {
@@ -1074,7 +1154,7 @@ int main(int argc, char *argv[]) {
 
 	/* ANDI_HIP_CLI_TRACE=1: where the wall time goes -- reading the input, the matrix, printing it (stderr; scripts/full_size.py --cli) */
 	if (progress == P_AUTO && rect) progress = isatty(STDERR_FILENO) ? P_ALWAYS : P_NEVER;
-	if (rect) return run_rect(&ref_files, &files, join, verbose, truncate, progress == P_ALWAYS, &opts);
+	if (rect) return run_rect(&ref_files, &files, join, verbose, truncate, progress == P_ALWAYS, &opts, &place);
 	const int cli_trace = getenv("ANDI_HIP_CLI_TRACE") != NULL;
 	struct timespec ts0, ts1, ts2, ts3;
 	clock_gettime(CLOCK_MONOTONIC, &ts0);

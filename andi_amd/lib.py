@@ -127,6 +127,11 @@ SYMBOLS = {
     "andi_hip_cluster_medoids": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "andi_hip_cluster_stability": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P]),
     "andi_hip_format_newick_linkage": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_place": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
+    "andi_hip_distances_rect": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P]),
+    "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
+    "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
+                                            C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -481,6 +486,63 @@ def newick_linkage(Z, names, truncate_names=False):
     for _ in range(2):  # (the call returns the bytes it needs)
         out = C.create_string_buffer(cap)
         need = load().andi_hip_format_newick_linkage(Z.ctypes.data, n, cn, int(truncate_names), C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
+
+
+# andi_hip_placement: where a query sits on a tree (the edge, -1 for none; the usable leaves; the point on the edge from
+# its child end; the length of the hanging branch; the weighted squared error)
+PLACEMENT = np.dtype([("edge", "<i4"), ("used", "<u4"), ("distal", "<f8"), ("pendant", "<f8"), ("err", "<f8")])
+PLACE_METHODS = {"ols": 0, "fm": 1}
+
+
+def _place_method(method):
+    if method not in PLACE_METHODS:
+        raise ValueError("placement method %r: expected fm or ols" % (method,))
+    return PLACE_METHODS[method]
+
+
+def distances_rect(MRQ, MQR, model=M_JC):
+    """The (nq, nr) float64 distances format_distances_rect prints for dist_rect's (MRQ, MQR), unrounded
+    (andi_hip_distances_rect).  No GPU is touched."""
+    MRQ = np.ascontiguousarray(MRQ, dtype=np.uint32)
+    MQR = np.ascontiguousarray(MQR, dtype=np.uint32)
+    nr, nq = MRQ.shape[0], MQR.shape[0]
+    assert MRQ.shape == (nr, nq, 17) and MQR.shape == (nq, nr, 17)
+    D = np.empty((nq, nr), np.float64)
+    if load().andi_hip_distances_rect(MRQ.ctypes.data, MQR.ctypes.data, nr, nq, model, D.ctypes.data):
+        raise AndiHipError("andi_hip_distances_rect failed")
+    return D
+
+
+def parse_newick(text, names, truncate_names=False):
+    """The n - 2 records (dtype NJ_JOIN) of the unrooted binary tree in the Newick `text` whose leaves are `names`
+    (andi_hip_parse_newick, the inverse of newick); AndiHipError with the parser's message, which names the byte offset,
+    for a text it refuses.  No GPU is touched."""
+    n = len(names)
+    J = np.zeros(max(n - 2, 0), NJ_JOIN)
+    err = C.create_string_buffer(512)
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    if load().andi_hip_parse_newick(raw, _names(names), n, int(truncate_names), J.ctypes.data, err, len(err)):
+        raise AndiHipError(err.value.decode(errors="replace"))
+    return J
+
+
+def jplace(J, ref_names, placements, query_names, method="fm", truncate_names=False):
+    """The jplace text (version 3) of place's records for the tree J over `ref_names` (andi_hip_format_jplace); "" where
+    the library refuses (malformed records).  No GPU is touched."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    P = np.ascontiguousarray(placements, dtype=PLACEMENT)
+    n, nq = len(ref_names), len(query_names)
+    assert len(J) == n - 2 and P.shape == (nq,)
+    rn, qn = _names(ref_names), _names(query_names)
+    cap = 512 + 64 * n + sum(len(x) for x in ref_names) + 128 * nq + sum(len(x) for x in query_names)
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_jplace(J.ctypes.data, n, rn, int(truncate_names), P.ctypes.data, nq, qn,
+                                             _place_method(method), C.cast(out, _P), cap)
         if need < cap:
             break
         cap = need + 1
@@ -875,6 +937,24 @@ def linkage_batch(ctx: Context, Ds, method="average"):
     ctx._check(load().andi_hip_linkage_batch(ctx._h, Ds.ctypes.data, n, count, method, Z.ctypes.data,
                                              bad.ctypes.data), "linkage_batch")
     return Z, bad
+
+
+def place(ctx: Context, J, D, method="fm", per=False):
+    """Distance-based placement (andi_hip_place) of the rows of D (nq, n) -- each a query's distances to the n leaves, a
+    NaN where there is none -- on the tree J (n - 2 records of nj or parse_newick): a structured array of dtype PLACEMENT,
+    one record per query (edge -1: not placed); with per=True also the (nq, 2n - 3) float64 arrays err, x and p of every
+    edge.  method: "fm" (weights 1 / d^2) or "ols"."""
+    m = _place_method(method)
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    assert D.ndim == 2 and D.shape[1] == n
+    nq, E = D.shape[0], 2 * n - 3
+    out = np.zeros(nq, PLACEMENT)
+    rows = [np.zeros((nq, E), np.float64) for _ in range(3)] if per else [None] * 3
+    ctx._check(load().andi_hip_place(ctx._h, J.ctypes.data, n, D.ctypes.data, nq, m, out.ctypes.data,
+                                     *[r.ctypes.data if per else None for r in rows]), "place")
+    return (out, *rows) if per else out
 
 
 def nj_support(ctx: Context, J, reps, skip=None):

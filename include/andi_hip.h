@@ -22,7 +22,8 @@
  * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only); and bootstrap
  * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only); and linkage
  * clustering: andi_hip_linkage, andi_hip_linkage_batch, andi_hip_linkage_cut, andi_hip_cluster_medoids,
- * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only).
+ * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only); and placement of queries on a tree:
+ * andi_hip_place, andi_hip_distances_rect, andi_hip_parse_newick and andi_hip_format_jplace (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -556,6 +557,81 @@ int andi_hip_cluster_stability(const uint32_t *labels, size_t nclusters, const u
  * (a height of +inf: a pair without a distance) give 0 and an empty string. */
 size_t andi_hip_format_newick_linkage(const andi_hip_link *links, size_t n, const char *const *names, int truncate_names,
 									  char *out, size_t cap);
+
+/* Distance-based placement of queries on a neighbor-joining tree (least-squares placement, as APPLES does it): for every
+ * query, the edge of the tree, the point on it and the length of the branch hanging there that fit the query's distances
+ * to the leaves best.  tree: the n - 2 records of andi_hip_nj for n leaves (validated on the host by andi_hip_nj_support's
+ * rule); D: nq rows of n distances, D[q*n + i] from query q to leaf i (host memory; andi_hip_distances_rect gives them);
+ * method: ANDI_PLACE_OLS or ANDI_PLACE_FM; out: nq records; per_err, per_x, per_p: NULL, or nq * (2n - 3) doubles each, the
+ * values of every edge.  3 <= n <= 65535.  Bad arguments (a NULL ctx, tree, D or out, nq == 0, n out of range, a method
+ * outside 0 ... 1) fail with 1 before any HIP call; a branch length that is not finite and records that are not
+ * andi_hip_nj's fail with 1 through the context's error, also before any HIP call.  Synchronous, on the context's stream.
+ *
+ * The result is bit-exact to this contract (tests/place_model.py restates it); every operation is an IEEE double operation
+ * rounded on its own (no a*b+c contracted into an FMA), every sum sequential in the order given:
+ *  - the tree: leaf i has id i, pair record s < n - 3 makes node n + s, the final record the centre C = 2n - 3.  parent(v)
+ *    and len(v) come from the record that has v as a child (la, lb or lc).  There are 2n - 3 edges; edge v, 0 <= v < 2n - 3,
+ *    joins v to parent(v) (its jplace edge number as well).  Negative lengths are kept as they are;
+ *  - path lengths h(v, i) from node v to leaf i: h(i, i) = +0.0; upwards from i to C, h(parent(v), i) = h(v, i) + len(v);
+ *    for every other node c, in descending id order, h(c, i) = h(parent(c), i) + len(c).  below(v, i) iff v lies on the
+ *    path from i to C;
+ *  - a query's row d = D[q*n .. q*n + n); leaf i is USABLE iff d_i is finite (a NaN is a pair without a distance and counts
+ *    for nothing, as in andi_hip_linkage); its weight w_i is 1.0 under OLS and 1.0 / (d_i * d_i) under FM (Fitch and
+ *    Margoliash's weights; the default of the command line);
+ *  - per edge v, with L = len(v) and Lc = L > 0 ? L : +0.0, pass 1 over the usable i in ascending order, four sums from
+ *    +0.0: if below(v, i): u = d_i - h(v, i), WA += w, UA += w*u; otherwise u = (d_i - h(parent(v), i)) - L, WB += w,
+ *    UB += w*u.  If WA == 0.0 or WB == 0.0 the edge is no candidate: err = +inf, x = p = +0.0;
+ *  - the solve: s = UA/WA, t = UB/WB, W = WA + WB, p0 = (s + t)*0.5, x0 = (s - t)*0.5.  If p0 >= 0 && x0 >= 0 && x0 <= Lc,
+ *    (p, x) = (p0, x0).  Otherwise three candidates, in this order: (pos(((WA*s) + (WB*t))/W), +0.0);
+ *    (pos(((WA*(s - Lc)) + (WB*(t + Lc)))/W), Lc); (+0.0, clamp(((WA*s) - (WB*t))/W)), with pos(a) = a > 0 ? a : +0.0 and
+ *    clamp(a) = a > 0 ? (a < Lc ? a : Lc) : +0.0; the one with the least Q = WA*(e*e) + WB*(f*f), e = (p + x) - s,
+ *    f = (p - x) - t, ties to the earlier one, a NaN after every number.  (In (p + x, p - x) the objective decouples, so
+ *    the optimum over x in [0, Lc], p >= 0 is the free one or lies on one of the three boundary lines.)
+ *  - pass 2, err from +0.0 over the usable i in ascending order: m = below(v, i) ? ((p + x) + h(v, i)) :
+ *    ((p + (L - x)) + h(parent(v), i)); r = d_i - m; err += w*(r*r);
+ *  - under FM, if some usable d_i == 0.0 the query IS the first such leaf i: every edge gets err = +inf, x = p = +0.0, but
+ *    edge i err = +0.0 (this rule comes before the one below);
+ *  - the choice: the edge with the least err by value, ties to the smaller v, a NaN after every number; the record is
+ *    {v, used, x, p, err}, used the number of usable leaves.  If the least err is +inf or NaN the query is unplaced:
+ *    {-1, used, +0.0, +0.0, +inf} -- always so with fewer than two usable leaves.
+ * distal is x, measured from the child end of the edge (the end away from the centre: jplace's distal end).
+ * On the device: the table of the (2n - 3) x n path lengths, 8 bytes each (152 MB at 3085 leaves, 68.7 GB at 65535); when
+ * it does not fit the call fails through the context's error, which names the bytes.  The queries are taken in groups
+ * that fit; the results do not depend on the grouping.  Work: nq * (2n - 3) * n leaf visits, twice. */
+enum { ANDI_PLACE_OLS = 0, ANDI_PLACE_FM = 1 };
+/* One placement (andi_hip_place): the edge (-1: unplaced), the usable leaves, the point on the edge, the length of the
+ * hanging branch, the weighted squared error.  32 bytes. */
+typedef struct {
+	int32_t edge;
+	uint32_t used;
+	double distal, pendant, err;
+} andi_hip_placement;
+int andi_hip_place(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, size_t nq, int method,
+				   andi_hip_placement *out, double *per_err, double *per_x, double *per_p);
+/* The distances of the query-versus-reference mode as doubles: D[q*nr + r] = the unrounded value
+ * andi_hip_format_distances_rect prints for that cell (without extra_verbose; it is the same computation).  Row-parallel
+ * like andi_hip_distances.  Returns 1 on NULL pointers.  No GPU is touched. */
+int andi_hip_distances_rect(const andi_hip_model *MRQ, const andi_hip_model *MQR, size_t nr, size_t nq, int model, double *D);
+/* The inverse of andi_hip_format_newick: the n - 2 records (joins) of the unrooted binary tree in `text`, whose leaves are
+ * the n names (3 <= n <= 65535).  The leaf whose text -- unquoted, '' undoubled, cut to ten characters under
+ * truncate_names -- equals names[i] (cut likewise) gets id i.  Pair nodes are numbered n + s in the order their ")"
+ * closes; a pair record has a < b, the final record x < y < z.  Labels behind a ")" (support, TBE and consensus numbers)
+ * are ignored, blanks, tabs and line ends between tokens too; lengths are parsed by strtod.  Not recursive.  Refused, with
+ * a message in errbuf that names the byte offset: a root without exactly three subtrees, an inner node without exactly two
+ * children, a missing or non-finite length, an unknown name, a duplicate name, a missing name, and trailing text other
+ * than whitespace.  Returns 0, or 1 (also on a NULL text, names or joins and n out of range).  No GPU is touched. */
+int andi_hip_parse_newick(const char *text, const char *const *names, size_t n, int truncate_names, andi_hip_nj_join *joins,
+						  char *errbuf, size_t errlen);
+/* Placements as jplace text (version 3) for the usual readers.  "tree" is the text of andi_hip_format_newick's walk over
+ * `tree` with "{v}" behind every length, v the edge number; "fields" are edge_num, likelihood, like_weight_ratio,
+ * distal_length, pendant_length -- likelihood carries err and the ratio is 1, as distance-based placers fill them; one
+ * {"p":[[...]],"n":["name"]} per placed query in input order, numbers %.17g, names JSON-escaped (and cut to ten characters
+ * under truncate_names, as the table prints them); unplaced queries (edge -1) are left out; "metadata" names the method.
+ * Return value and cap as andi_hip_format_newick; malformed records, a NULL pointer and a method outside 0 ... 1 give 0
+ * and an empty string. */
+size_t andi_hip_format_jplace(const andi_hip_nj_join *tree, size_t n, const char *const *ref_names, int truncate_names,
+							  const andi_hip_placement *placements, size_t nq, const char *const *query_names, int method,
+							  char *out, size_t cap);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
