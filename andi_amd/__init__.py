@@ -10,4 +10,5 @@ from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_rang
                   match_positions, newick, newick_consensus, newick_transfer, nj, nj_batch, nj_splits, nj_support, nj_transfer,
                   LINK, cluster_medoids, cluster_stability, linkage, linkage_batch, linkage_cut, newick_linkage,
                   PLACEMENT, distances_rect, jplace, parse_newick, place,
+                  Sketches, screen, screen_select, sketch, sketch_shared,
                   scan_rows, subject_prepare, suffix_array)

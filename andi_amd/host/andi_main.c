@@ -380,6 +380,14 @@ static void usage(int status) {
 		"                       fit its distances to the references best (least squares)\n"
 		"      --place-method=METHOD  Weigh the squared errors with 'fm' (1/d^2, Fitch-Margoliash) or 'ols' (all alike);\n"
 		"                       default: fm\n"
+		"      --screen=K       With --reference or --reference-list: sketch every sequence first (k-mer hashes, on the GPU)\n"
+		"                       and compare each query only with its K references that share the most hashes with it\n"
+		"      --screen-kmer=INT  The k-mer length of the sketches, 4 to 32; default: 21 (sourmash's default)\n"
+		"      --screen-scale=INT  Keep one hash in INT (a hash h is kept iff h <= (2^64 - 1) / INT); default: 1000\n"
+		"                       (sourmash's default)\n"
+		"      --screen-min=INT  A reference must share at least INT hashes with a query to be taken; default: 1\n"
+		"      --screen-report=FILE  Write every (query, reference) pair that shares a hash to FILE, tab-separated: the\n"
+		"                       counts, the sketch sizes, the containment of the query and whether the reference was kept\n"
 		"  -t, --threads=INT    Set the number of host threads; by default, all processors are used\n"
 		"      --tree=FILE      Write a neighbor-joining tree of each printed matrix to FILE (Newick, one line per\n"
 		"                       matrix)\n"
@@ -893,8 +901,10 @@ static void place_read_backbone(place_out *pl, const genome *refs, size_t nr, in
 	free(rn), free(text);
 }
 
+/* rn, nr: the backbone's leaves.  col == NULL: MRQ and MQR hold all of them; else (--screen) they hold the nk references
+ * col[0] < col[1] < ... only, and the others count as references without a distance (NaN) */
 static void place_queries(const place_out *pl, const andi_hip_model *MRQ, const andi_hip_model *MQR, const char **rn, size_t nr,
-						  const char **qn, size_t nq, int model, int truncate, int device) {
+						  const size_t *col, size_t nk, const char **qn, size_t nq, int model, int truncate, int device) {
 	andi_hip_ctx *ctx = NULL;
 	char msg[512];
 	if (andi_hip_ctx_create(&ctx, device, msg, sizeof msg)) {
@@ -903,7 +913,15 @@ static void place_queries(const place_out *pl, const andi_hip_model *MRQ, const 
 	}
 	double *D = malloc(nq * nr * sizeof *D);
 	andi_hip_placement *P = malloc(nq * sizeof *P);
-	if (!D || !P || andi_hip_distances_rect(MRQ, MQR, nr, nq, model, D)) err(errno, "Could not allocate enough memory for the placements.");
+	if (!D || !P || andi_hip_distances_rect(MRQ, MQR, col ? nk : nr, nq, model, D)) err(errno, "Could not allocate enough memory for the placements.");
+	if (col) /* the nq x nk distances lie at the front of D: spread every row over its nr columns, from the back */
+		for (size_t q = nq; q-- > 0;) {
+			size_t j = nk;
+			for (size_t r = nr; r-- > 0;) {
+				if (j > 0 && col[j - 1] == r) D[q * nr + r] = D[q * nk + --j];
+				else D[q * nr + r] = NAN;
+			}
+		}
 	if (andi_hip_place(ctx, pl->J, nr, D, nq, pl->method, P, NULL, NULL, NULL)) {
 		soft_warnx("No placements: %s", andi_hip_last_error(ctx));
 	} else {
@@ -922,17 +940,75 @@ static void place_queries(const place_out *pl, const andi_hip_model *MRQ, const 
 	andi_hip_ctx_destroy(ctx);
 }
 
+/* --screen=K: a k-mer sketch screen in front of the query-versus-reference mode */
+typedef struct {
+	size_t keep; /* 0: no screen */
+	int k, k_given, scale_given, min_given;
+	uint64_t scale;
+	uint32_t min;
+	const char *report_path;
+	FILE *rf;
+} screen_opts;
+
+/* Sketches both sets, selects, writes the report; returns the indices of the kept references, ascending, *nk of them.
+ * A run that keeps nothing ends here. */
+static size_t *screen_references(const screen_opts *sc, const genome_list *refs, const genome_list *qs, int truncate, int verbose,
+								 int device, size_t *nk) {
+	const size_t nr = refs->n, nq = qs->n;
+	if (SIZE_MAX / sizeof(uint32_t) / nr < nq) errx(1, "The screen is limited to fewer sequences (%zu given).", nr + nq);
+	uint32_t *shared = malloc(nr * nq * sizeof *shared), *rs = malloc(nr * sizeof *rs), *qsz = malloc(nq * sizeof *qsz);
+	uint32_t *taken = malloc(nq * sizeof *taken);
+	uint8_t *kept = malloc(nr);
+	if (!shared || !rs || !qsz || !taken || !kept) err(errno, "Could not allocate enough memory for the screen.");
+	andi_hip_seq *rin = seq_array(refs), *qin = seq_array(qs);
+	char msg[512];
+	if (andi_hip_screen(rin, nr, qin, nq, sc->k, sc->scale, device, shared, rs, qsz, msg, sizeof msg)) errx(1, "%s", msg);
+	if (andi_hip_screen_select(shared, nq, nr, sc->keep, sc->min, kept, taken)) errx(1, "The screen could not select references.");
+	if (sc->rf) {
+		const int w = truncate ? 10 : INT_MAX;
+		int bad = fprintf(sc->rf, "#query\treference\tshared\tquery_hashes\treference_hashes\tcontainment\tkept\n") < 0;
+		for (size_t q = 0; q < nq && !bad; q++)
+			for (size_t r = 0; r < nr && !bad; r++) {
+				const uint32_t c = shared[q * nr + r];
+				if (c)
+					bad |= fprintf(sc->rf, "%.*s\t%.*s\t%u\t%u\t%u\t%.6f\t%d\n", w, qs->v[q].name, w, refs->v[r].name, (unsigned)c,
+								   (unsigned)qsz[q], (unsigned)rs[r], (double)c / (double)qsz[q], (int)kept[r]) < 0;
+			}
+		if (bad || fclose(sc->rf)) err(1, "%s", sc->report_path);
+	}
+	size_t *col = xmalloc(nr * sizeof *col), n = 0;
+	for (size_t r = 0; r < nr; r++)
+		if (kept[r]) col[n++] = r;
+	if (verbose) fprintf(stderr, "%s: The screen kept %zu of %zu references.\n", program_invocation_short_name, n, nr);
+	if (n == 0)
+		errx(1, "The screen kept no reference: no query shares %u or more hashes with any of them (--screen-kmer=%d, --screen-scale=%llu).",
+			 (unsigned)(sc->min > 1 ? sc->min : 1), sc->k, (unsigned long long)sc->scale);
+	for (size_t q = 0; q < nq; q++)
+		if (!taken[q]) soft_warnx("The screen kept no reference for '%s': it shares too few hashes with every one of them.", qs->v[q].name);
+	free(shared), free(rs), free(qsz), free(taken), free(kept), free(rin), free(qin);
+	*nk = n;
+	return col;
+}
+
 /* --reference: the queries (the FILES) against the references, the two cross blocks of the square run over both sets */
 static int run_rect(const name_list *ref_files, const name_list *files, int join, int verbose, int truncate, int show_progress,
-					andi_hip_opts *opts, place_out *pl) {
-	genome_list refs = {0}, qs = {0};
+					andi_hip_opts *opts, place_out *pl, const screen_opts *sc) {
+	genome_list refs = {0}, qs = {0}, all_refs = {0};
 	read_all_files(ref_files->v, ref_files->n, join, opts->host_threads, &refs);
 	read_all_files(files->v, files->n, join, opts->host_threads, &qs);
 	if (refs.n == 0) errx(1, "No reference sequences given: --reference and --reference-list name no readable sequence.");
 	if (qs.n == 0) errx(1, "No query sequences given: name at least one FASTA file besides the references.");
+	size_t *col = NULL; /* --screen: the kept references' places among all of them; from here on refs holds the kept ones only */
+	if (sc->keep) {
+		size_t nk = 0;
+		col = screen_references(sc, &refs, &qs, truncate, verbose, opts->device, &nk);
+		all_refs = refs;
+		refs.v = xmalloc(nk * sizeof *refs.v), refs.n = refs.cap = nk;
+		for (size_t j = 0; j < nk; j++) refs.v[j] = all_refs.v[col[j]];
+	}
 	check_genomes(&refs, &qs, truncate);
 	const size_t nr = refs.n, nq = qs.n;
-	if (pl->path) place_read_backbone(pl, refs.v, nr, truncate);
+	if (pl->path) place_read_backbone(pl, col ? all_refs.v : refs.v, col ? all_refs.n : nr, truncate);
 	if (show_progress) {
 		progress_n = nr + nq;
 		opts->progress = progress_cb;
@@ -955,7 +1031,9 @@ static int run_rect(const name_list *ref_files, const name_list *files, int join
 		}
 	}
 	if (pl->path) {
-		place_queries(pl, MRQ, MQR, rn, nr, qn, nq, opts->model, truncate, opts->device);
+		const char **an = col ? name_array(all_refs.v, all_refs.n) : rn;
+		place_queries(pl, MRQ, MQR, an, col ? all_refs.n : nr, col, nr, qn, nq, opts->model, truncate, opts->device);
+		if (col) free(an);
 		if (fclose(pl->f)) err(1, "%s", pl->path);
 		free(pl->J);
 	}
@@ -964,7 +1042,17 @@ static int run_rect(const name_list *ref_files, const name_list *files, int join
 	free(MQR);
 	free(rin);
 	free(qin);
+	free(col);
 	return soft_error ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
+/* a positive integer of at most `max`, or 0 */
+static unsigned long long positive_arg(const char *text, unsigned long long max) {
+	errno = 0;
+	char *end;
+	if (!isdigit((unsigned char)*text)) return 0;
+	const unsigned long long v = strtoull(text, &end, 10);
+	return errno || end == text || *end || v > max ? 0 : v;
 }
 
 int main(int argc, char *argv[]) {
@@ -977,6 +1065,11 @@ int main(int argc, char *argv[]) {
 												 {"backbone", required_argument, NULL, 0},
 												 {"place", required_argument, NULL, 0},
 												 {"place-method", required_argument, NULL, 0},
+												 {"screen", required_argument, NULL, 0},
+												 {"screen-kmer", required_argument, NULL, 0},
+												 {"screen-scale", required_argument, NULL, 0},
+												 {"screen-min", required_argument, NULL, 0},
+												 {"screen-report", required_argument, NULL, 0},
 												 {"tree", required_argument, NULL, 0},
 												 {"support", required_argument, NULL, 0},
 												 {"consensus", required_argument, NULL, 0},
@@ -1013,6 +1106,8 @@ int main(int argc, char *argv[]) {
 	tree_out tree = {.o = &outs[OUT_TREE]};
 	cluster_out clus = {.method = ANDI_LINK_AVERAGE};
 	place_out place = {.method = ANDI_PLACE_FM};
+	screen_opts screen = {.k = 21, .scale = 1000, .min = 1};
+	int screen_given = 0;
 
 	for (;;) {
 		int idx = 0;
@@ -1050,6 +1145,27 @@ int main(int argc, char *argv[]) {
 					else if (!strcasecmp(optarg, "ols")) place.method = ANDI_PLACE_OLS;
 					else errx(1, "Expected one of 'fm' or 'ols' for --place-method, but '%s' was given.", optarg);
 				}
+				if (!strcmp(o, "screen")) {
+					screen_given = 1;
+					if (!(screen.keep = (size_t)positive_arg(optarg, SIZE_MAX)))
+						errx(1, "Expected a positive number of references to keep for --screen, but '%s' was given.", optarg);
+				}
+				if (!strcmp(o, "screen-kmer")) {
+					const unsigned long long v = positive_arg(optarg, 32);
+					if (v < 4) errx(1, "Expected a k-mer length of 4 to 32 for --screen-kmer, but '%s' was given.", optarg);
+					screen.k = (int)v, screen.k_given = 1;
+				}
+				if (!strcmp(o, "screen-scale")) {
+					if (!(screen.scale = positive_arg(optarg, UINT64_MAX)))
+						errx(1, "Expected a positive integer for --screen-scale, but '%s' was given.", optarg);
+					screen.scale_given = 1;
+				}
+				if (!strcmp(o, "screen-min")) {
+					if (!(screen.min = (uint32_t)positive_arg(optarg, UINT32_MAX)))
+						errx(1, "Expected a positive integer for --screen-min, but '%s' was given.", optarg);
+					screen.min_given = 1;
+				}
+				if (!strcmp(o, "screen-report")) screen.report_path = optarg;
 				if (!strcmp(o, "reference-list")) rect = 1, read_file_of_filenames(optarg, &ref_files);
 				if (!strcmp(o, "reference")) rect = 1, push_name(&ref_files, optarg);
 				if (!strcmp(o, "progress")) {
@@ -1137,6 +1253,9 @@ int main(int argc, char *argv[]) {
 	if (place.path && !rect) errx(1, "Placement (--place) needs references to place on: give --reference=FILE or --reference-list=FILE.");
 	if (place.path && !place.backbone_path) errx(1, "Placement (--place) needs the tree of the references: give --backbone=FILE.");
 	if (place.backbone_path && !place.path) errx(1, "A backbone tree (--backbone) needs somewhere to go: give --place=FILE.");
+	if (screen_given && !rect) errx(1, "A screen (--screen) needs references to choose from: give --reference=FILE or --reference-list=FILE.");
+	if (!screen_given && (screen.k_given || screen.scale_given || screen.min_given || screen.report_path))
+		errx(1, "The options --screen-kmer, --screen-scale, --screen-min and --screen-report need a screen: give --screen=K.");
 	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
 	if (trees_only && !any_out)
 		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
@@ -1145,6 +1264,7 @@ int main(int argc, char *argv[]) {
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
 	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
+	if (screen.report_path && !(screen.rf = fopen(screen.report_path, "w"))) err(1, "%s", screen.report_path);
 	tree.device_for_ctx = clus.device_for_ctx = opts.device;
 	if (join && files.n == 0) errx(1, "In join mode at least one filename needs to be supplied.");
 	if (files.n < (size_t)(join && !rect ? 2 : 1)) {
@@ -1154,7 +1274,7 @@ int main(int argc, char *argv[]) {
 
 	/* ANDI_HIP_CLI_TRACE=1: where the wall time goes -- reading the input, the matrix, printing it (stderr; scripts/full_size.py --cli) */
 	if (progress == P_AUTO && rect) progress = isatty(STDERR_FILENO) ? P_ALWAYS : P_NEVER;
-	if (rect) return run_rect(&ref_files, &files, join, verbose, truncate, progress == P_ALWAYS, &opts, &place);
+	if (rect) return run_rect(&ref_files, &files, join, verbose, truncate, progress == P_ALWAYS, &opts, &place, &screen);
 	const int cli_trace = getenv("ANDI_HIP_CLI_TRACE") != NULL;
 	struct timespec ts0, ts1, ts2, ts3;
 	clock_gettime(CLOCK_MONOTONIC, &ts0);

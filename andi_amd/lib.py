@@ -132,6 +132,16 @@ SYMBOLS = {
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
                                             C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_sketch": (C.c_int, [_P, C.POINTER(Seq), C.c_size_t, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "andi_hip_sketch_count": (C.c_size_t, [_P]),
+    "andi_hip_sketch_sizes": (C.c_int, [_P, _P, _P]),
+    "andi_hip_sketch_download": (C.c_int, [_P, _P, C.c_size_t, _P]),
+    "andi_hip_sketch_free": (None, [_P, _P]),
+    "andi_hip_sketch_timings": (C.c_int, [_P, _P]),
+    "andi_hip_sketch_shared": (C.c_int, [_P, _P, _P, _P]),
+    "andi_hip_screen_select": (C.c_int, [_P, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, _P, _P]),
+    "andi_hip_screen": (C.c_int, [C.POINTER(Seq), C.c_size_t, C.POINTER(Seq), C.c_size_t, C.c_int, C.c_uint64, C.c_int, _P, _P, _P,
+                                  C.c_char_p, C.c_size_t]),
     "andi_hip_device_count": (C.c_int, []),
     "andi_hip_reload_knobs": (None, []),
     "andi_hip_ctx_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_char_p, C.c_size_t]),
@@ -1070,3 +1080,85 @@ def dist_rect(refs, queries, p_value=0.025, model=M_JC, device=0, host_threads=0
     if L.andi_hip_dist_rect(MRQ.ctypes.data, MQR.ctypes.data, ra, nr, qa, nq, C.byref(o), err, len(err)):
         raise AndiHipError(err.value.decode())
     return MRQ, MQR
+
+
+# ---------------------------------------------------------------- the k-mer sketch screen
+class Sketches:
+    """The sketches of a set of sequences, resident on the context's device (andi_hip_sketch): len(), .sizes (uint32),
+    .hashes(i) (uint64, ascending), .timings() (ms: pack, upload, hash, sort), close()."""
+
+    def __init__(self, ctx: Context, seqs, k=21, scale=1000):
+        seqs = [bytes(s) for s in seqs]
+        arr = _seq_array(seqs) if seqs else None
+        self._ctx, self._h = ctx, _P()
+        self.k, self.scale = int(k), int(scale)
+        if not 0 <= int(scale) < 1 << 64:
+            raise AndiHipError("sketch: scale %r does not fit 64 bits" % (scale,))
+        ctx._check(load().andi_hip_sketch(ctx._h, arr, len(seqs), int(k), int(scale), C.byref(self._h)), "sketch")
+        n = load().andi_hip_sketch_count(self._h)
+        self.sizes = np.zeros(n, np.uint32)
+        ctx._check(load().andi_hip_sketch_sizes(ctx._h, self._h, self.sizes.ctypes.data), "sketch_sizes")
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def hashes(self, i):
+        out = np.zeros(int(self.sizes[i]), np.uint64)
+        self._ctx._check(load().andi_hip_sketch_download(self._ctx._h, self._h, int(i), out.ctypes.data), "sketch_download")
+        return out
+
+    def timings(self):
+        ms = np.zeros(4, np.float64)
+        load().andi_hip_sketch_timings(self._h, ms.ctypes.data)
+        return dict(zip(("pack_ms", "upload_ms", "hash_ms", "sort_ms"), ms.tolist()))
+
+    def close(self):
+        if self._h and self._ctx._h:
+            load().andi_hip_sketch_free(self._ctx._h, self._h)
+        self._h = _P()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def sketch(ctx: Context, seqs, k=21, scale=1000):
+    """andi_hip_sketch: the sketches of seqs (bytes over A C G T !) at k-mer length k and the given scale (the defaults are
+    sourmash's), as a Sketches object."""
+    return Sketches(ctx, seqs, k, scale)
+
+
+def sketch_shared(ctx: Context, A: Sketches, B: Sketches):
+    """andi_hip_sketch_shared: the uint32 array (len(A), len(B)) of the numbers of hashes sketch i of A and sketch j of B share."""
+    out = np.zeros((len(A), len(B)), np.uint32)
+    ctx._check(load().andi_hip_sketch_shared(ctx._h, A._h, B._h, out.ctypes.data), "sketch_shared")
+    return out
+
+
+def screen_select(shared, keep, min_shared=1):
+    """andi_hip_screen_select on the (nq, nr) counts: (kept, taken) -- kept[r] (bool) iff some query took reference r among its
+    best `keep` with at least max(1, min_shared) shared hashes, taken[q] (uint32) how many query q took.  No GPU."""
+    shared = np.ascontiguousarray(shared, dtype=np.uint32)
+    if shared.ndim != 2:
+        raise ValueError("screen_select: shared must be (nq, nr)")
+    nq, nr = shared.shape
+    kept, taken = np.zeros(nr, np.uint8), np.zeros(nq, np.uint32)
+    if load().andi_hip_screen_select(shared.ctypes.data, nq, nr, int(keep), int(min_shared), kept.ctypes.data, taken.ctypes.data):
+        raise AndiHipError("screen_select: bad arguments (nq and nr must be at least 1)")
+    return kept.astype(bool), taken
+
+
+def screen(refs, queries, k=21, scale=1000, device=0):
+    """andi_hip_screen, the one call: (shared (nq, nr) uint32, ref_sizes, query_sizes)."""
+    refs = [bytes(s) for s in refs]
+    queries = [bytes(s) for s in queries]
+    nr, nq = len(refs), len(queries)
+    shared = np.zeros((nq, nr), np.uint32)
+    rs, qs = np.zeros(nr, np.uint32), np.zeros(nq, np.uint32)
+    err = C.create_string_buffer(512)
+    if load().andi_hip_screen(_seq_array(refs) if refs else None, nr, _seq_array(queries) if queries else None, nq, int(k), int(scale),
+                              int(device), shared.ctypes.data, rs.ctypes.data, qs.ctypes.data, err, len(err)):
+        raise AndiHipError(err.value.decode(errors="replace"))
+    return shared, rs, qs

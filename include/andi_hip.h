@@ -23,7 +23,9 @@
  * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only); and linkage
  * clustering: andi_hip_linkage, andi_hip_linkage_batch, andi_hip_linkage_cut, andi_hip_cluster_medoids,
  * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only); and placement of queries on a tree:
- * andi_hip_place, andi_hip_distances_rect, andi_hip_parse_newick and andi_hip_format_jplace (additions only).
+ * andi_hip_place, andi_hip_distances_rect, andi_hip_parse_newick and andi_hip_format_jplace (additions only); and the k-mer
+ * sketch screen in front of the query-versus-reference mode: andi_hip_sketch and the calls around it,
+ * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -632,6 +634,61 @@ int andi_hip_parse_newick(const char *text, const char *const *names, size_t n, 
 size_t andi_hip_format_jplace(const andi_hip_nj_join *tree, size_t n, const char *const *ref_names, int truncate_names,
 							  const andi_hip_placement *placements, size_t nq, const char *const *query_names, int method,
 							  char *out, size_t cap);
+
+/* ------------------------------------------------------------------ */
+/* The k-mer sketch screen: which references are worth an exact run    */
+/* ------------------------------------------------------------------ */
+/* A screen in front of the query-versus-reference mode, as Mash and sourmash are put in front of exact methods: a sketch of
+ * every sequence, the number of hashes every (query, reference) pair shares, and a rule that keeps each query's best
+ * references.  Everything is an integer and exact (tests/sketch_model.py restates the contract in NumPy).
+ *
+ * Sketch(seq, k, scale), 4 <= k <= 32, scale >= 1; seq is an andi_hip_seq, bytes over A C G T !:
+ *  - a window is k consecutive bytes that are all in ACGT; a window that holds a '!' yields nothing, a sequence shorter
+ *    than k has no window;
+ *  - its forward code f: A = 0, C = 1, G = 2, T = 3, two bits a symbol, the first symbol most significant, a uint64; its
+ *    reverse-complement code r: the same coding of the reverse complement; its canonical code c = min(f, r);
+ *  - its hash h = fmix64(c), MurmurHash3's 64-bit finaliser: h ^= h >> 33; h *= 0xff51afd7ed558ccd; h ^= h >> 33;
+ *    h *= 0xc4ceb9fe1a85ec53; h ^= h >> 33; all arithmetic mod 2^64;
+ *  - the window is kept iff h <= UINT64_MAX / scale (integer division; scale = 1 keeps every window);
+ *  - the sketch is the set of the kept hashes, ascending, each once.  Its size fits a uint32.
+ * A sequence and its reverse complement have the same sketch.  shared(A, B) is the number of hashes in both sketches.
+ *
+ * andi_hip_sketch: the sketches of n sequences, device-resident.  The sequences are packed to 4-bit symbols
+ * (andi_hip_pack_symbols), uploaded and sketched in batches of bounded size through pinned buffers; only the sketches stay
+ * on the device, and the results do not depend on the batching.  A byte outside the alphabet of andi_hip_pack_symbols is
+ * refused through the context's error, as the scan refuses it (';', '#' and NUL end a window as '!' does).  Bad arguments (a
+ * NULL pointer, n == 0, k outside 4 ... 32, scale == 0, a sequence of more than (INT32_MAX - 1) / 2 bytes) fail with 1 before any
+ * HIP call; an empty sequence is allowed and has an empty sketch.  Scratch that does not fit the device fails through the
+ * context's error, which names the bytes; a batch may not yield 2^32 hashes or more.  Synchronous, on the context's stream.
+ * Free the result with andi_hip_sketch_free before the context is destroyed. */
+typedef struct andi_hip_sketches andi_hip_sketches; /* the sketches of a set of sequences in HBM */
+int andi_hip_sketch(andi_hip_ctx *ctx, const andi_hip_seq *seqs, size_t n, int k, uint64_t scale, andi_hip_sketches **out);
+size_t andi_hip_sketch_count(const andi_hip_sketches *s); /* n; 0 for NULL */
+/* the sizes of the n sketches (no HIP call: the host knows them) */
+int andi_hip_sketch_sizes(andi_hip_ctx *ctx, const andi_hip_sketches *s, uint32_t *sizes);
+/* the hashes of sketch idx, ascending: as many as its size says */
+int andi_hip_sketch_download(andi_hip_ctx *ctx, const andi_hip_sketches *s, size_t idx, uint64_t *hashes);
+void andi_hip_sketch_free(andi_hip_ctx *ctx, andi_hip_sketches *s);
+/* where the time of the call that made s went, in milliseconds: ms4[0] packing on the host, [1] the uploads and [2] the hash
+ * kernel's two passes (HIP events), [3] sort, unique and compaction (wall time with their synchronisations).  For
+ * scripts/screen_bench.py; returns 1 on a NULL pointer. */
+int andi_hip_sketch_timings(const andi_hip_sketches *s, double *ms4);
+/* shared[i * count(b) + j] = shared(sketch i of a, sketch j of b): host memory, count(a) x count(b), row-major.  Both sets
+ * must come from this context's device and have the same k and scale; otherwise the call fails through the context's
+ * error.  a == b is allowed.  A sketch of a is staged in LDS where it fits (20000 hashes) and searched in global memory
+ * where it does not; the numbers are the same.  Synchronous. */
+int andi_hip_sketch_shared(andi_hip_ctx *ctx, const andi_hip_sketches *a, const andi_hip_sketches *b, uint32_t *shared);
+/* Selection, on the host, no GPU: from shared (nq x nr, row-major) every query takes references in the order (shared
+ * descending, reference index ascending), the first `keep` of them whose count is >= max(1, min_shared).  kept[r] (nr
+ * bytes) = 1 iff any query took reference r, else 0; taken[q] (nq values; may be NULL) = the number of references query q
+ * took.  Returns 1 on a NULL shared or kept, nq == 0 or nr == 0. */
+int andi_hip_screen_select(const uint32_t *shared, size_t nq, size_t nr, size_t keep, uint32_t min_shared, uint8_t *kept,
+						   uint32_t *taken);
+/* The one call: a context on `device`, the sketches of both sets, shared[q * nr + r] (nq x nr), the sketch sizes
+ * (ref_sizes: nr values, query_sizes: nq; either may be NULL), everything freed.  Bad arguments (a NULL refs, queries or
+ * shared, nr or nq 0, k outside 4 ... 32, scale 0, a negative device) fail through errbuf before any HIP call. */
+int andi_hip_screen(const andi_hip_seq *refs, size_t nr, const andi_hip_seq *queries, size_t nq, int k, uint64_t scale,
+					int device, uint32_t *shared, uint32_t *ref_sizes, uint32_t *query_sizes, char *errbuf, size_t errlen);
 
 /* plain device memory helpers so callers need no HIP headers */
 int andi_hip_dev_alloc(andi_hip_ctx *ctx, size_t bytes, void **dptr);
