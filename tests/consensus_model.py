@@ -2,6 +2,8 @@
 andi_hip_format_newick_consensus; include/andi_hip.h), on support_model.leaf_sets: the distinct splits numbered by first
 appearance through a dict, their frequencies, the strict majority, parents by set containment, the sequential mean
 lengths and the Newick text.  What tests/test_consensus_*.py hold the library to."""
+import functools
+
 import numpy as np
 
 import nj_model
@@ -177,3 +179,94 @@ def other_final(J, n):
     K[n - 4]["a"], K[n - 4]["b"] = x, y
     K[n - 3]["a"], K[n - 3]["b"], K[n - 3]["c"] = p, q, z
     return K
+
+
+# ------------------------------------------------------------------ trees whose difference lies in the far words of the sets
+# A kernel that walks a set's W = ceil(n / 64) words 64 at a time takes its second trip at W > 64, n > 4096.  Two trees
+# that differ only where that trip reads are what shows a wrong one: a kernel that dropped the far words would call them equal.
+def swap_leaves(J, n, i, j):
+    """the same records with leaves i and j exchanged: a set that holds exactly one of them changes in bits i and j only"""
+    assert 0 <= i < n and 0 <= j < n and i != j
+    K = J.copy()
+    for f in "abc":
+        was_i, was_j = J[f] == i, J[f] == j
+        K[f][was_i], K[f][was_j] = j, i
+    return K
+
+
+def _record_of(J, n, v):
+    """(record, field) that has node v as a child"""
+    for f in "abc":
+        at = np.nonzero(J[f] == v)[0]
+        if len(at):
+            return int(at[0]), f
+    raise AssertionError("node %d is nobody's child" % v)
+
+
+def far_swap(J, n, i, j):
+    """swap_leaves for two leaves of the words a second trip reads (i, j >= 4096) that are not siblings"""
+    assert i >= 4096 and j >= 4096 and _record_of(J, n, i)[0] != _record_of(J, n, j)[0]
+    return swap_leaves(J, n, i, j)
+
+
+def near_swap(J, n, i, j):
+    """the control: two leaves of word 0 that are not siblings"""
+    assert i < 64 and j < 64 and _record_of(J, n, i)[0] != _record_of(J, n, j)[0]
+    return swap_leaves(J, n, i, j)
+
+
+def move_leaf(J, n, x):
+    """the same records with leaf x cut off and hung on the edge above another node z: the sets between the two places gain
+    or lose bit x and nothing else changes (at n = 4097 leaf 4096 is the only leaf of word 64, so no two can be swapped).
+    Record s of x, (y, x), becomes (z, x) -- z an earlier node whose parent is a later record --; y takes the place of
+    node n + s where that was a child, and node n + s the place of z."""
+    s, f = _record_of(J, n, x)
+    assert s < n - 4  # a pair record, and not the last one (other_final wants that node as the final record's third child)
+    y = int(J[s]["b" if f == "a" else "a"])
+    for z in range(64, n + s):
+        t, g = _record_of(J, n, z)
+        if z not in (x, y) and s < t:
+            break
+    else:
+        raise AssertionError("no place to hang leaf %d" % x)
+    K = J.copy()
+    up, h = _record_of(J, n, n + s)
+    K[s]["a"], K[s]["b"] = z, x
+    K[up][h] = y
+    K[t][g] = n + s
+    return K
+
+
+@functools.lru_cache(maxsize=None)
+def far_word_case(n):
+    """(tree, far, near, edge) for the tests of leaf sets around and past 64 words.  tree = random_tree(n, n); near = two
+    leaves of word 0 exchanged; far = a tree that lacks some of tree's splits and has in their place splits that differ from
+    them in bits >= edge = 64 * min(64, W - 1) alone: two
+    leaves of the second (and, where there is one, the third) trip exchanged; at n = 4097, where leaf 4096 is alone past
+    bit 4095, that leaf moved; at n <= 4096, where no word lies past the first trip, two leaves of the last word exchanged.
+    What the case says about itself is asserted here, on Python ints, without a device.  (Computed once per n and
+    shared: the records are not to be written to.)"""
+    W = (n + 63) // 64
+    edge = 64 * min(64, W - 1)
+    tree = random_tree(n, n)
+    if n == 4097:
+        far = move_leaf(tree, n, 4096)
+    else:
+        i, j = edge + 4 if edge + 4 < n - 1 else edge, n - 1
+        while _record_of(tree, n, i)[0] == _record_of(tree, n, j)[0]:
+            i += 1
+        far = far_swap(tree, n, i, j) if edge == 4096 else swap_leaves(tree, n, i, j)
+    i, j = 3, 40
+    while _record_of(tree, n, i)[0] == _record_of(tree, n, j)[0]:
+        j += 1
+    near = near_swap(tree, n, i, j)
+    low = (1 << edge) - 1
+    mine, theirs = support_model.leaf_sets(tree, n), support_model.leaf_sets(far, n)
+    lost, gained = set(mine) - set(theirs), set(theirs) - set(mine)
+    twin = {b & low: b for b in gained}
+    twins = [(a, twin[a & low]) for a in lost if a & low in twin]
+    # splits of tree that far lacks, each with a split of far beside it that the far words alone tell from it
+    assert twins and all(a != b and (a ^ b) & low == 0 for a, b in twins)
+    close = support_model.leaf_sets(near, n)
+    assert any(mine[s] != close[s] and (mine[s] ^ close[s]) >> 64 == 0 for s in range(n - 3))  # the control: word 0 alone
+    return tree, far, near, edge

@@ -1,8 +1,9 @@
 """The distinct splits of a bootstrap on the MI355X: andi_hip_nj_splits against tests/consensus_model.py -- ids by first
 appearance, frequencies and sets, all equal -- on hand-made records (the canonical side, the set-word edges, skip, a
 2000-leaf caterpillar against its mirror image) and on andi_hip_nj_batch's output; against andi_hip_nj_support; with
-the hash cut short so that collisions are the normal case; across a group boundary; and andi-hip -b N --consensus=FILE
+the hash cut short so that collisions are the normal case; on sets of more than 64 words, with and without the hash; across a group boundary; and andi-hip -b N --consensus=FILE
 end to end."""
+import functools
 import os
 import subprocess
 
@@ -183,6 +184,44 @@ def test_the_result_does_not_depend_on_the_hash(ctx, bits):
             assert _same(_check(ctx, reps), want)
         with knobs(SPLIT_HASH_BITS=bits, NJ_GROUP=2):  # ... and the table's entries too
             assert _same(_check(ctx, reps), want)
+
+
+@functools.lru_cache(maxsize=None)
+def _far_word_case(n):
+    """(replicates, the model's splits) for sets of 64, 65, 66 and 129 words, once per n (the model takes 0.3 s at n = 4161
+    and 1.4 s at n = 8193 on the host, nearly all of it the words of the distinct sets).  What the input is: the splits
+    the replicate `far` lacks and the ones it has in their place are distinct entries of the model's table, some pair of
+    them equal in every bit below the far words (consensus_model.far_word_case asserts that there is one), and far's other
+    writing -- one set built as its complement -- has far's splits, id for id."""
+    tree, far, near, edge = cm.far_word_case(n)
+    reps = [tree, far, near, cm.other_final(tree, n), cm.other_final(far, n), cm.caterpillar(n)]
+    ids, freq, sets = want = cm.splits(np.stack(reps))
+    lost = sorted(set(ids[0].tolist()) - set(ids[1].tolist()))
+    new = sorted(set(ids[1].tolist()) - set(ids[0].tolist()))
+    words = min(64, sets.shape[1] - 1)
+    assert lost and new and any((sets[a, :words] == sets[b, :words]).all() for a in lost for b in new)
+    assert ids[4].tolist() == ids[1].tolist() and reps[4].tobytes() != reps[1].tobytes()
+    return reps, want
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 4161, 8193])
+def test_splits_past_64_words_of_a_set(ctx, n):
+    """k_sets' second block, k_hash's and k_append's second (third) trip, the last word's mask in that trip: the table's
+    sets, ids and frequencies equal the model's where two replicates differ in the far words alone."""
+    reps, want = _far_word_case(n)
+    assert _same(_splits(ctx, reps), want)
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 4161, 8193])
+def test_splits_past_64_words_when_every_hash_collides(ctx, n):
+    """ANDI_SPLIT_HASH_BITS=0: every set lies in one run of equal keys, so only wave_same's walk over all W words -- its
+    second trip from word 64 on -- keeps the far-swapped sets apart, in k_class and, with ANDI_NJ_GROUP=2 (three groups),
+    against the table in k_lookup.  (The model is not run again, so 8193 leaves cost only the device's time here.)"""
+    reps, want = _far_word_case(n)
+    with knobs(SPLIT_HASH_BITS=0):
+        assert _same(_splits(ctx, reps), want)
+    with knobs(SPLIT_HASH_BITS=0, NJ_GROUP=2):
+        assert _same(_splits(ctx, reps), want)
 
 
 def test_splits_across_a_group_boundary(ctx):

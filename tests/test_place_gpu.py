@@ -1,5 +1,5 @@
 """andi_hip_place on the MI355X: bit-exact to the NumPy restatement (tests/place_model.py) on everything it returns, for
-both methods, across the tiles of k_place, on rows with pairs without a distance, on odd trees, in forced small groups of
+both methods, across the tiles of k_place, on rows with pairs without a distance, on odd trees, on a tree of 4097 leaves, in forced small groups of
 queries; its argument checks; and andi-hip --reference --backbone --place."""
 import json
 import os
@@ -177,6 +177,38 @@ def test_exact_recovery_under_ols(ctx):
         x, p = float(rng.integers(1, int(L[v] * 64))) / 64.0, float(rng.integers(0, 9)) / 64.0
         out = lib.place(ctx, J, pm.point_distances(J, n, v, x, p)[None, :], "ols")[0]
         assert (out["edge"], out["distal"], out["pendant"], out["err"], out["used"]) == (v, x, p, 0.0, n)
+
+
+def test_a_tree_whose_leaf_sets_have_65_words(ctx):
+    """n = 4097: W = 65, so k_sets runs a second block, and k_paths and k_place ask child_word for word (tile) 64 -- the
+    one that holds leaf 4096 alone.  (a) Exact recovery under OLS with lengths in 64ths (every sum exact, as in
+    test_exact_recovery_under_ols) of points on the edges of leaf 4096, of leaf 70 and of the inner node above leaf 4096,
+    whose set holds that leaf: a wrong bit 4096 puts the leaf on the wrong side of the edge and the error is no longer 0.
+    (b) Two noisy queries under FM, bit for bit against the model, every edge.  The table T is 268 MB on the device; the
+    host's part dominates: the model's path lengths take 0.6 s and its two queries 6 s (measured; hence FM only and two
+    queries), the device's calls a small fraction of that."""
+    from andi_amd import lib
+    n = 4097
+    rng = np.random.default_rng(n)
+    J = pm.random_tree(rng, n, lambda m: rng.integers(2, 17, m) / 64.0)
+    H, below, parent, L = pm.paths(J, n)
+    E = 2 * n - 3
+
+    def point(v, x, p):  # (place_model.point_distances, on the paths computed once)
+        return np.where(below[v], (p + x) + H[v], (p + (L[v] - x)) + H[parent[v]])
+
+    above = int(parent[4096])
+    assert above < E and below[above, 4096] and below[above].sum() >= 2 and not below[70, 4096]
+    want = [(4096, 1 / 64.0, 3 / 64.0), (70, 1 / 64.0, 0.0), (above, (L[above] * 64 - 1) / 64.0, 5 / 64.0)]
+    out = lib.place(ctx, J, np.stack([point(*w) for w in want]), "ols")
+    for q, (v, x, p) in enumerate(want):
+        assert (out["edge"][q], out["distal"][q], out["pendant"][q], out["err"][q], out["used"][q]) == (v, x, p, 0.0, n), q
+    # (b)
+    D = np.stack([point(above, 0.5 * L[above], 0.02), point(int(rng.integers(E)), 0.0, 0.03)])
+    D = D * (1.0 + rng.uniform(-0.03, 0.03, D.shape))
+    got, model = lib.place(ctx, J, D, "fm", per=True), pm.place(J, D, "fm", per=True)
+    _same(got, model)
+    assert (model[0]["edge"] >= 0).all() and np.isfinite(model[1]).all()
 
 
 def test_bad_arguments_and_records_leave_the_context_usable(ctx):

@@ -1,6 +1,6 @@
 """The k-mer sketch screen on the device (andi_amd/csrc/sketch.hip) against its contract in NumPy (tests/sketch_model.py):
-sketches at every window shape the hash kernel can meet, the shared counts through LDS and through global memory, the
-one call, and andi-hip --screen.  Every device result must be EQUAL to the model's."""
+sketches at every window shape the hash kernel can meet, the shared counts through LDS and through global memory, at the
+sketch sizes where k_shared's launch changes and against more sketches than its wavefronts take in one trip, the one call, and andi-hip --screen.  Every device result must be EQUAL to the model's."""
 import json
 import os
 import subprocess
@@ -115,13 +115,19 @@ def test_a_scale_that_empties_every_sketch(ctx, cases):
 K16 = 16
 
 
-def _kmer_sets():
-    """Sequences whose sketches (k = 16, scale = 1) are chosen sets of hashes: 16-mers joined by '!', one window each.
-    pool: distinct random 16-mers in ascending order of their hash."""
+def _kmer_pool():
+    """distinct random 16-mers in ascending order of their hash"""
     rng = np.random.default_rng(77)
     kmers = sorted({rand_dna(rng, K16) for _ in range(700)}, key=lambda m: int(sm.sketch(m, K16, 1)[0]))
     hashes = [int(sm.sketch(m, K16, 1)[0]) for m in kmers]
     assert len(set(hashes)) == len(hashes)
+    return kmers
+
+
+def _kmer_sets():
+    """Sequences whose sketches (k = 16, scale = 1) are chosen sets of hashes: 16-mers joined by '!', one window each.
+    pool: distinct random 16-mers in ascending order of their hash."""
+    kmers = _kmer_pool()
     join = lambda idx: b"!".join(kmers[i] for i in idx)
     n = len(kmers)
     sets = {
@@ -177,6 +183,127 @@ def test_shared_counts_through_lds_and_through_global_memory(ctx, kmer_sets):
         forced1 = andi_amd.sketch_shared(ctx, S, S)
     assert np.array_equal(free, M) and np.array_equal(forced, M) and np.array_equal(forced1, M)
     S.close()
+
+
+# ---------------------------------------------------------------- k_shared: the sizes at which its launch changes
+LDS_64K = 65536 // 8   # hashes: up to here the launch takes its dynamic LDS without asking for the attribute
+LDS_MAX = 20000        # sketch.hip: SKETCH_LDS_MAX, the longest sketch that is staged (160 000 bytes)
+STAGED_SIZES = [100, LDS_64K, LDS_64K + 1, LDS_MAX, LDS_MAX + 1, 25000]
+
+
+def _prefix_with(seq, size):
+    """the shortest prefix of seq whose model sketch (k = 16, scale = 1) has exactly `size` hashes: a base more adds at
+    most one hash, so the sizes of the prefixes pass through every number on their way up"""
+    lo, hi = 0, len(seq)
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if len(sm.sketch(seq[:mid], K16, 1)) < size:
+            lo = mid + 1
+        else:
+            hi = mid
+    return seq[:lo]
+
+
+def _mutated(rng, seq, rate):
+    b = np.frombuffer(seq, np.uint8).copy()
+    at = np.nonzero(rng.random(len(b)) < rate)[0]
+    b[at] = np.frombuffer(b"CGTA", np.uint8)[np.searchsorted(np.frombuffer(b"ACGT", np.uint8), b[at])]
+    return b.tobytes()
+
+
+def _sized_sketches():
+    """(A, B, the model's sketches of both): A has sketches of exactly STAGED_SIZES hashes (prefixes of one random
+    sequence, so each holds the ones before it) and an empty one; B has the same, prefixes of an unrelated sequence, and
+    copies of three of A's with a base in 50 changed -- counts that are full, zero and in between."""
+    rng = np.random.default_rng(160000)
+    seq, other = rand_dna(rng, 26_000), rand_dna(rng, 26_000)
+    A = [_prefix_with(seq, s) for s in STAGED_SIZES] + [b""]
+    B = A + [other[:5000], other] + [_mutated(rng, A[i], 0.02) for i in (1, 2, 5)]
+    wa, wb = _model(A, K16, 1), _model(B, K16, 1)
+    assert [len(w) for w in wa] == STAGED_SIZES + [0]
+    M = sm.shared_matrix(wa, wb)
+    assert M[:6, :6].tolist() == [[min(a, b) for b in STAGED_SIZES] for a in STAGED_SIZES] and not M[:, 6:9].any()
+    for col, i in zip((9, 10, 11), (1, 2, 5)):  # a changed base takes up to 16 windows with it: some hashes stay, not all
+        assert 0 < M[0, col] < 100 and STAGED_SIZES[i] // 4 < M[i, col] < STAGED_SIZES[i]
+    return A, B, wa, wb
+
+
+@pytest.fixture(scope="module")
+def sized_sketches():
+    return _sized_sketches()
+
+
+def _assert_shared(ctx, S, T, want_s, want_t):
+    import andi_amd
+    got = andi_amd.sketch_shared(ctx, S, T)
+    assert got.dtype == np.uint32 and np.array_equal(got, sm.shared_matrix(want_s, want_t))
+
+
+def test_shared_counts_at_the_sizes_where_the_launch_changes(ctx, sized_sketches):
+    """The first set's longest staged sketch decides k_shared's launch: up to 8192 hashes it takes 65 536 bytes of dynamic
+    LDS as it is; from 8193 on it asks for the attribute first; with 20000 it takes all 160 000 bytes, and in that same
+    launch the sketches of 20001 and 25000 hashes are searched in global memory.  In this order, so that a process that
+    runs this test first meets the launches in ascending order of what they ask for."""
+    import andi_amd
+    A, B, wa, wb = sized_sketches
+    SB = andi_amd.sketch(ctx, B, K16, 1)
+    _assert_sketches(SB, wb)
+    for upto in (LDS_64K, LDS_64K + 1, 25000):
+        keep = [i for i, w in enumerate(wa) if len(w) <= upto]
+        SA = andi_amd.sketch(ctx, [A[i] for i in keep], K16, 1)
+        part = [wa[i] for i in keep]
+        assert max(len(w) for w in part) == upto
+        _assert_sketches(SA, part)
+        _assert_shared(ctx, SA, SB, part, wb)
+        _assert_shared(ctx, SA, SA, part, part)
+        if upto == 25000:
+            _assert_shared(ctx, SB, SA, wb, part)
+        SA.close()
+    SB.close()
+
+
+def test_shared_counts_of_long_sketches_forced_through_global_memory(ctx, sized_sketches):
+    """ANDI_SKETCH_LDS=64: none of these sketches but the empty one is staged.  Equal numbers."""
+    import andi_amd
+    A, B, wa, wb = sized_sketches
+    SA, SB = andi_amd.sketch(ctx, A, K16, 1), andi_amd.sketch(ctx, B, K16, 1)
+    with knobs(SKETCH_LDS=64):
+        _assert_shared(ctx, SA, SB, wa, wb)
+        _assert_shared(ctx, SB, SA, wb, wa)
+    SA.close(), SB.close()
+
+
+def _many_sketches(nb):
+    """(A, B, the model's sketches of both, the model's counts): B has nb sketches of 1 to 70 16-mers of the pool, A five --
+    65 hashes, the whole pool, one hash, none, 200.  k_shared gives a block's four wavefronts the sketches b = 4 * group +
+    wave of B and then every 256th from there (64 groups), so b >= 256 is the loop's second trip and b >= 512 its third;
+    nb = 256 is the last size with one.  An empty sketch sits in the second trip at b = 258."""
+    kmers = _kmer_pool()
+    rng = np.random.default_rng(nb)
+    join = lambda idx: b"!".join(kmers[i] for i in idx)
+    A = [join(range(100, 165)), join(range(len(kmers))), join([5]), b"", join(range(50, 250))]
+    B = [join(rng.choice(len(kmers), int(rng.integers(1, 71)), replace=False)) for _ in range(nb)]
+    if nb > 258:
+        B[258] = b""
+    wa, wb = _model(A, K16, 1), _model(B, K16, 1)
+    M = sm.shared_matrix(wa, wb)
+    assert [len(w) for w in wa] == [65, len(kmers), 1, 0, 200] and all(1 <= len(w) <= 70 for b, w in enumerate(wb) if b != 258)
+    assert M[1].tolist() == [len(w) for w in wb] and M[:, -1].any() and not M[3].any()  # the last column is live
+    assert 0 < M[0].sum() < M[1].sum() and 0 < M[4].sum() < M[1].sum() and (M[0] != M[4]).any()
+    if nb > 256:  # ... and so is the first of the second trip
+        assert M[:, 256].any() and (nb <= 258 or not M[:, 258].any())
+    return A, B, wa, wb, M
+
+
+@pytest.mark.parametrize("nb", [256, 257, 261, 600])
+def test_shared_counts_against_more_sketches_than_one_trip_takes(ctx, nb):
+    import andi_amd
+    A, B, wa, wb, M = _many_sketches(nb)
+    SA, SB = andi_amd.sketch(ctx, A, K16, 1), andi_amd.sketch(ctx, B, K16, 1)
+    _assert_sketches(SB, wb)
+    assert np.array_equal(andi_amd.sketch_shared(ctx, SA, SB), M)
+    assert np.array_equal(andi_amd.sketch_shared(ctx, SB, SA), M.T)
+    SA.close(), SB.close()
 
 
 def test_sketch_sets_of_another_k_or_scale_are_refused(ctx):

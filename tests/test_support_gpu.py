@@ -1,13 +1,14 @@
 """Bootstrap support on the MI355X: andi_hip_nj_batch bit for bit against andi_hip_nj per matrix (and tests/nj_model.py)
 at the tile edges, past 1024 active nodes, on ties, with bad matrices and across a group boundary; andi_hip_nj_support
 against tests/support_model.py on hand-made records (the canonical side, the set-word edges, a 2000-leaf caterpillar,
-skip) and on neighbor-joining output; and andi-hip -b N --support=FILE end to end."""
+sets of more than 64 words, skip) and on neighbor-joining output; and andi-hip -b N --support=FILE end to end."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import consensus_model as cm
 import nj_model
 import support_model
 from conftest import ROOT, knobs
@@ -189,6 +190,34 @@ def test_support_at_the_set_word_edges(ctx, n):
     assert _check(ctx, tree, reps)[-1] >= 2
     assert _check(ctx, _caterpillar(n), reps) [0] >= 2
     assert _check(ctx, _other_final(tree, n), [tree]) == [1] * (n - 3)
+
+
+def _far_word_case(n):
+    """(tree, far, replicates) for sets of 64, 65, 66 and 129 words.  The replicate `far` differs from the tree in the far
+    words alone (consensus_model.far_word_case, asserted there on Python ints); what follows from it, from the model: far
+    lacks some of the tree's splits, the control `near` (two leaves of word 0 exchanged) lacks others, so among the
+    replicates a split far lacks counts 3 (or 2), one near lacks 4, every other 5."""
+    tree, far, near, edge = cm.far_word_case(n)
+    assert tree.tobytes() == _random_tree(n, n).tobytes()
+    reps = [tree, far, near, _other_final(tree, n), _other_final(far, n), _caterpillar(n)]
+    of_far, of_near = support_model.support(tree, [far]), support_model.support(tree, [near])
+    assert 0 in of_far and 0 in of_near and of_far != of_near and support_model.support(tree, [tree]) == [1] * (n - 3)
+    want = support_model.support(tree, reps)
+    assert max(want) == 5 and 3 in want and 4 in want and all((v <= 3) == (f == 0) for v, f in zip(want, of_far))
+    return tree, far, reps
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 4161, 8193])
+def test_support_past_64_words_of_a_set(ctx, n):
+    """W = 64, 65, 66, 129 words: k_sets' second block, the second (third) trip of k_hash's lane-strided loop, k_match past
+    word 63, and canonical_word's mask on a last word that lies in that trip (n = 4097: bit 0 of word 64 alone).  A
+    count that ignored the far words would be 5 where the model says 3."""
+    tree, far, reps = _far_word_case(n)
+    _check(ctx, tree, reps)
+    # the complement's side: in _other_final(far) one set is built as the other side, so its canonical side is taken
+    # through the last word's mask; every split of far is found in it and the other way round
+    assert _check(ctx, far, [_other_final(far, n)]) == [1] * (n - 3)
+    assert _check(ctx, _other_final(far, n), [far, tree]) == [1 + v for v in support_model.support(_other_final(far, n), [tree])]
 
 
 def test_support_skip_and_a_single_replicate(ctx):

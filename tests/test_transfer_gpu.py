@@ -1,5 +1,5 @@
 """Transfer bootstrap support on the MI355X: andi_hip_nj_transfer against tests/transfer_model.py on hand-made records at
-the set-word edges, the tile edges of k_transfer and past one chunk of words; the hand case that pins the cap; equal
+the set-word edges, the tile edges of k_transfer, past one chunk of words and past 64 words; the hand case that pins the cap; equal
 topologies; the zero-count cross-check against andi_hip_nj_support on neighbor-joining output; skip, bad records, groups
 and chunked calls; and andi-hip -b N --transfer=FILE end to end."""
 import os
@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import consensus_model as cm
 import nj_model
 import support_model
 import transfer_model
@@ -124,6 +125,37 @@ def test_transfer_past_one_chunk_of_words(ctx, n, count):
     reps = [_moved(tree, n, 1, n // 16), _random_tree(n, n + 1), tree][:count]
     depth, total, per = _check(ctx, tree, reps, numpy=True)
     assert (per[0] > 0).any() and (per[0] == 0).any()
+
+
+def _far_word_case(n):
+    """(tree, replicates, the model's result) for sets of 64, 65 and 66 words: consensus_model.far_word_case's tree, the
+    tree `far` that differs from it in the far words alone, and `near` (two leaves of word 0 exchanged) in its other
+    writing.  What the input is, from the model: the branches far lacks are at distance 2 from far's nearest branch where
+    two leaves were exchanged and 1 where one was moved (n = 4097) -- all of it past bit 4095 (at n = 4096: in word 63),
+    so a kernel that dropped those words would give 0."""
+    tree, far, near, edge = cm.far_word_case(n)
+    reps = [far, _other_final(near, n)]
+    want = transfer_model.transfer_numpy(tree, reps)
+    depth, total, per = want
+    mine, theirs = support_model.leaf_sets(tree, n), set(support_model.leaf_sets(far, n))
+    lost = [s for s in range(n - 3) if mine[s] not in theirs]
+    away = 1 if n == 4097 else 2
+    assert lost and (per[0][lost] > 0).all() and (per[0][lost] == away).any() and per[0].sum() == per[0][lost].sum()
+    assert (per[1] > 0).any() and (per[1][lost] == 0).any()  # the control loses other branches
+    return tree, reps, want
+
+
+# W = 64: the last size at which k_depth's lanes take one trip and k_transfer 8 chunks; 65: a ninth chunk of one word, and
+# that word holds bit 4096 alone; 66: a ninth chunk of two.  The NumPy statement takes 2 s per size on the host (float32
+# products of 4158 x 4161 zeros and ones: sums below 2^24, exact); the device's part is a few milliseconds.
+@pytest.mark.parametrize("n", [4096, 4097, 4161])
+def test_transfer_past_64_words_of_a_set(ctx, n):
+    from andi_amd import lib
+    tree, reps, want = _far_word_case(n)
+    depth, total, per = lib.nj_transfer(ctx, tree, np.stack(reps), per=True)
+    assert depth.tolist() == want[0].tolist() and per.tolist() == want[2].tolist() and total.tolist() == want[1].tolist()
+    d2, t2 = lib.nj_transfer(ctx, tree, np.stack(reps))  # per == NULL: the same sums
+    assert d2.tolist() == depth.tolist() and t2.tolist() == total.tolist()
 
 
 def test_transfer_hand_case_pins_the_cap(ctx):
