@@ -1,6 +1,6 @@
-// api_internal.h — what the library's host translation units share (api.hip, scan_call.hip, seam.hip, nj.hip and the
-// calls on nj_sets.h): the objects behind the C-ABI's handles, the error helpers, the scope of a call's device buffers
-// (DevScope), the size of a group of replicates (nj_group_size), and the helpers the scan call and the seam take from api.hip.
+// api_internal.h — what the library's host translation units share (api.hip, scan_call.hip, seam.hip and the tree calls
+// on rep_groups.h and nj_sets.h): the objects behind the C-ABI's handles, the error helpers, the scope of a call's device
+// buffers (DevScope), the size of a group (nj_group_size), and the helpers the scan call and the seam take from api.hip.
 // Private: no kernel code, nothing of it is exported (the functions declared here are hidden).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -155,8 +155,9 @@ hipError_t dmalloc(T **p, size_t count) {
 }
 
 // The device buffers of one call.  alloc() is dmalloc() that remembers what it handed out and does nothing once an
-// allocation has failed (err keeps the first failure, so a run of allocs is checked once, behind it).  The scope's end
-// waits for the stream -- nothing in flight uses the buffers then, also on an error exit -- and gives them all back.
+// allocation has failed (err keeps the first failure, so a run of allocs is checked once, behind it).  release() waits
+// for the stream -- nothing in flight uses the buffers then, also on an error exit --, gives them all back and leaves
+// the scope as new, for a caller that tries again with less (rep_groups.h); the scope's end is a release().
 struct DevScope {
 	hipStream_t stream;
 	hipError_t err = hipSuccess;
@@ -166,23 +167,26 @@ struct DevScope {
 	void alloc(T **p, size_t count) {
 		if (err == hipSuccess && (err = dmalloc(p, count)) == hipSuccess) held.push_back(*p);
 	}
-	~DevScope() {
+	void release() {
 		(void)hipStreamSynchronize(stream);
 		for (void *p : held) (void)andi_arena::dev_free(p, false);
+		held.clear();
+		err = hipSuccess;
 	}
+	~DevScope() { release(); }
 	DevScope(const DevScope &) = delete;
 	DevScope &operator=(const DevScope &) = delete;
 };
 
-// The replicates of one group, for every call that takes replicates as its grids' second dimension (nj.hip, nj_sets.h):
-// as many as `budget` bytes of device memory hold at `each` bytes per replicate -- at least one, at most what that
-// dimension takes.  Test hook ANDI_NJ_GROUP: a size of the test's choosing, within the same bounds.
-size_t nj_group_size(size_t budget, size_t each) {
-	constexpr size_t MAX_GROUP = 65535;
+// The members of one group, for every call that takes its items some at a time (the replicates of rep_groups.h and
+// nj_sets.h, place.hip's queries): as many as `budget` bytes of device memory hold at `each` bytes per member -- at least
+// one, at most `max`, what the grid dimension they go by takes.  `knob` is the call's test hook (ANDI_NJ_GROUP,
+// ANDI_PLACE_GROUP): a size of the test's choosing, within the same bounds.
+size_t nj_group_size(AndiKnob knob, size_t max, size_t budget, size_t each) {
 	size_t G = budget / each;
-	if (const char *v = andi_knob(KNOB_NJ_GROUP))
+	if (const char *v = andi_knob(knob))
 		if (atoll(v) >= 1) G = (size_t)atoll(v);
-	return G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
+	return G < 1 ? 1 : G > max ? max : G;
 }
 
 void resolve_events(andi_hip_ctx *ctx) {

@@ -7,7 +7,8 @@
 // slot of its two children, the other slot retires), the active slots an ascending compacted list ping-ponged between two
 // buffers, the REPLICATE as every grid's second dimension (andi_hip_linkage_batch; the single call is the group of one),
 // no host synchronisation between steps, no grid-wide barrier, no in-launch hand-off between blocks, one D2H copy of the
-// records at the end.
+// records at the end.  The host code around a group's steps is not a copy of nj.hip's but the same code (rep_groups.h:
+// the group's size and buffers, the loop over the groups, what happens to an unusable matrix, the buffers' lifetime).
 //
 // Unlike nj.hip no step searches the active triangle.  Every active row keeps its NEAREST NEIGHBOUR: nn[x], the least
 // (d, id_lo, id_hi) over the pairs of x with every other active slot, in the contract's order (better(), nj_cand.h).  The
@@ -29,12 +30,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "api_internal.h"
 #include "nj_cand.h"
+#include "rep_groups.h"
 
 static_assert(sizeof(andi_hip_link) == 24, "andi_hip_link: 2 ids, size, pad, height");
 
@@ -172,16 +171,7 @@ __global__ __launch_bounds__(JOIN_THREADS) void k_link_join(double *__restrict__
 	}
 }
 
-constexpr unsigned long long NOT_BAD = ~0ull;
-constexpr size_t GROUP_BYTES = (size_t)4 << 30; // andi_hip_linkage_batch: device memory of a group of replicates, at most (one always fits)
-
-// device bytes of one replicate: D, the caches, the lists, the sizes, the last join's slots, the records, the bad word
-size_t replicate_bytes(size_t n) {
-	return n * n * sizeof(double) + n * sizeof(Cand) + 3 * n * sizeof(int32_t) + n * sizeof(uint32_t) + sizeof(Joined) +
-		   (n - 1) * sizeof(andi_hip_link) + sizeof(unsigned long long);
-}
-
-// the buffers of a group of g replicates of n x n, one replicate after the other in each
+// the buffers of a group of g replicates of n x n, one replicate after the other in each (rep_groups.h: alloc_group)
 struct LinkBuffers {
 	double *D = nullptr;
 	Cand *nn = nullptr;
@@ -190,62 +180,31 @@ struct LinkBuffers {
 	Joined *joined = nullptr;
 	andi_hip_link *rec = nullptr;
 	unsigned long long *bad = nullptr;
+
+	// device bytes of one replicate: D, the caches, the lists, the sizes, the last join's slots, the records, the bad word
+	static size_t replicate_bytes(size_t n) {
+		return n * n * sizeof(double) + n * sizeof(Cand) + 3 * n * sizeof(int32_t) + n * sizeof(uint32_t) + sizeof(Joined) +
+			   (n - 1) * sizeof(andi_hip_link) + sizeof(unsigned long long);
+	}
+	hipError_t alloc(DevScope &dev, size_t n, size_t g) {
+		dev.alloc(&D, g * n * n), dev.alloc(&nn, g * n), dev.alloc(&lists, g * 3 * n), dev.alloc(&size, g * n);
+		dev.alloc(&joined, g), dev.alloc(&rec, g * (n - 1)), dev.alloc(&bad, g);
+		return dev.err;
+	}
 };
 
-// (the caller has waited for the stream)
-void link_free(LinkBuffers &b) {
-	for (void *p : {(void *)b.D, (void *)b.nn, (void *)b.lists, (void *)b.size, (void *)b.joined, (void *)b.rec, (void *)b.bad})
-		if (p) (void)andi_arena::dev_free(p, false);
-	b = LinkBuffers{};
-}
-
-hipError_t link_alloc(LinkBuffers &b, size_t n, size_t g) {
-	hipError_t e = dmalloc(&b.D, g * n * n);
-	if (e == hipSuccess) e = dmalloc(&b.nn, g * n);
-	if (e == hipSuccess) e = dmalloc(&b.lists, g * 3 * n);
-	if (e == hipSuccess) e = dmalloc(&b.size, g * n);
-	if (e == hipSuccess) e = dmalloc(&b.joined, g);
-	if (e == hipSuccess) e = dmalloc(&b.rec, g * (n - 1));
-	if (e == hipSuccess) e = dmalloc(&b.bad, g);
-	return e;
-}
-
-// as many replicates as GROUP_BYTES hold (nj_group_size, api_internal.h), as there are; G receives the group's size
-hipError_t link_alloc_group(LinkBuffers &b, size_t n, size_t count, size_t &G) {
-	G = nj_group_size(GROUP_BYTES, replicate_bytes(n));
-	if (G > count) G = count;
-	hipError_t e = link_alloc(b, n, G);
-	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix the single call needs too
-		link_free(b);
-		(void)hipGetLastError();
-		G = (G + 1) / 2;
-		e = link_alloc(b, n, G);
-	}
-	return e;
-}
-
-// The clustering of g host matrices (one after the other) in buffers for at least g: bad[k] receives replicate k's first
-// -inf entry (i * n + j) or NOT_BAD, links the records of all g when at least one matrix is usable -- and nothing when
-// none is.  As in nj_group a bad replicate among good ones is not kept out of the step kernels: every index comes from
-// the lists, the ids and the cached slots, never from a distance, and better() and none() make every pick a real pair of
-// active slots whatever D holds, so its steps fault nothing and leave records the caller zeroes.  Synchronous; the one
-// host synchronisation before the steps is the read of the bad words, none between steps.
+// The clustering of g host matrices (one after the other) in buffers for at least g, between group_begin and group_end
+// (rep_groups.h: what bad is; the init kernel is k_link_init, an unusable entry a -inf): links receives the records of all
+// g when at least one matrix is usable -- and nothing when none is.  Synchronous; no host synchronisation between steps.
 hipError_t link_group(andi_hip_ctx *ctx, const LinkBuffers &b, const double *D, uint32_t N, uint32_t g, int method,
 					  andi_hip_link *links, unsigned long long *bad) {
 	const size_t n = N;
 	hipStream_t st = ctx->stream;
-	hipError_t e = hipMemcpyAsync(b.D, D, g * n * n * sizeof(double), hipMemcpyHostToDevice, st);
-	if (e == hipSuccess) e = hipMemsetAsync(b.bad, 0xff, g * sizeof *bad, st);
-	if (e == hipSuccess) {
-		k_link_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.size, b.bad);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess) e = hipMemcpyAsync(bad, b.bad, g * sizeof *bad, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) return e;
-	bool any_good = false;
-	for (uint32_t k = 0; k < g; ++k) any_good |= bad[k] == NOT_BAD;
-	if (!any_good) return hipSuccess;
+	bool any_good;
+	hipError_t e = group_begin(
+		st, b.D, D, n, g, b.bad, bad, nullptr, [&] { k_link_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.size, b.bad); },
+		any_good);
+	if (e != hipSuccess || !any_good) return e;
 	uint32_t cur = 0; // where in a replicate's lists the current act list starts: 0 or n
 	k_link_nn<<<dim3((N + 3) / 4, g), 256, 0, st>>>(b.D, N, b.lists, cur, N, b.nn, b.joined, 1);
 	e = hipGetLastError();
@@ -256,9 +215,7 @@ hipError_t link_group(andi_hip_ctx *ctx, const LinkBuffers &b, const double *D, 
 		if (r - 1 >= 2) k_link_nn<<<dim3((r - 1 + 3) / 4, g), 256, 0, st>>>(b.D, N, b.lists, cur, r - 1, b.nn, b.joined, 0);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) e = hipMemcpyAsync(links, b.rec, g * (n - 1) * sizeof *links, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	return e;
+	return e == hipSuccess ? group_end(st, links, b.rec, g * (n - 1)) : e;
 }
 
 bool bad_method(int method) { return method != ANDI_LINK_SINGLE && method != ANDI_LINK_COMPLETE && method != ANDI_LINK_AVERAGE; }
@@ -273,22 +230,19 @@ int andi_hip_linkage(andi_hip_ctx *ctx, const double *D, size_t n, int method, a
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	DevScope dev(ctx->stream);
 	LinkBuffers b;
 	unsigned long long bad = NOT_BAD;
-	std::vector<andi_hip_link> out(n - 1); // (nothing is written to links unless the matrix is usable)
-	hipError_t e = link_alloc(b, n, 1);
-	if (e == hipSuccess) e = link_group(ctx, b, D, (uint32_t)n, 1, method, out.data(), &bad);
-	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
-	link_free(b);
+	hipError_t e = b.alloc(dev, n, 1);
+	if (e == hipSuccess) e = link_group(ctx, b, D, (uint32_t)n, 1, method, links, &bad); // (an unusable matrix: nothing reaches links)
 	if (e != hipSuccess) return fail(ctx, "andi_hip_linkage", e);
 	if (bad != NOT_BAD) {
-		const size_t i = (size_t)(bad / n), j = (size_t)(bad % n);
+		const Entry at = bad_entry(bad, n);
 		char msg[160];
-		snprintf(msg, sizeof msg, "andi_hip_linkage: D[%zu][%zu] is -inf", i, j);
+		snprintf(msg, sizeof msg, "andi_hip_linkage: D[%zu][%zu] is -inf", at.i, at.j);
 		ctx->err = msg;
 		return 1;
 	}
-	memcpy(links, out.data(), (n - 1) * sizeof *links);
 	return 0;
 }
 
@@ -301,22 +255,14 @@ int andi_hip_linkage_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t 
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const size_t nrec = n - 1;
+	DevScope dev(ctx->stream);
 	LinkBuffers b;
 	size_t G = 0;
-	hipError_t e = link_alloc_group(b, n, count, G);
-	std::vector<unsigned long long> hb(G);
-	for (size_t first = 0; e == hipSuccess && first < count; first += G) {
-		const size_t g = count - first < G ? count - first : G;
-		andi_hip_link *L = links + first * nrec;
-		e = link_group(ctx, b, D + first * n * n, (uint32_t)n, (uint32_t)g, method, L, hb.data());
-		for (size_t k = 0; e == hipSuccess && k < g; ++k) {
-			bad[first + k] = hb[k] == NOT_BAD ? -1 : (int64_t)hb[k];
-			if (hb[k] != NOT_BAD) memset(L + k * nrec, 0, nrec * sizeof *L);
-		}
-	}
-	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
-	link_free(b);
+	hipError_t e = alloc_group(dev, b, n, count, G);
+	if (e == hipSuccess)
+		e = for_groups(count, G, n - 1, links, bad, [&](size_t first, size_t g, andi_hip_link *L, unsigned long long *hb) {
+			return link_group(ctx, b, D + first * n * n, (uint32_t)n, (uint32_t)g, method, L, hb);
+		});
 	if (e != hipSuccess) return fail(ctx, "andi_hip_linkage_batch", e);
 	return 0;
 }

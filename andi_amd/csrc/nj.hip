@@ -16,20 +16,20 @@
 // Every kernel takes the REPLICATE as its grid's second dimension (andi_hip_nj_batch): matrices of one n are all at the
 // same r at step s, so a step of a whole group of them is still these three launches.  The buffers hold one replicate
 // after the other -- D (n x n), R (n), the lists (two act lists and the ids: 3n), the tile results, the records -- and a
-// block offsets its pointers by blockIdx.y.  andi_hip_nj is the group of one.
+// block offsets its pointers by blockIdx.y.  andi_hip_nj is the group of one.  The host code around a group's steps --
+// its size and buffers, the loop over the groups, what happens to an unusable matrix, the buffers' lifetime -- is
+// rep_groups.h's, shared with linkage.hip; here are the kernels, a replicate's buffers and the step loop.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
 
 #include "api_internal.h"
 #include "bootstrap.h"
 #include "nj_cand.h" // Cand, better, none, wave_min, block_min
+#include "rep_groups.h"
 
 static_assert(sizeof(andi_hip_nj_join) == 40, "andi_hip_nj_join: 3 ids, pad, 3 lengths");
 
@@ -217,70 +217,40 @@ uint64_t tiles_of(uint32_t r) {
 	return t * (t + 1) / 2;
 }
 
-constexpr unsigned long long NOT_BAD = ~0ull;
-constexpr size_t GROUP_BYTES = (size_t)4 << 30; // andi_hip_nj_batch: device memory of a group of replicates, at most (one always fits)
+size_t records_of(size_t n) { return n == 2 ? 1 : n - 2; }
 
-// device bytes of one replicate: D, R, the lists, the tile results, the records, the bad word
-size_t replicate_bytes(size_t n) {
-	const size_t nrec = n == 2 ? 1 : n - 2;
-	return n * n * sizeof(double) + n * sizeof(double) + 3 * n * sizeof(int32_t) + tiles_of((uint32_t)n) * sizeof(Cand) +
-		   nrec * sizeof(andi_hip_nj_join) + sizeof(unsigned long long);
-}
-
-// the buffers of a group of g replicates of n x n, one replicate after the other in each
+// the buffers of a group of g replicates of n x n, one replicate after the other in each (rep_groups.h: alloc_group)
 struct NjBuffers {
 	double *D = nullptr, *R = nullptr;
 	int32_t *lists = nullptr; // per replicate: two act lists, the ids
 	Cand *part = nullptr;
 	andi_hip_nj_join *rec = nullptr;
 	unsigned long long *bad = nullptr;
+
+	// device bytes of one replicate: D, R, the lists, the tile results, the records, the bad word
+	static size_t replicate_bytes(size_t n) {
+		return n * n * sizeof(double) + n * sizeof(double) + 3 * n * sizeof(int32_t) + tiles_of((uint32_t)n) * sizeof(Cand) +
+			   records_of(n) * sizeof(andi_hip_nj_join) + sizeof(unsigned long long);
+	}
+	hipError_t alloc(DevScope &dev, size_t n, size_t g) {
+		dev.alloc(&D, g * n * n), dev.alloc(&R, g * n), dev.alloc(&lists, g * 3 * n);
+		dev.alloc(&part, g * tiles_of((uint32_t)n)), dev.alloc(&rec, g * records_of(n)), dev.alloc(&bad, g);
+		return dev.err;
+	}
 };
 
-// (the caller has waited for the stream)
-void nj_free(NjBuffers &b) {
-	for (void *p : {(void *)b.D, (void *)b.R, (void *)b.lists, (void *)b.part, (void *)b.rec, (void *)b.bad})
-		if (p) (void)andi_arena::dev_free(p, false);
-	b = NjBuffers{};
-}
-
-hipError_t nj_alloc(NjBuffers &b, size_t n, size_t g) {
-	const size_t nrec = n == 2 ? 1 : n - 2;
-	hipError_t e = dmalloc(&b.D, g * n * n);
-	if (e == hipSuccess) e = dmalloc(&b.R, g * n);
-	if (e == hipSuccess) e = dmalloc(&b.lists, g * 3 * n);
-	if (e == hipSuccess) e = dmalloc(&b.part, g * tiles_of((uint32_t)n));
-	if (e == hipSuccess) e = dmalloc(&b.rec, g * nrec);
-	if (e == hipSuccess) e = dmalloc(&b.bad, g);
-	return e;
-}
-
-// Neighbor-joining of g matrices (host, one after the other; D == nullptr: their upper triangles are in b.D already, left
-// there by kernels on the context's stream) in buffers for at least g; D_out, if given, receives the g matrices as
-// k_nj_init leaves them (mirrored, diagonal +0.0), copied before the first join step: bad[k] receives replicate k's
-// first non-finite entry (i * n + j) or NOT_BAD, joins the records of all g when at least one matrix is usable -- and
-// nothing when none is.  A bad replicate among good ones is NOT kept out of the step kernels: better() and none() make
-// every pick a real pair of active slots whatever the values in D are (every index comes from the lists and the ids,
-// never from a distance), so its steps run like any other's on NaN and inf, fault nothing, and leave records the caller
-// throws away (andi_hip_nj_batch zeroes them).  Synchronous; the one host synchronisation before the steps is the read of
-// the bad words, none between steps.
+// Neighbor-joining of g matrices in buffers for at least g, between group_begin and group_end (rep_groups.h: what D,
+// D_out and bad are; the init kernel is k_nj_init, an unusable entry a non-finite one): joins receives the records of all
+// g when at least one matrix is usable -- and nothing when none is.  Synchronous; no host synchronisation between steps.
 hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint32_t N, uint32_t g, andi_hip_nj_join *joins,
 					unsigned long long *bad, double *D_out = nullptr) {
-	const size_t n = N, nrec = n == 2 ? 1 : n - 2;
+	const size_t n = N, nrec = records_of(n);
 	const uint32_t parts = (uint32_t)tiles_of(N);
 	hipStream_t st = ctx->stream;
-	hipError_t e = D ? hipMemcpyAsync(b.D, D, g * n * n * sizeof(double), hipMemcpyHostToDevice, st) : hipSuccess;
-	if (e == hipSuccess) e = hipMemsetAsync(b.bad, 0xff, g * sizeof *bad, st);
-	if (e == hipSuccess) {
-		k_nj_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.bad);
-		e = hipGetLastError();
-	}
-	if (e == hipSuccess && D_out) e = hipMemcpyAsync(D_out, b.D, g * n * n * sizeof(double), hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipMemcpyAsync(bad, b.bad, g * sizeof *bad, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	if (e != hipSuccess) return e;
-	bool any_good = false;
-	for (uint32_t k = 0; k < g; ++k) any_good |= bad[k] == NOT_BAD;
-	if (!any_good) return hipSuccess;
+	bool any_good;
+	hipError_t e = group_begin(
+		st, b.D, D, n, g, b.bad, bad, D_out, [&] { k_nj_init<<<dim3(N, g), 256, 0, st>>>(b.D, N, b.lists, b.bad); }, any_good);
+	if (e != hipSuccess || !any_good) return e;
 	uint32_t cur = 0; // where in a replicate's lists the current act list starts: 0 or n
 	for (uint32_t s = 0; e == hipSuccess && n >= 4 && s < N - 3; ++s) {
 		const uint32_t r = N - s;
@@ -296,24 +266,7 @@ hipError_t nj_group(andi_hip_ctx *ctx, const NjBuffers &b, const double *D, uint
 		k_nj_final<<<dim3(1, g), 64, 0, st>>>(b.D, N, b.lists, cur, n == 2 ? 2 : 3, b.rec, (uint32_t)nrec);
 		e = hipGetLastError();
 	}
-	if (e == hipSuccess) e = hipMemcpyAsync(joins, b.rec, g * nrec * sizeof *joins, hipMemcpyDeviceToHost, st);
-	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	return e;
-}
-
-// The buffers of andi_hip_nj_batch's group: as many replicates as GROUP_BYTES hold (nj_group_size, api_internal.h), as
-// there are; G receives the group's size.
-hipError_t nj_alloc_group(NjBuffers &b, size_t n, size_t count, size_t &G) {
-	G = nj_group_size(GROUP_BYTES, replicate_bytes(n));
-	if (G > count) G = count;
-	hipError_t e = nj_alloc(b, n, G);
-	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix andi_hip_nj needs too
-		nj_free(b);
-		(void)hipGetLastError();
-		G = (G + 1) / 2;
-		e = nj_alloc(b, n, G);
-	}
-	return e;
+	return e == hipSuccess ? group_end(st, joins, b.rec, g * nrec) : e;
 }
 
 } // namespace
@@ -324,17 +277,16 @@ int andi_hip_nj(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_nj_join *
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	DevScope dev(ctx->stream);
 	NjBuffers b;
 	unsigned long long bad = NOT_BAD;
-	hipError_t e = nj_alloc(b, n, 1);
+	hipError_t e = b.alloc(dev, n, 1);
 	if (e == hipSuccess) e = nj_group(ctx, b, D, (uint32_t)n, 1, joins, &bad);
-	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
-	nj_free(b);
 	if (e != hipSuccess) return fail(ctx, "andi_hip_nj", e);
 	if (bad != NOT_BAD) {
-		const size_t i = (size_t)(bad / n), j = (size_t)(bad % n);
+		const Entry at = bad_entry(bad, n);
 		char msg[160];
-		snprintf(msg, sizeof msg, "andi_hip_nj: D[%zu][%zu] is not finite (%g)", i, j, D[i * n + j]);
+		snprintf(msg, sizeof msg, "andi_hip_nj: D[%zu][%zu] is not finite (%g)", at.i, at.j, D[at.i * n + at.j]);
 		ctx->err = msg;
 		return 1;
 	}
@@ -347,22 +299,14 @@ int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const size_t nrec = n == 2 ? 1 : n - 2;
+	DevScope dev(ctx->stream);
 	NjBuffers b;
 	size_t G = 0;
-	hipError_t e = nj_alloc_group(b, n, count, G);
-	std::vector<unsigned long long> hb(G);
-	for (size_t first = 0; e == hipSuccess && first < count; first += G) {
-		const size_t g = count - first < G ? count - first : G;
-		andi_hip_nj_join *J = joins + first * nrec;
-		e = nj_group(ctx, b, D + first * n * n, (uint32_t)n, (uint32_t)g, J, hb.data());
-		for (size_t k = 0; e == hipSuccess && k < g; ++k) {
-			bad[first + k] = hb[k] == NOT_BAD ? -1 : (int64_t)hb[k];
-			if (hb[k] != NOT_BAD) memset(J + k * nrec, 0, nrec * sizeof *J);
-		}
-	}
-	(void)hipStreamSynchronize(ctx->stream); // (an error exit: nothing in flight uses the buffers below)
-	nj_free(b);
+	hipError_t e = alloc_group(dev, b, n, count, G);
+	if (e == hipSuccess)
+		e = for_groups(count, G, records_of(n), joins, bad, [&](size_t first, size_t g, andi_hip_nj_join *J, unsigned long long *hb) {
+			return nj_group(ctx, b, D + first * n * n, (uint32_t)n, (uint32_t)g, J, hb);
+		});
 	if (e != hipSuccess) return fail(ctx, "andi_hip_nj_batch", e);
 	return 0;
 }
@@ -380,34 +324,27 @@ int andi_hip_bootstrap_nj(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, 
 		return 1;
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const size_t nrec = n == 2 ? 1 : n - 2, pairs = n * (n - 1) / 2;
+	const size_t pairs = n * (n - 1) / 2;
 	hipStream_t st = ctx->stream;
+	DevScope sums(st), dev(st); // S for the whole call; M's copy, then the groups' buffers (alloc_group gives back all of its scope)
 	andi_hip_model *dM = nullptr;
 	uint32_t *S = nullptr;
-	hipError_t e = dmalloc(&S, pairs * 16);
-	if (e == hipSuccess) e = dmalloc(&dM, n * n);
+	sums.alloc(&S, pairs * 16);
+	if (sums.err == hipSuccess) dev.alloc(&dM, n * n);
+	hipError_t e = sums.err != hipSuccess ? sums.err : dev.err;
 	if (e == hipSuccess) e = hipMemcpyAsync(dM, M, n * n * sizeof *M, hipMemcpyHostToDevice, st);
 	if (e == hipSuccess) e = andi_launch_pair_sums(dM, S, (uint32_t)n, st);
 	if (e == hipSuccess) e = hipStreamSynchronize(st);
-	else (void)hipStreamSynchronize(st);
-	(void)andi_arena::dev_free(dM, false);
+	dev.release(); // (M's copy is 650 MB at n = 3085)
 	NjBuffers b;
 	size_t G = 0;
-	if (e == hipSuccess) e = nj_alloc_group(b, n, count, G);
-	std::vector<unsigned long long> hb(G);
-	for (size_t done = 0; e == hipSuccess && done < count; done += G) {
-		const size_t g = count - done < G ? count - done : G;
-		andi_hip_nj_join *J = joins + done * nrec;
-		e = andi_launch_bootstrap_dist(S, b.D, (uint32_t)n, model, (uint32_t)(first + done), (uint32_t)g, seed, st);
-		if (e == hipSuccess) e = nj_group(ctx, b, nullptr, (uint32_t)n, (uint32_t)g, J, hb.data(), D ? D + done * n * n : nullptr);
-		for (size_t k = 0; e == hipSuccess && k < g; ++k) {
-			bad[done + k] = hb[k] == NOT_BAD ? -1 : (int64_t)hb[k];
-			if (hb[k] != NOT_BAD) memset(J + k * nrec, 0, nrec * sizeof *J);
-		}
-	}
-	(void)hipStreamSynchronize(st); // (an error exit: nothing in flight uses the buffers below)
-	nj_free(b);
-	(void)andi_arena::dev_free(S, false);
+	if (e == hipSuccess) e = alloc_group(dev, b, n, count, G);
+	if (e == hipSuccess)
+		e = for_groups(count, G, records_of(n), joins, bad, [&](size_t done, size_t g, andi_hip_nj_join *J, unsigned long long *hb) {
+			hipError_t eg = andi_launch_bootstrap_dist(S, b.D, (uint32_t)n, model, (uint32_t)(first + done), (uint32_t)g, seed, st);
+			if (eg == hipSuccess) eg = nj_group(ctx, b, nullptr, (uint32_t)n, (uint32_t)g, J, hb, D ? D + done * n * n : nullptr);
+			return eg;
+		});
 	if (e != hipSuccess) return fail(ctx, "andi_hip_bootstrap_nj", e);
 	return 0;
 }

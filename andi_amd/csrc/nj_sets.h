@@ -129,7 +129,7 @@ inline bool sets_prepare(andi_hip_ctx *ctx, const char *fn, const andi_hip_nj_jo
 			ctx->err = msg;
 			return false;
 		}
-	p.G = nj_group_size(SETS_GROUP_BYTES, nsets * (W * sizeof(uint64_t) + set_bytes));
+	p.G = nj_group_size(KNOB_NJ_GROUP, 65535, SETS_GROUP_BYTES, nsets * (W * sizeof(uint64_t) + set_bytes));
 	if (p.G > p.used.size()) p.G = p.used.empty() ? 1 : p.used.size();
 	return true;
 }

@@ -21,8 +21,9 @@
 //              adds in ascending i.  An unusable leaf is skipped by a branch the whole wavefront takes: no 0 * inf
 //              reaches a sum;
 //   k_choose   one wavefront per query: the least (err, edge) over the edges, a NaN last.
-// The queries are taken in groups (PLACE_GROUP_BYTES of device memory; test hook ANDI_PLACE_GROUP: a size of the test's
-// choosing); a group's launches follow the one before on the context's stream, and one synchronisation ends the call.
+// The queries are taken in groups, sized by the rule of the replicates' groups (nj_group_size, api_internal.h) with this
+// call's budget, PLACE_GROUP_BYTES of device memory, and its own test hook, ANDI_PLACE_GROUP; a group's launches follow
+// the one before on the context's stream, and one synchronisation ends the call.
 #pragma clang fp contract(off)
 #include <hip/hip_runtime.h>
 
@@ -256,17 +257,6 @@ size_t query_bytes(size_t n) {
 	return 2 * n * sizeof(double) + 3 * (2 * n - 3) * sizeof(double) + sizeof(QueryInfo) + sizeof(andi_hip_placement);
 }
 
-// The queries of one group: as many as PLACE_GROUP_BYTES hold, at least one, at most what the grid's second dimension
-// takes.  Test hook ANDI_PLACE_GROUP: a size of the test's choosing, within the same bounds.
-size_t place_group_size(size_t n, size_t nq) {
-	constexpr size_t MAX_GROUP = (size_t)65535 * QT;
-	size_t G = PLACE_GROUP_BYTES / query_bytes(n);
-	if (const char *v = andi_knob(KNOB_PLACE_GROUP))
-		if (atoll(v) >= 1) G = (size_t)atoll(v);
-	G = G < 1 ? 1 : G > MAX_GROUP ? MAX_GROUP : G;
-	return G > nq ? nq : G;
-}
-
 } // namespace
 
 int andi_hip_place(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, size_t nq, int method,
@@ -304,7 +294,9 @@ int andi_hip_place(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, co
 	}
 
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const size_t G = place_group_size(n, nq);
+	// the queries of a group: at most what k_place's grid takes as its second dimension, QT queries a block
+	size_t G = nj_group_size(KNOB_PLACE_GROUP, (size_t)65535 * QT, PLACE_GROUP_BYTES, query_bytes(n));
+	if (G > nq) G = nq;
 	const uint32_t N = (uint32_t)n, Ed = (uint32_t)E, Wd = (uint32_t)W;
 	hipStream_t st = ctx->stream;
 	DevScope dev(st);
