@@ -798,6 +798,22 @@ extern "C" int andi_hip_test_download_text(andi_hip_ctx *ctx, const andi_hip_esa
 	if (P) HIP_TRY(ctx, hipMemcpy(P, e->Praw, p_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return 0;
 }
+// The list of the wavefront kernel's segments of the context's last routed scan call (scan.h: coop_items), as it lies in the call's scratch:
+// up to items_cap entries, and the class and cost-class bytes of up to pairs_cap pairs as they stand after the call.  info = { entries of the
+// list, pairs of the call, segments per subject of the wavefront kernel's layout, 1 if the call had a list }.  Any pointer may be NULL.
+extern "C" int andi_hip_test_coop_items(andi_hip_ctx *ctx, uint32_t *items, size_t items_cap, uint8_t *pair_class, uint8_t *pair_cost, size_t pairs_cap,
+										uint32_t *info) {
+	if (!ctx) return 1;
+	const auto &l = ctx->last_items;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (info) info[0] = l.n_items, info[1] = l.pairs, info[2] = l.total_segs, info[3] = l.items ? 1u : 0u;
+	const size_t ni = std::min<size_t>(items_cap, l.n_items), np = std::min<size_t>(pairs_cap, l.pairs);
+	if (items && l.items && ni) HIP_TRY(ctx, hipMemcpy(items, l.items, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (pair_class && l.pair_class && np) HIP_TRY(ctx, hipMemcpy(pair_class, l.pair_class, np, hipMemcpyDeviceToHost));
+	if (pair_cost && l.pair_cost && np) HIP_TRY(ctx, hipMemcpy(pair_cost, l.pair_cost, np, hipMemcpyDeviceToHost));
+	return 0;
+}
 // The index build's pack kernel alone on a staged subject (no table: the text may be any bytes); forms: bit 0 with N1, bit 1 with P
 extern "C" int andi_hip_test_pack_text(andi_hip_ctx *ctx, andi_hip_esa *e, int forms) {
 	if (!ctx || !e) return 1;

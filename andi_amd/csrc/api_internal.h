@@ -66,6 +66,14 @@ struct andi_hip_ctx {
 	bool pool_failed = false;          // its allocation failed once: not tried again by this context
 	void *scratch2 = nullptr;          // the second lane layout (those pairs), grown on demand
 	size_t scratch2_bytes = 0;
+	uint32_t round_waves = 0; // resident wavefronts of k_coop_cold on this device: a round of pass A by wavefronts (scan_call.hip: carve_scratch)
+	// the last routed call's list of the wavefront kernel's segments, in the call's scratch (scan.h: coop_items; null: the call had none), with
+	// the pairs' classes and cost classes -- what the suite's hook andi_hip_test_coop_items reads
+	struct {
+		const uint32_t *items = nullptr;
+		const uint8_t *pair_class = nullptr, *pair_cost = nullptr;
+		uint32_t n_items = 0, pairs = 0, total_segs = 0;
+	} last_items;
 	unsigned long long *d_route = nullptr; // routed scan calls: query nucleotides whose pass A ran by wavefronts / by lanes, pairs handed back (read with the timings)
 	std::vector<EventPair> pending;
 	andi_hip_timings acc{};

@@ -89,11 +89,31 @@ struct ScanArgs {
 	uint32_t *pair_wave0;
 	uint32_t *pair_bsum;  // scratch: sums / offsets of 1024 pairs each
 	uint32_t max_waves;   // upper bound (every pair in class 0): the grid
-	// Routed calls: pass A by wavefronts takes the subjects heaviest first (sub_order[k]: the subject the k-th row of its grid works
-	// on; null: as they come).  A wavefront's segment takes a millisecond and a launch is three or four rounds of them: what the
-	// device does while the last ones finish depends on which they are (the bench set's 29 subjects in order of rising
-	// divergence 4.82 ms, as they come 4.50, heaviest first 4.39).  sub_cost: what k_pair_estimate's samples say a subject's pairs
-	// cost -- nucleotides over mean match length, summed.
+	// Routed calls whose host looks at the layout before pass A (launch_routed): pass A by wavefronts takes its segments from a LIST,
+	// coop_items[k] = subject * total_segs + segment -- exactly the segments of the pairs marked ANDI_ROUTE_COOP (no wavefront for a self
+	// pair or a pair of the lane scan), n_items = restitch_count[ANDI_COOP_SEGS] of them, ALL PAIRS HEAVIEST FIRST: a counting sort of the
+	// pairs by cost class (scan_lane.hip: andi_launch_coop_items), stable -- a pair's segments in their order, pairs of one class in the
+	// order of the slots.  pair_cost: a pair's cost class from k_pair_estimate's samples, ANDI_COST_CLASSES - 1 the heaviest (four classes
+	// per octave of the mean sampled match length: what a segment costs a wavefront falls with that length; where the lane layout has one
+	// segment length the samples are cut at 96 symbols, so pairs closer than about 1 % share the lightest two classes there).  A wavefront's segment takes a
+	// millisecond and a launch is three or four rounds of them: what the device does while the last ones finish depends on which they are.
+	// Pass A of the bench set, 812 pairs of 38 segments (profiles/r09_coop_order.md): lightest first 3.71 ms; whole subjects by falling
+	// summed cost, their segments in query order (the grid, until round 9) 3.31; the same with a subject's pairs heaviest first 3.29; all
+	// pairs heaviest first 3.17; the subjects' order with only the last one, two, three rounds' worth of pairs heaviest first 3.18, 3.15,
+	// 3.18 -- the tail is what the order buys, and the 29 tables under the resident wavefronts at once instead of eight cost nothing
+	// there.  A launch of dozens of rounds has little tail, and its subjects' tables all at once do cost (C4 shape + 5 % by k_pool_cold,
+	// + 1 % by k_coop_cold): a call has a list up to ANDI_ITEMS_ROUNDS rounds of wavefronts, and k_pool_cold does not use it (scan_call.hip).
+	// coop_items == nullptr (those launches; calls whose host does not look; calls that are not routed): the grid (segment, row).
+	uint8_t *pair_cost;
+	uint32_t *coop_items;
+	uint32_t n_items;
+	uint32_t *item_hist;   // scratch of the sort, calls of more than 1024 pairs: [class][block of 1024 pairs] segments, then their offsets into the list
+	uint32_t items_order;  // ANDI_ITEMS_*
+	const uint32_t *layout_count; // the lane layout's restitch_count (ANDI_COOP_SEGS), of the layout the list is built from
+	// Routed calls on the grid (those whose host does not look -- a look costs small calls 40 us of their few hundred --, long launches) take its rows --
+	// the subjects -- heaviest first: sub_order[k] is the subject row k works on (null: as they come), sub_cost what k_pair_estimate's samples
+	// say a subject's pairs cost, nucleotides over mean match length, summed.  (12 x 1 Mbp, such a call: pass A 0.61 ms, 0.635 with the
+	// subjects as they come; the bench set on the grid 3.31 against 3.45.)
 	float *sub_cost;
 	uint32_t *sub_order;
 	// Pairs whose sampled mean match length is at least quad_min_match (per-pair segment lengths only) take pass A with
@@ -151,6 +171,8 @@ hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st);
 // routed calls: the second lane layout (a2: the pairs pass A by wavefronts handed back); who took what, for the timings
 hipError_t andi_launch_pair_leftover(const ScanArgs &a2, hipStream_t st);
 hipError_t andi_launch_route_count(const ScanArgs &a, hipStream_t st);
+// routed calls: the list of the wavefront kernel's segments (b: that kernel's layout; behind andi_launch_pair_layout on the same stream)
+hipError_t andi_launch_coop_items(const ScanArgs &b, hipStream_t st);
 hipError_t andi_launch_lane_cold(const ScanArgs &a, hipStream_t st);
 // pass A with one wavefront per chain (scan_coop.hip)
 int andi_coop_enabled(void); // 0: off (ANDI_COOP=0); < 0: the engine chooses -- tiny calls every pair, others routed per pair (the default); n = 2, 4, 8: every pair, windows of 2048 n symbols
@@ -191,6 +213,11 @@ static_assert(ANDI_RESTITCH_ROUNDS < 8, "restitch_count[]: rounds 0 .. ROUNDS at
 #define ANDI_STRUCT_WAVES 4 /* restitch_count[this] during the layout of a routed call: wavefronts of pairs with unrelated stretches that are not merely far apart (k_pair_estimate) */
 #define ANDI_POOL_SEGS 6 /* restitch_count[this] after k_pair_route: segments of the wavefront kernel's pairs that suit k_pool_cold */
 #define ANDI_COOP_SEGS 7 /* ... of all its pairs */
+#define ANDI_COST_CLASSES 64u /* ScanArgs.pair_cost: classes of a pair's cost */
+#define ANDI_ITEMS_ROUNDS 8u /* a list only for launches of at most this many rounds of the device's resident wavefronts (scan_call.hip: carve_scratch) */
+#define ANDI_ITEMS_GRID 0     /* ScanArgs.items_order: no list -- the grid (segment, subject) */
+#define ANDI_ITEMS_HEAVY 1    /* all pairs heaviest first */
+#define ANDI_ITEMS_LIGHT 2    /* all pairs lightest first (the worst case: tests and measurements only) */
 #define ANDI_LAYOUT_LANES 1   /* ScanArgs.route: the lane scan's pairs */
 #define ANDI_LAYOUT_LANES2 2  /* the pairs pass A by wavefronts handed back */
 #define ANDI_LAYOUT_COOP 3    /* the wavefront kernel's pairs (one segment length) */

@@ -75,6 +75,7 @@ struct ScanPlan {
 	uint32_t max_class = 0;
 	uint64_t max_waves = 0; // per-pair segment lengths: wavefronts if every pair had the shortest segments (the grid)
 	uint32_t seg_factor = 0, quad_min_match = 0, knock = 0, pool_match = 0, route_all_few = 0, route_giveup = 0;
+	uint32_t items_order = ANDI_ITEMS_HEAVY; // the order of the wavefront kernel's segments (scan.h: coop_items)
 	uint32_t longest_q = 0, reduce_threads = 0, coop_reduce_threads = 0; // (the lane layouts', layout b's)
 	int exact_equal = 0;
 	bool force_reference = false, force_adaptive = false;
@@ -145,6 +146,8 @@ ScanPlan plan_call(andi_hip_esa *const *subjects, size_t nsub, const andi_hip_qu
 	P.route_all_few = call_nt < (small_log ? 1ull << small_log : ANDI_ROUTE_SMALL_NT) ? 1u : 0u;
 	// (tests: hand pairs back early, so that the second lane layout runs; small calls route pairs the sampling cannot judge: a lower limit)
 	P.route_giveup = (uint32_t)knob_int(KNOB_COOP_GIVEUP, 1, INT32_MAX, P.route_all_few ? 256 : 1024);
+	// (tests, measurements: ANDI_COOP_ORDER=G the grid -- no list --, R the list lightest first, the worst case; profiles/r09_coop_order.md)
+	if (const char *o = andi_knob(KNOB_COOP_ORDER)) P.items_order = o[0] == 'G' ? ANDI_ITEMS_GRID : o[0] == 'R' ? ANDI_ITEMS_LIGHT : ANDI_ITEMS_HEAVY;
 	for (size_t i = 0; i < q->nq; ++i) P.longest_q = std::max(P.longest_q, (uint32_t)q->len[i]);
 	P.coop_reduce_threads = reduce_threads(P.longest_q, coop_seg);
 	P.exact_equal = (model == ANDI_M_LOGDET || model == ANDI_M_ANI) ? 1 : 0; // src/model.c:247
@@ -184,9 +187,10 @@ void plan_layout(andi_hip_ctx *ctx, ScanPlan &P, const int64_t *h_self, size_t n
 // The scratch of one layout, carved from base + off; returns the end offset (a null base only measures: the size of a
 // scratch and its carving are one walk).  The per-slot arrays of n slots; then, where pairs != 0 (per-pair segment lengths,
 // routing), the pairs' wavefront counts and offsets, with cls their classes (the call's first layout: the others share
-// them); then, where nsub != 0 (the routed call's first layout), the order of the subjects (scan.h).  What is not carved
-// keeps its value.
-size_t carve_layout(ScanArgs &x, char *base, size_t off, size_t n, size_t pairs, bool cls, size_t nsub) {
+// them); then, where nsub != 0 (the routed call's first layout), the order of the subjects and, where items != 0, the list of the
+// wavefront kernel's segments, `items` of them at most, with the pairs' cost classes and the scratch of its sort (scan.h).  What is
+// not carved keeps its value.
+size_t carve_layout(ScanArgs &x, char *base, size_t off, size_t n, size_t pairs, bool cls, size_t nsub, size_t items = 0) {
 	uintptr_t p = (uintptr_t)base + off;
 	auto take = [&p](size_t bytes, size_t align = 1) {
 		p = (p + align - 1) & ~(uintptr_t)(align - 1);
@@ -217,6 +221,11 @@ size_t carve_layout(ScanArgs &x, char *base, size_t off, size_t n, size_t pairs,
 		x.sub_cost = (float *)take(nsub * sizeof(float), 16);
 		x.sub_order = (uint32_t *)take(nsub * sizeof(uint32_t));
 	}
+	if (items) {
+		x.pair_cost = (uint8_t *)take(pairs);
+		x.item_hist = (uint32_t *)take(ANDI_COST_CLASSES * ((pairs + 1023) / 1024) * sizeof(uint32_t), 16);
+		x.coop_items = (uint32_t *)take(items * sizeof(uint32_t));
+	}
 	return (size_t)(p - (uintptr_t)base);
 }
 
@@ -224,8 +233,21 @@ size_t carve_layout(ScanArgs &x, char *base, size_t off, size_t n, size_t pairs,
 // kernel's layout b at *b_off.  Carves a; b is carved from its copy of a (launch_routed).
 int carve_scratch(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size_t slots, size_t slots2, size_t nsub, size_t pairs_all, size_t *b_off) {
 	const size_t pairs = P.adaptive || P.routed ? pairs_all : 0, subs = P.routed ? nsub : 0;
+	// The wavefront kernel's segments as a list (scan.h: coop_items) where the host is going to look at the layout anyway -- the list's length
+	// comes with that look -- and the launch is at most ANDI_ITEMS_ROUNDS rounds of the device's resident wavefronts (slots2 bounds it): what
+	// the order takes is the tail, and a launch of dozens of rounds -- the C4 shape's 24 680 pairs -- has little of it, while the list, sorted
+	// by class, walks all its subjects' tables in every class where the grid finishes one subject after the other (C4 shape by k_pool_cold
+	// 20.6-20.9 -> 21.5-21.8 ms, of 40-contig genomes by k_coop_cold 42.4-42.7 -> 42.9-43.0; profiles/r09_coop_order.md).  Such calls
+	// neither build nor carve a list.
+	if (!ctx->round_waves) {
+		int cus = 0;
+		if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) cus = 256;
+		ctx->round_waves = (uint32_t)cus * 4u * 8u; // (k_coop_cold: eight wavefronts per SIMD)
+	}
+	const bool listed = P.routed && !P.route_all_few && P.items_order != ANDI_ITEMS_GRID && slots2 <= (size_t)ANDI_ITEMS_ROUNDS * ctx->round_waves;
+	const size_t items = listed ? slots2 : 0;
 	ScanArgs m = a;
-	*b_off = (carve_layout(m, nullptr, 0, slots, pairs, true, subs) + 15) & ~(size_t)15;
+	*b_off = (carve_layout(m, nullptr, 0, slots, pairs, true, subs, items) + 15) & ~(size_t)15;
 	const size_t need = (P.routed ? carve_layout(m, nullptr, *b_off, slots2, 0, false, 0) : *b_off) + 256; // (256 bytes of slack behind the last array)
 	if (ctx->scratch_bytes < need) {
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -235,7 +257,7 @@ int carve_scratch(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size_t slot
 		HIP_TRY(ctx, andi_arena::dev_malloc(&ctx->scratch, need));
 		ctx->scratch_bytes = need;
 	}
-	carve_layout(a, (char *)ctx->scratch, 0, slots, pairs, true, subs);
+	carve_layout(a, (char *)ctx->scratch, 0, slots, pairs, true, subs, items);
 	return 0;
 }
 
@@ -311,6 +333,8 @@ ScanArgs scan_args(andi_hip_ctx *ctx, const ScanPlan &P, size_t nsub, const andi
 	a.seg0 = P.seg0, a.max_waves = (uint32_t)P.max_waves, a.max_class = P.max_class;
 	a.pair_waves = a.pair_wave0 = a.pair_bsum = nullptr, a.pair_class = nullptr; // (carve_scratch: where the call has them)
 	a.sub_cost = nullptr, a.sub_order = nullptr;
+	a.pair_cost = nullptr, a.coop_items = nullptr, a.item_hist = nullptr, a.layout_count = nullptr; // (carve_scratch, launch_routed: where the call has a list)
+	a.n_items = 0, a.items_order = ANDI_ITEMS_GRID;
 	a.seg_factor = P.seg_factor;
 	a.M = M_dev;
 	a.fixups = ctx->d_fixups;
@@ -388,11 +412,16 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	b.qseg_start = q->c_qseg_start, b.seg2query = q->c_seg2query, b.total_segs = q->c_total_segs, b.seg = P.coop_seg;
 	b.reduce_threads = P.coop_reduce_threads;
 	carve_layout(b, (char *)ctx->scratch, b_off, slots2, 0, false, 0);
+	const bool look = !a.route_all_few;
+	const bool listed = b.coop_items != nullptr; // (carve_scratch: whether this call has a list)
+	b.items_order = listed ? P.items_order : (uint32_t)ANDI_ITEMS_GRID;
+	b.layout_count = a.restitch_count;
 	hipError_t e;
 	{
 		Timed t(ctx, 2);
 		e = hipMemsetAsync(b.restitch_count, 0, 16 * sizeof(uint32_t), ctx->stream);
 		if (e == hipSuccess) e = andi_launch_pair_layout(a, ctx->stream);
+		if (e == hipSuccess && listed) e = andi_launch_coop_items(b, ctx->stream);
 		t.stop();
 		if (e != hipSuccess) return what = "scan layout", e;
 	}
@@ -403,7 +432,6 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	// set, the C4 shape: 0.4 and 1.5 ms the other way round).  The host looks at the layout (one word).
 	// (Small calls do not look: the wavefront kernel first, the lane layout's passes whether it has pairs or not --
 	// a look costs them 40 us of their few hundred.)
-	const bool look = !a.route_all_few;
 	for (int k = 0; k < 16; ++k) ctx->h_any_left[1 + k] = 0;
 	ctx->h_any_left[1 + ANDI_LANE_WAVES] = 1;
 	e = hipSuccess;
@@ -413,6 +441,11 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	// which wavefront kernel: the pooled one where the pairs that suit it hold at least half of the segments (scan.h)
 	b.pool_use = look && e == hipSuccess && 2 * (uint64_t)ctx->h_any_left[1 + ANDI_POOL_SEGS] >= ctx->h_any_left[1 + ANDI_COOP_SEGS] && ctx->h_any_left[1 + ANDI_COOP_SEGS] != 0;
 	give_pool_scratch(ctx, b);
+	b.n_items = ctx->h_any_left[1 + ANDI_COOP_SEGS]; // (the list's length, where the call has one)
+	// (k_pool_cold, whose calls are the long launches of carve_scratch's rule, keeps the grid whatever the length: its choice comes with the look)
+	if (andi_coop_will_pool(b)) b.coop_items = nullptr;
+	ctx->last_items.items = b.coop_items, ctx->last_items.pair_class = b.pair_class, ctx->last_items.pair_cost = b.pair_cost;
+	ctx->last_items.n_items = b.n_items, ctx->last_items.pairs = (uint32_t)pairs_all, ctx->last_items.total_segs = b.total_segs;
 	if (e == hipSuccess) e = hipEventRecord(ctx->coop_fork, ctx->stream);
 	if (e == hipSuccess) e = hipStreamWaitEvent(ctx->coop_stream, ctx->coop_fork, 0);
 	if (e == hipSuccess && lanes_first) e = andi_launch_scan_cold(a, ctx->stream);
@@ -493,6 +526,7 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 	if (!ctx->side_stream) HIP_TRY(ctx, host_pool::stream_get(&ctx->side_stream, ctx->device, ctx->stream_prio));
 	if (!ctx->coop_stream) HIP_TRY(ctx, host_pool::stream_get(&ctx->coop_stream, ctx->device, 0));
 
+	ctx->last_items = {}; // (what the test hook reads points into this call's scratch: nothing of an earlier call's outlives it)
 	ScanPlan P = plan_call(subjects, nsub, q, model, segment);
 	if (ensure_segmentation(ctx, q, P.segment)) return 1;
 	int any_reference = 0;

@@ -24,7 +24,8 @@
 //      plain loop; tests/test_coop_gpu.py checks this kernel against k_lane_cold slot by slot.
 //
 // Layout: one segment length for the call (slot = subject * total_segs + segment), wavefront w of subject
-// blockIdx.y takes segment w.  LogDet and ANI count every anchor's nucleotides (EXACT: src/model.c:256-278).
+// blockIdx.y takes segment w -- or, in a routed call whose host looked at the layout, wavefront k the k-th entry of the list of the
+// kernel's segments, heaviest pairs first (scan.h: coop_items).  LogDet and ANI count every anchor's nucleotides (EXACT: src/model.c:256-278).
 #include "lane_chain.h"
 #include "knobs.h"
 
@@ -1246,9 +1247,15 @@ __global__ __launch_bounds__(64 * COOP_WAVES, NCH <= 5 ? COOP_OCC : 4) void k_co
 	__shared__ CoopLds<NCH> s_lds[COOP_WAVES];
 	CoopLds<NCH> &L = s_lds[threadIdx.x >> 6];
 	const uint32_t lane = __lane_id();
-	const uint32_t sub = a.sub_order ? uni(a.sub_order[blockIdx.y]) : blockIdx.y; // (routed calls: the heaviest subjects first, scan.h)
+	uint32_t sub, wseg = uni(blockIdx.x * COOP_WAVES + (threadIdx.x >> 6));
+	if (a.coop_items) { // (routed calls whose host looked at the layout: the wavefronts' segments as a list, scan.h)
+		if (wseg >= a.n_items) return;
+		const uint32_t item = uni(a.coop_items[wseg]);
+		sub = item / a.total_segs, wseg = item - sub * a.total_segs;
+		if (sub >= a.nsub) return;
+	} else
+		sub = a.sub_order ? uni(a.sub_order[blockIdx.y]) : blockIdx.y; // (routed calls on the grid: the heaviest subjects first, scan.h)
 	if (a.subjects[sub].mode != ANDI_MODE_PROBE) return;
-	const uint32_t wseg = uni(blockIdx.x * COOP_WAVES + (threadIdx.x >> 6));
 	if (wseg >= a.total_segs) return;
 	const uint32_t qidx = uni(a.seg2query[wseg]);
 	if (a.self[sub] == (int64_t)qidx) return;
@@ -1395,7 +1402,10 @@ int andi_coop_will_pool(const ScanArgs &a) {
 }
 
 hipError_t andi_launch_coop_cold(const ScanArgs &a, hipStream_t st) { // one segment length for the call, RAW/JC/Kimura
-	const dim3 grid((a.total_segs + COOP_WAVES - 1) / COOP_WAVES, a.nsub);
+	const bool listed = a.coop_items && !andi_coop_will_pool(a); // (k_pool_cold keeps the grid)
+	if (listed && a.n_items == 0) return hipSuccess; // (the list is empty: no pair is this kernel's)
+	dim3 grid((a.total_segs + COOP_WAVES - 1) / COOP_WAVES, a.nsub);
+	if (listed) grid = dim3((a.n_items - 1) / COOP_WAVES + 1, 1); // (a few rounds of the device at most: scan_call.hip)
 	const int nch = andi_coop_enabled();
 	// The windows' walks pooled through global memory (k_pool_cold: persistent wavefronts take the segments in order): segments long enough
 	// to fill its windows; in a routed call where the pairs with long sampled matches hold most of the segments (ScanArgs.pool_use)

@@ -36,6 +36,13 @@ constexpr uint32_t EST_WAVES_FEW = 8; // (calls of up to 1024 pairs: a round of 
 // (Calls of more pairs than that, `many`: the device is full with one wavefront per pair; four pairs share a block.  What
 // the pairs add up -- the layout's wavefront counts -- is k_pair_totals' business: 90 000 pairs adding to three words one
 // by one from here took a millisecond, a million 30 ms.)
+// A pair's cost class (scan.h: pair_cost) from its mean sampled match length: four classes per octave, the shortest matches the heaviest
+__device__ __forceinline__ uint32_t cost_class(uint32_t mean) {
+	const uint32_t m = mean < 1u ? 1u : mean, e = 31u - (uint32_t)__builtin_clz(m);
+	const uint32_t lg = 4u * e + (((m << 2) >> e) & 3u); // (means of 2^14 and more: the lightest class)
+	return lg < ANDI_COST_CLASSES ? ANDI_COST_CLASSES - 1u - lg : 0u;
+}
+
 __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a, bool many) {
 	__shared__ uint32_t s_shorts, s_runs;
 	const uint32_t est_waves = many ? 1u : blockDim.x >> 6;
@@ -46,6 +53,7 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 	const bool first = many ? lane == 0 : threadIdx.x == 0; // who writes the pair's results
 	if (a.self[sub] == (int64_t)qidx) {
 		if (first) a.pair_class[pair] = 0, a.pair_waves[pair] = 0;
+		if (first && a.pair_cost) a.pair_cost[pair] = 0;
 		return;
 	}
 	if (!many) { // (the same branch in every wavefront of the block)
@@ -204,6 +212,7 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 										 (coop_cand && islands ? ANDI_ROUTE_LEFT : 0u) | (coop_cand && guess ? ANDI_ROUTE_GUESS : 0u) |
 										 (a.route && (sum >> 6) >= a.pool_match && (sum >> 6) < 4096u && break_dist >= 262144u ? ANDI_ROUTE_POOLCAND : 0u));
 		a.pair_waves[pair] = (nseg + 63) / 64;
+		if (a.pair_cost) a.pair_cost[pair] = (uint8_t)cost_class(sum >> 6);
 		// (scan.h: sub_order; not in calls of thousands of pairs -- a few subjects with thousands of queries each, alike: their costs stay
 		// zero and the order is the subjects' own; 24 680 additions to eight words took 0.07 ms)
 		if (a.sub_cost && !many) atomicAdd(&a.sub_cost[sub], (float)c.qlen / (float)((sum >> 6) < 8u ? 8u : (sum >> 6)));
@@ -343,8 +352,7 @@ __global__ __launch_bounds__(256) void k_pair_route(ScanArgs a) {
 	if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(&a.restitch_count[ANDI_LANE_WAVES], mine); // (the host looks: which kernel goes first)
 	if ((threadIdx.x & 63u) == 0 && coop_segs) atomicAdd(&a.restitch_count[ANDI_COOP_SEGS], coop_segs), atomicAdd(&a.restitch_count[ANDI_POOL_SEGS], pool_segs); // (... and which wavefront kernel)
 }
-
-// routed calls: the subjects by falling cost (scan.h: sub_order); one block
+// routed calls that keep the grid: the subjects by falling cost (scan.h: sub_order); one block
 __global__ __launch_bounds__(1024) void k_sub_order(ScanArgs a) {
 	for (uint32_t s = threadIdx.x; s < a.nsub; s += 1024) {
 		if (a.nsub > 8192u) { // (ranking is quadratic: calls of that many subjects take them as they come)
@@ -358,6 +366,79 @@ __global__ __launch_bounds__(1024) void k_sub_order(ScanArgs a) {
 			rank += (o > c || (o == c && t < s)) ? 1u : 0u;
 		}
 		a.sub_order[rank] = s;
+	}
+}
+
+// ---- routed calls: the wavefront kernel's segments as a list (scan.h: coop_items), a stable counting sort of the PAIRS by cost class -- a
+// pair's segments stay together, in their order; pairs of one class keep the order of the slots.  Blocks of 1024 pairs, a pair per thread:
+// every wavefront places its pairs of one class after the other by a scan over the lanes and leaves the class's segments in
+// s_cnt[class][wavefront]; one scan of the block over that table (class-major) says where a wavefront's share of a class begins inside the
+// block's.  A call of up to 1024 pairs is one block, and that scan is the whole sort (ITEMS_ALL); larger calls write the blocks' sums per class
+// (ITEMS_HIST), scan them over [class][block] with one block (k_items_scan) and place the segments in a second launch (ITEMS_PLACE).  No pair
+// adds to a word another block adds to (k_pair_totals: what that costs).  (a: the wavefront kernel's layout.)
+enum { ITEMS_ALL, ITEMS_HIST, ITEMS_PLACE };
+static_assert(ANDI_COST_CLASSES * 16 == 1024, "k_items: the table [class][wavefront] is one entry per thread of the block");
+
+template <int MODE>
+__global__ __launch_bounds__(1024) void k_items(ScanArgs a, uint32_t nblocks) {
+	__shared__ uint32_t s_cnt[1024], s_part[1024];
+	const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6, pair = blockIdx.x * 1024 + t;
+	// the pair's segments (none: it is not in the list) and its key: the heaviest class first (ANDI_ITEMS_LIGHT: last)
+	uint32_t segs = 0, first = 0, key = 0;
+	if (pair < a.nsub * a.nq && (a.pair_class[pair] & ANDI_ROUTE_COOP)) { // (exactly the pairs k_pair_route counted)
+		const uint32_t sub = pair / a.nq, q = pair % a.nq, w0 = a.qseg_start[q];
+		segs = a.qseg_start[q + 1] - w0, first = sub * a.total_segs + w0;
+		const uint32_t cost = a.pair_cost[pair] < ANDI_COST_CLASSES ? a.pair_cost[pair] : ANDI_COST_CLASSES - 1u;
+		key = a.items_order == ANDI_ITEMS_LIGHT ? cost : ANDI_COST_CLASSES - 1u - cost;
+	}
+	s_cnt[t] = 0;
+	__syncthreads();
+	uint32_t place = 0; // of the pair's first segment: among its wavefront's segments of the key first
+	for (uint64_t todo = __ballot(segs != 0); todo;) { // the lanes of one key at a time
+		const uint32_t k = (uint32_t)__shfl((int)key, (int)__builtin_ctzll(todo));
+		const bool same = segs != 0 && key == k;
+		uint32_t incl = same ? segs : 0u;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const uint32_t o = (uint32_t)__shfl_up((int)incl, d);
+			incl += lane >= (uint32_t)d ? o : 0u;
+		}
+		if (same) place = incl - segs;
+		if (lane == 63) s_cnt[16 * k + wave] = incl;
+		todo &= ~__ballot(same);
+	}
+	__syncthreads();
+	const uint32_t cnt = s_cnt[t], incl = block_scan_1024(cnt, s_part); // (s_part: the inclusive sums)
+	s_cnt[t] = incl - cnt;
+	__syncthreads();
+	if (MODE == ITEMS_HIST) {
+		if (t < ANDI_COST_CLASSES) a.item_hist[(size_t)t * nblocks + blockIdx.x] = s_part[16 * t + 15] - s_cnt[16 * t];
+		return;
+	}
+	place += s_cnt[16 * key + wave];
+	if (MODE == ITEMS_PLACE) place += a.item_hist[(size_t)key * nblocks + blockIdx.x] - s_cnt[16 * key];
+	const uint32_t n_items = a.layout_count[ANDI_COOP_SEGS];
+	if (place >= n_items || segs > n_items - place) segs = 0; // (never: the list holds that many entries)
+	if (segs <= 8)
+		for (uint32_t i = 0; i < segs; ++i) a.coop_items[place + i] = first + i;
+	for (uint64_t big = __ballot(segs > 8); big; big &= big - 1) { // long queries: all lanes write a pair's segments
+		const int l = __builtin_ctzll(big);
+		const uint32_t p = (uint32_t)__shfl((int)place, l), s = (uint32_t)__shfl((int)segs, l), f = (uint32_t)__shfl((int)first, l);
+		for (uint32_t i = lane; i < s; i += 64) a.coop_items[p + i] = f + i;
+	}
+}
+
+__global__ __launch_bounds__(1024) void k_items_scan(ScanArgs a, uint32_t n) { // one block: exclusive, in place
+	__shared__ uint32_t s_part[1024];
+	const uint32_t per = (n + 1023) / 1024;
+	const uint32_t first = threadIdx.x * per < n ? threadIdx.x * per : n, last = first + per < n ? first + per : n;
+	uint32_t sum = 0;
+	for (uint32_t i = first; i < last; ++i) sum += a.item_hist[i];
+	uint32_t run = block_scan_1024(sum, s_part) - sum;
+	for (uint32_t i = first; i < last; ++i) {
+		const uint32_t v = a.item_hist[i];
+		a.item_hist[i] = run;
+		run += v;
 	}
 }
 
@@ -1358,6 +1439,19 @@ hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st) {
 		}
 	}
 	return a.adaptive ? pair_offsets(a, st) : hipSuccess; // (a routed call with one segment length for its lanes: the marks only)
+}
+
+hipError_t andi_launch_coop_items(const ScanArgs &b, hipStream_t st) {
+	const uint32_t P = b.nsub * b.nq, nblocks = (P + 1023) / 1024;
+	if (nblocks == 1) {
+		k_items<ITEMS_ALL><<<1, 1024, 0, st>>>(b, 1);
+	} else {
+		k_items<ITEMS_HIST><<<nblocks, 1024, 0, st>>>(b, nblocks);
+		k_items_scan<<<1, 1024, 0, st>>>(b, ANDI_COST_CLASSES * nblocks);
+		k_items<ITEMS_PLACE><<<nblocks, 1024, 0, st>>>(b, nblocks);
+	}
+	CHECK_LAUNCH();
+	return hipSuccess;
 }
 
 hipError_t andi_launch_pair_leftover(const ScanArgs &a2, hipStream_t st) {

@@ -182,6 +182,7 @@ SYMBOLS = {
 HOOK_SYMBOLS = {
     "andi_hip_test_download_text": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
     "andi_hip_test_pack_text": (C.c_int, [_P, _P, C.c_int]),
+    "andi_hip_test_coop_items": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None
@@ -587,6 +588,16 @@ class Context:
 
     def timings_reset(self):
         load().andi_hip_timings_reset(self._h)
+
+    def coop_items(self):
+        """(a test hook) the last routed scan call's list of the wavefront kernel's segments: (items or None if the call had no
+        list, the pairs' class bytes, their cost classes, segments per subject of that kernel's layout)"""
+        hook = _hook("andi_hip_test_coop_items")
+        info = np.zeros(4, np.uint32)
+        self._check(hook(self._h, None, 0, None, None, 0, info.ctypes.data), "test_coop_items")
+        items, cls, cost = np.zeros(int(info[0]), np.uint32), np.zeros(int(info[1]), np.uint8), np.zeros(int(info[1]), np.uint8)
+        self._check(hook(self._h, items.ctypes.data, len(items), cls.ctypes.data, cost.ctypes.data, len(cls), info.ctypes.data), "test_coop_items")
+        return (items if info[3] else None), cls, cost, int(info[2])
 
     def alloc(self, nbytes):
         p = _P()
