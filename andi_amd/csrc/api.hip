@@ -822,6 +822,17 @@ extern "C" int andi_hip_test_pack_text(andi_hip_ctx *ctx, andi_hip_esa *e, int f
 									   ctx->stream));
 	return 0;
 }
+// The staged 2-bit codes (andi_hip_queries.codes) of query qidx of a staged set or a view of one: `words` words from the query's first block on
+extern "C" int andi_hip_test_query_codes(andi_hip_ctx *ctx, const andi_hip_queries *q, size_t qidx, uint32_t *out, size_t words) {
+	if (!ctx || !q || !out || qidx >= q->nq || !q->codes || words > 2 * (((size_t)q->len[qidx] + 1 + 255) / 256 * 8)) {
+		if (ctx) ctx->err = "andi_hip_test_query_codes: bad arguments, or more than the query's blocks hold";
+		return 1;
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (words) HIP_TRY(ctx, hipMemcpy(out, q->codes + 2 * (q->off[qidx] / 32), words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
 #endif
 
 int andi_hip_esa_single_form(const andi_hip_esa *e) { return e && e->index_built ? e->deep_ext : 0; }
@@ -883,6 +894,7 @@ int andi_hip_queries_stage(andi_hip_ctx *ctx, const andi_hip_seq *seqs, size_t n
 	chk(dmalloc(&q->pool, pool_bytes));
 	chk(dmalloc(&q->nib, pool_bytes / 2 + 64));
 	chk(dmalloc(&q->planes, 3 * (pool_bytes / 32) + 16));
+	chk(dmalloc(&q->codes, 2 * (pool_bytes / 32) + 16));
 	if (!(q->h_foreign = (int32_t *)host_pool::word_get())) chk(hipErrorOutOfMemory);
 	int32_t *d_foreign = nullptr;
 	chk(dmalloc(&d_foreign, 1));
@@ -946,7 +958,7 @@ int andi_hip_queries_stage(andi_hip_ctx *ctx, const andi_hip_seq *seqs, size_t n
 	if (err == hipSuccess) err = hipMemsetAsync(d_foreign, 0, sizeof(int32_t), ctx->stream);
 	if (err == hipSuccess)
 		err = andi_launch_pack_symbols(q->pool, pool_bytes, q->nib, nullptr, d_foreign, ctx->stream);
-	if (err == hipSuccess) err = andi_launch_pack_planes(q->nib, pool_bytes, q->planes, ctx->stream);
+	if (err == hipSuccess) err = andi_launch_pack_planes(q->nib, pool_bytes, q->planes, q->codes, ctx->stream);
 	if (err == hipSuccess) err = queries_count_separators(ctx, q);
 	if (err == hipSuccess)
 		err = hipMemcpyAsync(q->h_foreign, d_foreign, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream);
@@ -968,7 +980,7 @@ void andi_hip_queries_free(andi_hip_ctx *ctx, andi_hip_queries *q) {
 	void *own[] = {q->d_qseg_start, q->d_seg2query, q->c_qseg_start, q->c_seg2query}; // (every set's, a view's too)
 	for (void *b : own) (void)andi_arena::dev_free(b, false);
 	if (q->owns_pool) {
-		void *bufs[] = {q->pool, q->nib, q->planes, q->d_off, q->d_len, q->d_sep};
+		void *bufs[] = {q->pool, q->nib, q->planes, q->codes, q->d_off, q->d_len, q->d_sep};
 		for (void *b : bufs) (void)andi_arena::dev_free(b, false);
 		host_pool::word_put(q->h_foreign);
 	}
@@ -985,7 +997,7 @@ int andi_hip_queries_view(andi_hip_ctx *ctx, const andi_hip_queries *q, size_t f
 	}
 	auto *v = new andi_hip_queries;
 	v->owns_pool = false;
-	v->pool = q->pool, v->nib = q->nib, v->planes = q->planes, v->h_foreign = q->h_foreign;
+	v->pool = q->pool, v->nib = q->nib, v->planes = q->planes, v->codes = q->codes, v->h_foreign = q->h_foreign;
 	v->d_off = q->d_off + first, v->d_len = q->d_len + first, v->d_sep = q->d_sep ? q->d_sep + first : nullptr;
 	v->off.assign(q->off.begin() + first, q->off.begin() + first + count);
 	v->len.assign(q->len.begin() + first, q->len.begin() + first + count);
@@ -1110,13 +1122,14 @@ int queries_stage_packed(andi_hip_ctx *ctx, const PackedQueries &P, andi_hip_que
 	chk(dmalloc(&q->pool, P.pool_bytes));
 	chk(dmalloc(&q->nib, P.pool_bytes / 2 + 64));
 	chk(dmalloc(&q->planes, 3 * (P.pool_bytes / 32) + 16));
+	chk(dmalloc(&q->codes, 2 * (P.pool_bytes / 32) + 16));
 	if (!(q->h_foreign = (int32_t *)host_pool::word_get())) chk(hipErrorOutOfMemory);
 	chk(dmalloc(&q->d_off, n));
 	chk(dmalloc(&q->d_len, n));
 	if (err == hipSuccess) *q->h_foreign = P.foreign;
 	if (err == hipSuccess) err = hipMemcpyAsync(q->nib, P.nib, P.pool_bytes / 2, hipMemcpyHostToDevice, ctx->stream);
 	if (err == hipSuccess) err = andi_launch_unpack_symbols(q->nib, P.pool_bytes, q->pool, ctx->stream);
-	if (err == hipSuccess) err = andi_launch_pack_planes(q->nib, P.pool_bytes, q->planes, ctx->stream);
+	if (err == hipSuccess) err = andi_launch_pack_planes(q->nib, P.pool_bytes, q->planes, q->codes, ctx->stream);
 	if (err == hipSuccess) err = hipMemcpyAsync(q->d_off, q->off.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
 	if (err == hipSuccess) err = hipMemcpyAsync(q->d_len, q->len.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
 	if (err == hipSuccess) err = queries_count_separators(ctx, q);

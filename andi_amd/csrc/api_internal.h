@@ -107,12 +107,13 @@ struct andi_hip_esa {
 };
 
 struct andi_hip_queries {
-	// a view (andi_hip_queries_view) shares its parent's pool, nib, planes and h_foreign, and its d_off, d_len and d_sep point
+	// a view (andi_hip_queries_view) shares its parent's pool, nib, planes, codes and h_foreign, and its d_off, d_len and d_sep point
 	// into the parent's arrays; it owns only its segmentation caches
 	bool owns_pool = true;
 	uint8_t *pool = nullptr;
 	uint8_t *nib = nullptr;       // the pool as 4-bit symbols
 	uint32_t *planes = nullptr;   // ... bit-sliced (EsaDev.P)
+	uint32_t *codes = nullptr;    // ... as interleaved 2-bit codes of bits 0 and 1, two words per block of 32 symbols (ScanArgs.qcodes)
 	int32_t *h_foreign = nullptr; // pinned: set if the pool holds bytes outside the alphabet
 	uint64_t *d_off = nullptr;
 	uint32_t *d_len = nullptr;

@@ -38,6 +38,7 @@ struct ScanArgs {
 	const uint8_t *qpool;
 	const uint8_t *qnib;  // the pool as 4-bit symbols: sequence q starts at qnib + qoff[q] / 2
 	const uint32_t *qplanes; // the pool bit-sliced (andi_dev.h: EsaDev.P): sequence q starts at block qoff[q] / 32
+	const uint32_t *qcodes;  // the pool as interleaved 2-bit codes, two words per block of 32 symbols (scan_lane.hip: k_pack_planes): what coop_window keeps in LDS
 	const uint64_t *qoff; // [nq]
 	const uint32_t *qlen; // [nq]
 	const uint32_t *qsep; // [nq] contig separators ('!') of every query, or null (k_sep_counts; the routing keeps pairs whose diagonals break often away from the wavefront kernels)
@@ -165,7 +166,7 @@ hipError_t andi_launch_unpack_symbols(const uint8_t *N0, size_t bytes, uint8_t *
 hipError_t andi_launch_pack_symbols(const uint8_t *src, size_t bytes, uint8_t *N0, uint8_t *N1,
 									int32_t *foreign, hipStream_t st);
 // the bit-sliced form of 4-bit symbols (EsaDev.P): `symbols` of them from N0 (rounded up to blocks of 32) into planes
-hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *planes, hipStream_t st);
+hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *planes, uint32_t *codes, hipStream_t st);
 // adaptive mode: sample every pair's match lengths, choose its segment length (and, in a routed call, its pass A), lay out the slots
 hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st);
 // routed calls: the second lane layout (a2: the pairs pass A by wavefronts handed back); who took what, for the timings

@@ -326,7 +326,7 @@ ScanArgs scan_args(andi_hip_ctx *ctx, const ScanPlan &P, size_t nsub, const andi
 	a.subjects = (const EsaDev *)ctx->desc_dev;
 	a.self = (const int64_t *)((const EsaDev *)ctx->desc_dev + nsub);
 	a.nsub = (uint32_t)nsub;
-	a.qpool = q->pool, a.qnib = q->nib, a.qplanes = q->planes, a.qoff = q->d_off, a.qlen = q->d_len, a.qsep = q->d_sep, a.nq = (uint32_t)q->nq;
+	a.qpool = q->pool, a.qnib = q->nib, a.qplanes = q->planes, a.qcodes = q->codes, a.qoff = q->d_off, a.qlen = q->d_len, a.qsep = q->d_sep, a.nq = (uint32_t)q->nq;
 	a.qseg_start = q->d_qseg_start, a.seg2query = q->d_seg2query;
 	a.total_segs = q->total_segs, a.seg = P.segment;
 	a.adaptive = P.adaptive ? 1 : 0;

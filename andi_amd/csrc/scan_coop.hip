@@ -566,6 +566,14 @@ __device__ __forceinline__ void subst_flush_pairs(const SubstAcc &acc, lds_u32 *
 	if (lane < 12 && v) lds_add(&hist[(sn << 2) | qn], add ? v : 0u - v);
 }
 
+// A wave-uniform value as a value of its own from here on: the register allocator weighs it by the loop that follows, not by the whole kernel
+// (an empty statement; nothing is emitted for it but the copy)
+template <class T>
+__device__ __forceinline__ T own_sgpr(T x) {
+	asm volatile("" : "+s"(x));
+	return x;
+}
+
 // ------------------------------------------------------------------ mode W
 // The chain stands at a canonical state of diagonal dg: st.p = e0 + 1 behind the anchor [lastQ, e0), e0 a mismatch
 // of the diagonal.  Returns true if the chain moved; st is a genuine loop-top state either way.
@@ -612,31 +620,47 @@ __device__ __forceinline__ bool coop_window(const ScanArgs &a, const PairCtx &c,
 		SubstAcc acc;
 #pragma unroll
 		for (int k = 0; k < 12; ++k) acc.n[k] = 0;
-		const uint32_t sh = (uint32_t)((int64_t)(wbase + WNT * lane) + dg) & 31u; // (a lane's subject offset keeps its low five bits from chunk to chunk)
-#pragma unroll 2
+		const uint32_t sh = (uint32_t)((int64_t)(wbase + WNT * lane) + dg) & 31u; // (a lane's subject offset keeps its low five bits from chunk to chunk; from the
+		// kernel's own dg, not the loop's copy below: that cost the kernel 12 more bytes of scratch and doubled its lane moves)
+		// The loop's wave-uniform values as values of its own (own_sgpr): the kernel's are spilled to lanes of a register, and every iteration read
+		// the query's length, its two pointers and the diagonal back from there, nine lane moves per chunk.
+		const uint32_t qlen = own_sgpr(c.qlen);
+		const g_u32p Qp = own_sgpr(c.Qp), Qc = own_sgpr(c.Qc), Sp = own_sgpr(c.E.P);
+		const int64_t dgw = own_sgpr(dg), sn = own_sgpr((int64_t)c.E.n);
+		// (wbase = e0 & ~31: the window's first word alone holds positions before e0, which are none of the window's business)
+		uint32_t keep = lane == 0 ? ~0u << (e0 - wbase) : ~0u;
+		// (not unrolled: by two, every iteration ended with thirteen moves of the twelve counters and `dirty` back to the registers the loop's
+		// head expects; unrolled in full, the kernel's scratch grows from 56 to 128 bytes per lane -- profiles/r10_coop_valu.md)
+#pragma unroll 1
 		for (int ck = 0; ck < NCH; ++ck) {
 			const uint32_t x0 = wbase + 2048 * ck + WNT * lane;
 			uint32_t m = ~0u, mc = 0; // positions at and beyond the query's end: lcp() stops there; mc: the mismatches that are counted
 			uint2 codes = make_uint2(0, 0);
-			if (x0 < c.qlen) {
+			if (x0 < qlen) {
+				// (the codes' load issued with the planes': behind them it would wait a second round trip)
+				const u32x2_t cv = *(const __attribute__((address_space(1))) u32x2_t *)(Qc + 2 * (x0 >> 5));
 				RawPlanes raw;
-				ld_raw_planes(c, x0, (int64_t)x0 + dg, raw);
+				raw.q = *(const __attribute__((address_space(1))) u32x3_t *)(Qp + 3 * (x0 >> 5));
+				raw.a = (u32x4_t)(~0u), raw.n = (u32x2_t)(~0u); // (at and beyond the text's end: NUL, all ones)
+				const int64_t s = (int64_t)x0 + dgw;
+				if (s < sn) {
+					const g_u32p p = Sp + 3 * (int32_t)(s >> 5); // (block >= -1: a block of padding lies in front)
+					raw.a = *(const __attribute__((address_space(1))) u32x4_t *)p;
+					raw.n = *(const __attribute__((address_space(1))) u32x2_t *)(p + 4);
+				}
 				Planes qv, sv;
 				planes_of(raw, sh, qv, sv);
+				codes = make_uint2(cv.x, cv.y);
 				m = (qv.b0 ^ sv.b0) | (qv.b1 ^ sv.b1) | (qv.b2 ^ sv.b2);
 				mc = m & ~(qv.b2 | sv.b2); // both nucleotides (src/model.c:318-320)
-				codes = make_uint2(spread16(qv.b0) | (spread16(qv.b1) << 1), spread16(qv.b0 >> 16) | (spread16(qv.b1 >> 16) << 1));
 				uint32_t inq = ~0u;
-				if (c.qlen - x0 < WNT) inq = ~(~0u << (c.qlen - x0)), m |= ~inq, mc &= inq;
+				if (qlen - x0 < WNT) inq = ~(~0u << (qlen - x0)), m |= ~inq, mc &= inq;
 				dirty |= qv.b2 & inq;
-				if (x0 <= e0 && e0 - x0 < WNT) mc &= ~0u << (e0 - x0);
-				if (x0 + WNT <= e0) mc = 0;
-				subst_count(acc, mc, qv, sv);
+				subst_count(acc, mc & keep, qv, sv);
 			}
-			if (x0 <= e0 && e0 - x0 < WNT) m &= ~0u << (e0 - x0); // (what lies before the anchor is none of the window's business)
-			if (x0 + WNT <= e0) m = 0;
-			L.mbits[64 * ck + lane] = m;
+			L.mbits[64 * ck + lane] = m & keep;
 			*(uint2 *)&L.q2[2 * (64 * ck + lane)] = codes;
+			keep = ~0u;
 		}
 		subst_flush_pairs(acc, hist, true);
 	} else {

@@ -21,6 +21,7 @@ struct PairCtx {
 	g_u8p Q;
 	g_u8p Qn; // packed symbols of the query
 	g_u32p Qp; // ... bit-sliced (block 0 = its symbols 0 ... 31)
+	g_u32p Qc; // ... as 2-bit codes, two words per block (ScanArgs.qcodes)
 	uint32_t qlen;
 	uint32_t thr;
 	uint32_t border; // n / 2, src/process.c:149
@@ -116,6 +117,7 @@ __device__ __forceinline__ PairCtx make_ctx(const ScanArgs &a, uint32_t sub, uin
 	c.Q = (g_u8p)(a.qpool + a.qoff[qidx]);
 	c.Qn = (g_u8p)(a.qnib + a.qoff[qidx] / 2);
 	c.Qp = (g_u32p)(a.qplanes + 3 * (a.qoff[qidx] / 32));
+	c.Qc = (g_u32p)(a.qcodes + 2 * (a.qoff[qidx] / 32));
 	c.qlen = a.qlen[qidx];
 	c.thr = (uint32_t)c.E.thr;
 	c.border = (uint32_t)c.E.n / 2;

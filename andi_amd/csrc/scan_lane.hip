@@ -1253,12 +1253,25 @@ __device__ __forceinline__ void planes_of(const uint4 v, uint32_t *out) {
 	}
 }
 
-__global__ __launch_bounds__(256) void k_pack_planes(const uint4 *__restrict__ N0, int64_t blocks, uint32_t *__restrict__ planes) {
+// ... and, for the queries, bits 0 and 1 of each symbol once more as interleaved 2-bit codes (symbol k of a half block: bits 2k, 2k + 1), two
+// words per block: what a window of pass A by wavefronts keeps of the query in LDS (scan_coop.hip: coop_window).  They are made from the
+// plane words themselves, so separators, padding and a ragged last block read as they do in the planes.
+__global__ __launch_bounds__(256) void k_pack_planes(const uint4 *__restrict__ N0, int64_t blocks, uint32_t *__restrict__ planes, uint32_t *__restrict__ codes) {
 	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= blocks) return;
 	uint32_t o[3];
 	planes_of(N0[j], o);
 	planes[3 * j] = o[0], planes[3 * j + 1] = o[1], planes[3 * j + 2] = o[2];
+	if (codes) {
+		auto spread = [](uint32_t x) { // 16 bits -> the even bits of a word (bit k to bit 2k)
+			x &= 0xffffu;
+			x = (x | (x << 8)) & 0x00ff00ffu;
+			x = (x | (x << 4)) & 0x0f0f0f0fu;
+			x = (x | (x << 2)) & 0x33333333u;
+			return (x | (x << 1)) & 0x55555555u;
+		};
+		*(uint2 *)(codes + 2 * j) = make_uint2(spread(o[0]) | (spread(o[1]) << 1), spread(o[0] >> 16) | (spread(o[1] >> 16) << 1));
+	}
 }
 
 // The text of a subject in one pass (the index build): a thread reads 32 bytes once and writes them in all three forms --
@@ -1356,10 +1369,10 @@ hipError_t andi_launch_unpack_symbols(const uint8_t *N0, size_t bytes, uint8_t *
 	return hipSuccess;
 }
 
-hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *planes, hipStream_t st) {
+hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *planes, uint32_t *codes, hipStream_t st) { // codes: may be null
 	const int64_t blocks = (int64_t)((symbols + 31) / 32);
 	if (blocks == 0) return hipSuccess;
-	k_pack_planes<<<(unsigned)((blocks + 255) / 256), 256, 0, st>>>((const uint4 *)N0, blocks, planes);
+	k_pack_planes<<<(unsigned)((blocks + 255) / 256), 256, 0, st>>>((const uint4 *)N0, blocks, planes, codes);
 	CHECK_LAUNCH();
 	return hipSuccess;
 }

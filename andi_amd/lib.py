@@ -183,6 +183,7 @@ HOOK_SYMBOLS = {
     "andi_hip_test_download_text": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
     "andi_hip_test_pack_text": (C.c_int, [_P, _P, C.c_int]),
     "andi_hip_test_coop_items": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "andi_hip_test_query_codes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
 }
 
 _lib = None
@@ -749,6 +750,13 @@ class Queries:
         """queries [first, first + count) of this set on its device buffers (nothing copied): scan with it like any
         staged set; close it before this one"""
         return QueriesView(self, first, count)
+
+    def codes(self, qidx):
+        """(a test hook) the staged 2-bit codes of query qidx: two uint32 words per block of 32 symbols, over the whole of the
+        query's place in the pool (its symbols, the NUL behind them and the padding up to the next multiple of 256)"""
+        out = np.zeros(2 * ((len(self.seqs[qidx]) + 1 + 255) // 256 * 8), np.uint32)
+        self.ctx._check(_hook("andi_hip_test_query_codes")(self.ctx._h, self._h, int(qidx), out.ctypes.data, len(out)), "test_query_codes")
+        return out
 
     def close(self):
         if self._h and self.ctx._h:
