@@ -46,7 +46,7 @@ struct EsaDev {
 	const int32_t *flags;
 	const uint8_t *N0, *N1; // nibble-packed text, two alignments (scan_lane.hip)
 	const uint16_t *R2;     // per suffix, in suffix-array order: the (up to min(4, 16 - K)) nucleotides behind its first K symbols: count << 8 | 2-bit codes, first in the low bits (the device sorter's by-product; null: not there)
-	const uint32_t *P;      // the text bit-sliced (coop_pool.h): block b = words 3b, 3b+1, 3b+2 = bit 0, 1, 2 of the symbols 32b ... 32b+31; a block of padding in front
+	const uint32_t *P;      // the text bit-sliced (coop_dev.h): block b = words 3b, 3b+1, 3b+2 = bit 0, 1, 2 of the symbols 32b ... 32b+31; a block of padding in front
 	int32_t n;
 	int32_t thr;
 	int32_t deepK;

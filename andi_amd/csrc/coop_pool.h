@@ -1,5 +1,5 @@
 // coop_pool.h -- pass A with one wavefront per chain, the window's walks POOLED through global memory (mode P).
-// Included by scan_coop.hip inside its namespace; it shares that file's mode G and its helpers.
+// On top of coop_dev.h alone (mode G's step, the probes, the walks' verdicts, the segment driver); scan_coop.hip holds the kernel.
 //
 // coop_window (mode W) keeps a window of 8192 positions in LDS -- mismatch bits, the query's 2-bit codes, the heads'
 // records -- and walks the window's heads (42 on average on the bench set) with 64 lanes: 16 lanes at work per trip
@@ -21,11 +21,20 @@
 // The states and counts are those of the sequential loop (src/process.c:141-214), as coop_window's: tests/test_coop_gpu.py
 // runs both against the oracle and against each other.  LogDet / ANI (EXACT) stay with coop_window.
 
+#pragma once
+#include "coop_dev.h"
+
+namespace {
+
 #ifndef POOL_MW_POS
 #define POOL_MW_POS 131072
 #endif
 constexpr uint32_t POOL_MW = POOL_MW_POS;       // positions of a window at most (a multiple of 2048)
 constexpr uint32_t POOL_CHUNK_HEADS = 128;      // heads of one round of 2048 positions (more: as above)
+#ifndef POOL_OCC
+#define POOL_OCC 7 /* wavefronts per SIMD: 72 registers, 19 spilled -- round 5: bench set 5.66 / 5.09 / 4.92 ms at 4 / 5 / 6; round 6, first session: 7 and 8 a fifth and a third
+                      slower than 6 (45 / 108 spilled); with sweep W's loop split (19 / 34 spilled): C4 shape 19.8 / 19.8 / 22.9 ms at 6 / 7 / 8, C3-like 1.63 / 1.56 / 1.82 */
+#endif
 
 struct __attribute__((aligned(16))) PoolRec { // what a head's walk reads
 	uint32_t q2[4];   // the query's symbols at positions pos + 1 ... pos + 64, bit-sliced: [0], [1] = bit 0 of the 64 symbols, [2], [3] = bit 1
@@ -131,129 +140,6 @@ __device__ __forceinline__ uint32_t pool_prev_bit_lane(const PoolScratch *G, uin
 	if (((o - 1) & 31u) != 31u) v &= (2u << ((o - 1) & 31u)) - 1u;
 	while (v == 0 && w > 0) v = pool_ld_bits(&G->bits[--w]);
 	return v ? wbase + 32 * (uint32_t)w + 31u - (uint32_t)__builtin_clz(v) : NOPOS;
-}
-
-// substitutions of Q[q..q+len) against S[s..s+len) taken back from the counts (all lanes, 32 positions each; what sweep S counted of
-// a stretch that is counted nowhere)
-__device__ __forceinline__ void pool_uncount_coop(const PairCtx &c, lds_u32 *hist, uint32_t q, uint32_t s, uint32_t len) {
-	const uint32_t lane = __lane_id(), qe = q & ~1u, end = q + len;
-	const int64_t dg = (int64_t)s - (int64_t)q;
-	for (uint32_t base = qe; base < end; base += 64 * WNT) {
-		const uint32_t x0 = base + WNT * lane;
-		if (x0 >= end) continue;
-		const uint4 qv = ld_query(c, x0), sv = ld_subject_guarded(c, (int64_t)x0 + dg);
-		const uint32_t lo = q > x0 ? q - x0 : 0u, hi = end - x0 < WNT ? end - x0 : WNT;
-		for (uint32_t j = lo >> 3; 8 * j < hi; ++j) {
-			const uint32_t a = lo > 8 * j ? lo - 8 * j : 0u, b = hi - 8 * j < 8 ? hi - 8 * j : 8u;
-			const uint32_t qw = pick(qv, j), sw = pick(sv, j), dw = neq8(qw, sw) >> 3;
-			for (uint32_t ne = symbol_range(a, b) & ~(qw >> 2) & ~(sw >> 2) & dw; ne; ne &= ne - 1) {
-				const uint32_t k = (uint32_t)__builtin_ctz(ne);
-				lds_add(&hist[(((sw >> k) & 3u) << 2) | ((qw >> k) & 3u)], 0u - 1u);
-			}
-		}
-	}
-}
-
-// the equal nucleotides of Q[q..q+len) against S[s..s+len) into the diagonal cells (all lanes, 32 positions each; a stretch longer
-// than its head's record)
-__device__ __forceinline__ void pool_count_equal_coop(const PairCtx &c, uint32_t q, uint32_t s, uint32_t len, uint32_t &n0, uint32_t &n1, uint32_t &n2, uint32_t &n3) {
-	const uint32_t lane = __lane_id(), qe = q & ~1u, end = q + len;
-	const int64_t dg = (int64_t)s - (int64_t)q;
-	for (uint32_t base = qe; base < end; base += 64 * WNT) {
-		const uint32_t x0 = base + WNT * lane;
-		if (x0 >= end) continue;
-		const uint4 qv = ld_query(c, x0), sv = ld_subject_guarded(c, (int64_t)x0 + dg);
-		const uint32_t lo = q > x0 ? q - x0 : 0u, hi = end - x0 < WNT ? end - x0 : WNT;
-#pragma unroll
-		for (uint32_t j = 0; j < 4; ++j) {
-			const uint32_t a = lo > 8 * j ? (lo - 8 * j < 8 ? lo - 8 * j : 8u) : 0u, b = hi > 8 * j ? (hi - 8 * j < 8 ? hi - 8 * j : 8u) : 0u;
-			if (a >= b) continue;
-			const uint32_t qw = pick(qv, j), sw = pick(sv, j), dw = neq8(qw, sw) >> 3;
-			const uint32_t eq = symbol_range(a, b) & ~(qw >> 2) & ~(sw >> 2) & ~dw, b0 = qw, b1 = qw >> 1;
-			n0 += (uint32_t)__builtin_popcount(eq & ~(b0 | b1)), n1 += (uint32_t)__builtin_popcount(eq & b0 & ~b1);
-			n2 += (uint32_t)__builtin_popcount(eq & b1 & ~b0), n3 += (uint32_t)__builtin_popcount(eq & b0 & b1);
-		}
-	}
-}
-
-// The texts bit-sliced (andi_dev.h: EsaDev.P): 32 symbols of the query from x0 (a multiple of 32) / of the subject from any offset s
-// (>= -32; at and beyond the text's end: NUL, all ones) as bit 0, 1, 2 of the symbols
-struct Planes {
-	uint32_t b0, b1, b2;
-};
-__device__ __forceinline__ Planes ld_query_planes(const PairCtx &c, uint32_t x0) {
-	const g_u32p p = c.Qp + 3 * (x0 >> 5);
-	Planes r;
-	r.b0 = p[0], r.b1 = p[1], r.b2 = p[2];
-	return r;
-}
-__device__ __forceinline__ Planes ld_subject_planes(const PairCtx &c, int64_t s) {
-	Planes r;
-	r.b0 = r.b1 = r.b2 = ~0u;
-	if (s >= (int64_t)c.E.n) return r;
-	const int32_t blk = (int32_t)(s >> 5);
-	const uint32_t sh = (uint32_t)s & 31u;
-	const g_u32p p = c.E.P + 3 * blk; // (blk >= -1: a block of padding lies in front)
-	const uint32_t a0 = p[0], a1 = p[1], a2 = p[2], n0 = p[3], n1 = p[4], n2 = p[5];
-	r.b0 = __builtin_amdgcn_alignbit(n0, a0, sh), r.b1 = __builtin_amdgcn_alignbit(n1, a1, sh), r.b2 = __builtin_amdgcn_alignbit(n2, a2, sh);
-	return r;
-}
-// The same two fetches as the words come from memory -- no use of a loaded value, so that the loads of round t + 1 stay in flight
-// while round t is worked on (ld_subject_planes shifts its words at once: the wait for them then stands right behind the loads,
-// and sweep S paid the stream's whole latency every round; round 6) -- and what turns them into planes.
-// (aligned(4): the words lie at 4-byte multiples only -- three per block of 32 symbols)
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2), aligned(4)));
-typedef uint32_t u32x3_t __attribute__((ext_vector_type(3), aligned(4)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4), aligned(4)));
-struct RawPlanes { // (whole registers tuples as the loads deliver them: taken apart only where they are used -- a struct of nine words was
-	u32x3_t q;     // copied word by word at the loop's head, with the wait for the loads in front of the copies)
-	u32x4_t a;     // subject block: planes 0, 1, 2 and plane 0 of the next block
-	u32x2_t n;     // planes 1, 2 of the next block
-};
-__device__ __forceinline__ void ld_raw_planes(const PairCtx &c, uint32_t x0, int64_t s, RawPlanes &r) {
-	r.q = *(const __attribute__((address_space(1))) u32x3_t *)(c.Qp + 3 * (x0 >> 5));
-	r.a = (u32x4_t)(~0u), r.n = (u32x2_t)(~0u); // (at and beyond the text's end: NUL, all ones)
-	if (s < (int64_t)c.E.n) {
-		const g_u32p p = c.E.P + 3 * (int32_t)(s >> 5); // (block >= -1: a block of padding lies in front)
-		r.a = *(const __attribute__((address_space(1))) u32x4_t *)p;
-		r.n = *(const __attribute__((address_space(1))) u32x2_t *)(p + 4);
-	}
-}
-__device__ __forceinline__ void planes_of(const RawPlanes &r, uint32_t sh, Planes &q, Planes &s) {
-	q.b0 = r.q.x, q.b1 = r.q.y, q.b2 = r.q.z;
-	s.b0 = __builtin_amdgcn_alignbit(r.a.w, r.a.x, sh), s.b1 = __builtin_amdgcn_alignbit(r.n.x, r.a.y, sh), s.b2 = __builtin_amdgcn_alignbit(r.n.y, r.a.z, sh);
-}
-// the substitutions among the positions `mm` (query symbol != subject symbol, both nucleotides) by kind, into twelve counters:
-// kind k = 3 * (query nucleotide) + (rank of the subject's among the three others) -- no loop over the mismatches, no LDS
-struct SubstAcc {
-	uint32_t n[12];
-};
-__device__ __forceinline__ void subst_count(SubstAcc &acc, uint32_t mm, const Planes &q, const Planes &s) {
-	const uint32_t qA = mm & ~q.b1 & ~q.b0, qC = mm & ~q.b1 & q.b0, qG = mm & q.b1 & ~q.b0, qT = mm & q.b1 & q.b0;
-	const uint32_t sA = ~s.b1 & ~s.b0, sC = ~s.b1 & s.b0, sG = s.b1 & ~s.b0, sT = s.b1 & s.b0;
-	acc.n[0] += (uint32_t)__builtin_popcount(qA & sC), acc.n[1] += (uint32_t)__builtin_popcount(qA & sG), acc.n[2] += (uint32_t)__builtin_popcount(qA & sT);
-	acc.n[3] += (uint32_t)__builtin_popcount(qC & sA), acc.n[4] += (uint32_t)__builtin_popcount(qC & sG), acc.n[5] += (uint32_t)__builtin_popcount(qC & sT);
-	acc.n[6] += (uint32_t)__builtin_popcount(qG & sA), acc.n[7] += (uint32_t)__builtin_popcount(qG & sC), acc.n[8] += (uint32_t)__builtin_popcount(qG & sT);
-	acc.n[9] += (uint32_t)__builtin_popcount(qT & sA), acc.n[10] += (uint32_t)__builtin_popcount(qT & sC), acc.n[11] += (uint32_t)__builtin_popcount(qT & sG);
-}
-// the counters of all lanes into the 4 x 4 counts (cell = subject nucleotide << 2 | query nucleotide, src/model.c:309-337), added or taken back
-__device__ __forceinline__ void subst_flush(const SubstAcc &acc, lds_u32 *hist, bool add) {
-	const uint32_t lane = __lane_id();
-#pragma unroll
-	for (int k = 0; k < 12; ++k) {
-		const uint32_t qn = (uint32_t)k / 3, r = (uint32_t)k % 3, sn = r + (r >= qn ? 1u : 0u);
-		const uint32_t v = wave_sum(acc.n[k]);
-		if (lane == 0 && v) lds_add(&hist[(sn << 2) | qn], add ? v : 0u - v);
-	}
-}
-
-// 16 bits -> the even bits of a word (bit k to bit 2k)
-__device__ __forceinline__ uint32_t spread16(uint32_t x) {
-	x &= 0xffffu;
-	x = (x | (x << 8)) & 0x00ff00ffu;
-	x = (x | (x << 4)) & 0x0f0f0f0fu;
-	x = (x | (x << 2)) & 0x33333333u;
-	return (x | (x << 1)) & 0x55555555u;
 }
 
 #ifdef POOL_KNOCK /* diagnostic builds: parts of the kernel switched off at run time (ANDI_KNOCK=bits) to count their instructions; results are then wrong */
@@ -465,7 +351,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 			return r;
 		};
 		auto generic_probe = [&](uint32_t pp) { return coop_generic_probe(c, pp); };
-		auto settle = [&](uint32_t res, uint32_t ra, uint32_t rlen, const Probe &pr, bool have) { // (as coop_window's)
+		auto settle = [&](uint32_t res, uint32_t ra, uint32_t rlen, const Probe &pr, bool have) { // (coop_dev.h: walk_settle, as text of its own here and below: through the shared functions k_pool_cold measured up to 0.9 % slower, profiles/r11_coop_segment.md)
 			if (!res && have) {
 				if (pr.unique && pr.len >= thr) {
 					if (pr.pos == p + sd) {
@@ -754,7 +640,7 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 				cur = F, done = true;
 			} else if (ej == NOPOS) { // its walk did not land (or where the anchor ends is not in the window): the chain stops at the head
 				cur = pj, done = true;
-				if ((fj & W_STATUS) == W_BREAK) ch.stuck = 1; // (scan_coop.hip: Chain.stuck)
+				if ((fj & W_STATUS) == W_BREAK) ch.stuck = 1; // (coop_dev.h: Chain.stuck)
 			} else { // hopped; the chain stands where the anchor ends
 				if (lane == j) onpath = true;
 				cur = ej;
@@ -925,48 +811,14 @@ __device__ __forceinline__ bool pool_resolve(const ScanArgs &a, const PairCtx &c
 	return true;
 }
 
-__device__ __forceinline__ bool pool_window(const ScanArgs &a, const PairCtx &c, Chain &ch, PoolLds &L, const PoolScratch *G, uint32_t end, uint32_t chunks, bool &through, uint32_t (&same)[4]) {
-	PoolWin pw;
-	pool_stream(a, c, ch, L, G, end, chunks, pw);
-	return pool_resolve(a, c, ch, L, G, end, pw, through, same);
-}
-
-// ------------------------------------------------------------------ the kernel: persistent wavefronts take the segments in order
-#ifndef POOL_OCC
-#define POOL_OCC 7 /* wavefronts per SIMD: 72 registers, 19 spilled -- round 5: bench set 5.66 / 5.09 / 4.92 ms at 4 / 5 / 6; round 6, first session: 7 and 8 a fifth and a third
-                      slower than 6 (45 / 108 spilled); with sweep W's loop split (19 / 34 spilled): C4 shape 19.8 / 19.8 / 22.9 ms at 6 / 7 / 8, C3-like 1.63 / 1.56 / 1.82 */
-#endif
-// One segment: mode G until the chain has a diagonal, windows while it stays on it.
-__device__ __forceinline__ void pool_segment(const ScanArgs &a, PoolLds &L, const PoolScratch *G, uint32_t sub, uint32_t wseg) {
-	const uint32_t lane = __lane_id();
-	if (a.subjects[sub].mode != ANDI_MODE_PROBE) return;
-	const uint32_t qidx = uni(a.seg2query[wseg]);
-	if (a.self[sub] == (int64_t)qidx) return;
-	const uint32_t seg_in_q = wseg - uni(a.qseg_start[qidx]);
-	PairCtx c = make_ctx(a, sub, qidx);
-	const uint32_t start = seg_in_q * a.seg, end = start + a.seg < c.qlen ? start + a.seg : c.qlen;
-	const size_t slot = (size_t)sub * a.total_segs + wseg;
-	const uint32_t n = (uint32_t)c.E.n, thr = c.thr;
-	uint8_t *route = a.route ? a.pair_class + (size_t)sub * a.nq + qidx : nullptr;
-	auto give_up = [&]() {
-		if (lane == 0) a.restitch_count[ANDI_ROUTE_ANY_LEFT] = 1;
-		if (lane == 0) __hip_atomic_store(route, (uint8_t)(__hip_atomic_load(route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | ANDI_ROUTE_LEFT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	};
-	auto given_up = [&]() { return route && (uni(__hip_atomic_load(route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & (ANDI_ROUTE_COOP | ANDI_ROUTE_LEFT)) != ANDI_ROUTE_COOP; };
-	if (given_up()) return;
-	wave_sync();
-	Chain ch;
-	uint32_t my_g = 0;
-	PoolWin pw;
-	if (lane < 16) L.hist[lane] = 0;
-	ch.st = seg_in_q == 0 ? initial_state() : cold_state(start, n);
-	ch.quarter = ch.rest = ch.anchors = ch.marked = 0, ch.blk_base = NOPOS, ch.stuck = 0;
-	ChainState &st = ch.st;
-	wave_sync();
-
-	CSTAT(CS_SEGMENTS, 1);
-	TICK(tall);
+// coop_segment's windows in mode P, for one segment of a persistent wavefront
+struct WindowsPool {
+	static constexpr bool COUNTS_EQUAL = true;
+	const PoolScratch *G;
 	uint32_t same[4] = {0, 0, 0, 0}; // equal pairs the windows found in gaps, by nucleotide
+	uint32_t hint_chunks;            // how long the next run's first window should be, in rounds of 2048 positions (below)
+	uint32_t chunks = 4;             // of a run of windows: rounds the next one may take (begin() sets both)
+	bool through = false;            // ... the last one's chain got to its window's end
 	// How long the next window should be (rounds of 2048 positions): sweep S streams a window to its end before anything is known
 	// about it, so a window that ends early -- the chain leaves its diagonal: an indel, the separator of a joined contig -- has
 	// streamed the rest for nothing.  A window the chain went through doubles the next one; one it did not go through sets the next to
@@ -977,116 +829,28 @@ __device__ __forceinline__ void pool_segment(const ScanArgs &a, PoolLds &L, cons
 	// (the persistent wavefronts begin their segments with windows of different lengths -- 64, 24, 40, 56 rounds by their number -- so that
 	// the six of a SIMD do not all stream, or all walk, at the same time: C4 shape 20.36 -> 20.08 ms; the bench set forced onto this kernel
 	// 4.30 -> 4.36: profiles/r07_pool/stagger_ab.txt)
-	uint32_t hint_chunks = a.pool_first == 64u ? (blockIdx.x & 3u) == 0 ? 64u : (blockIdx.x & 3u) == 1 ? 24u : (blockIdx.x & 3u) == 2 ? 40u : 56u : a.pool_first;
-	// windows one after the other while the chain stays canonical on the diagonal and moves; false: the pair was handed back
-	auto windows = [&]() {
-		// (behind an anchor of thousands of symbols the next mismatch is far: genomes 1e-5 apart -- a window finds one or two, and nothing is
-		// decided behind the last: short windows first)
-		uint32_t chunks = st.lastLen >= 4096 ? 4u : hint_chunks;
-		bool through = false;
-		for (;;) {
-			if (!(st.p < end && st.lastQ + st.lastLen < c.qlen)) break;
-			const uint32_t from = st.lastQ + st.lastLen;
-			pool_stream(a, c, ch, L, G, end, chunks, pw);
-			const bool moved = pool_resolve(a, c, ch, L, G, end, pw, through, same);
-			if (moved && through) {
-				chunks = 2 * chunks < G->maxchunks ? 2 * chunks : G->maxchunks;
-			} else {
-				const uint32_t covered = moved ? st.p - from : 0u;
-				chunks = 4;
-				while (chunks < G->maxchunks && 2048u * chunks < covered) chunks *= 2;
-			}
-			hint_chunks = chunks;
-			if (!moved) break;
-			if (given_up()) return false;
-			if (ch.stuck) break; // (the chain stands at a head whose walk gave up: mode G's step, not another window at the same place)
+	__device__ __forceinline__ WindowsPool(const ScanArgs &a, const PoolScratch *g)
+		: G(g), hint_chunks(a.pool_first == 64u ? (blockIdx.x & 3u) == 0 ? 64u : (blockIdx.x & 3u) == 1 ? 24u : (blockIdx.x & 3u) == 2 ? 40u : 56u : a.pool_first) {}
+	// (behind an anchor of thousands of symbols the next mismatch is far: genomes 1e-5 apart -- a window finds one or two, and nothing is
+	// decided behind the last: short windows first)
+	__device__ __forceinline__ void begin(const Chain &ch) { chunks = ch.st.lastLen >= 4096 ? 4u : hint_chunks, through = false; }
+	// one window; true if the chain moved
+	__device__ __forceinline__ bool window(const ScanArgs &a, const PairCtx &c, Chain &ch, PoolLds &L, uint32_t end) {
+		const ChainState &st = ch.st;
+		const uint32_t from = st.lastQ + st.lastLen;
+		PoolWin pw;
+		pool_stream(a, c, ch, L, G, end, chunks, pw);
+		const bool moved = pool_resolve(a, c, ch, L, G, end, pw, through, same);
+		if (moved && through) {
+			chunks = 2 * chunks < G->maxchunks ? 2 * chunks : G->maxchunks;
+		} else {
+			const uint32_t covered = moved ? st.p - from : 0u;
+			chunks = 4;
+			while (chunks < G->maxchunks && 2048u * chunks < covered) chunks *= 2;
 		}
-		return true;
-	};
-	while (st.p < end) {
-		CSTAT(CS_G_STEPS, 1);
-		++my_g;
-		if (route) {
-			if (my_g > a.route_giveup + (a.seg >> 12)) return give_up();
-			if (given_up()) return;
-		}
-		// ---- one step of mode G (src/process.c:153-197), as k_coop_cold's
-		bool found = false, lucky = false;
-		uint32_t curS = 0, curLen = 0;
-		if (lucky_applies(st, n, thr)) {
-			curS = st.lastS + (st.p - st.lastQ);
-			curLen = coop_lcp(c, st.p, curS, c.qlen - st.p, route ? COOP_TRIAL_LCP : ~0u);
-			if (curLen == NOPOS) return give_up();
-			found = lucky = curLen >= thr;
-		}
-		if (!found) {
-			if (ch.blk_base == NOPOS || st.p < ch.blk_base || st.p - ch.blk_base >= 64) {
-				const uint32_t p = st.p + lane;
-				CSTAT(CS_BLOCKS, 1);
-				Probe pr;
-				pr.len = 0, pr.pos = 0, pr.unique = false;
-				if (p < c.qlen) {
-					LWin w;
-					w.q0 = EMPTY, w.dg = NO_DIAG;
-					pr = lane_probe(c, p, w);
-				}
-				wave_sync();
-				L.pl[lane] = pr.len | (pr.unique ? 0x80000000u : 0u), L.pp[lane] = pr.pos;
-				ch.blk_base = st.p;
-				wave_sync();
-			}
-			const uint32_t v = uni(L.pl[st.p - ch.blk_base]);
-			curLen = v & 0x7fffffffu, curS = uni(L.pp[st.p - ch.blk_base]);
-			found = (v >> 31) && curLen >= thr;
-		}
-		if (found) {
-			coop_account<false>(c, ch, L, curS);
-			st.lastS = curS, st.lastQ = st.p, st.lastLen = curLen;
-		}
-		st.p += curLen + 1;
-		if (found) {
-			wave_sync();
-			coop_note_anchor(a, slot, ch, L);
-		}
-		if (found && lucky && !windows()) return;
+		hint_chunks = chunks;
+		return moved;
 	}
-	TOCK(tall, 7);
-	wave_sync();
-#ifdef ANDI_COOP_STATS
-	if (lane == 0) atomicMax(&g_coop_max[0], my_g);
-#endif
-	(void)my_g;
-	// ---- what pass B reads (scan.h)
-	if (lane == 0) {
-		ColdMark *m = a.marks + slot * ANDI_COLD_MARKS;
-		if (!ch.marked) m->st.pad[0] = 0; // unused mark
-		ChainState out = st;
-		out.pad[0] = 0, out.pad[1] = ch.anchors < 255 ? ch.anchors : 255, out.pad[2] = 0;
-		a.cold_exit[slot] = out;
-		a.exit_p[slot] = st.p;
-	}
-	if (lane < 16) {
-		uint32_t v = L.hist[lane];
-		if (lane == 0 || lane == 5 || lane == 10 || lane == 15) v += ch.quarter;
-		if (lane == 15) v += ch.rest;
-		v += lane == 0 ? same[0] : lane == 5 ? same[1] : lane == 10 ? same[2] : lane == 15 ? same[3] : 0u;
-		a.cold_counts[slot * 16 + lane] = v;
-	}
-}
+};
 
-// the kernel: persistent wavefronts, a scratch each, take the segments in order
-__global__ __launch_bounds__(64, POOL_OCC) void k_pool_cold(ScanArgs a) {
-	__shared__ PoolLds L;
-	const PoolScratch Gs = pool_scratch_at(a.pool_scratch, blockIdx.x, a.pool_maxchunks, a.pool_hc);
-	const uint32_t items = a.total_segs * a.nsub;
-	uint32_t item = blockIdx.x; // the first one; then whatever comes next
-	while (item < items) {
-		const uint32_t row = item / a.total_segs;
-		pool_segment(a, L, &Gs, a.sub_order ? uni(a.sub_order[row]) : row, item % a.total_segs);
-		wave_sync();
-		uint32_t nx = 0;
-		if (__lane_id() == 0) nx = atomicAdd(a.pool_ticket, 1u);
-		item = gridDim.x + lane_read(nx, 0);
-	}
-}
-
+} // namespace

@@ -140,10 +140,10 @@ struct ScanArgs {
 	uint32_t route_seg;           // the wavefront kernel's segment length in a routed call
 	uint32_t reduce_threads;      // pass C: threads of a pair's block (64 where no query has more than 64 segments, else the lane scan's block)
 	uint32_t route_all_few;       // small calls: where the lane scan's pairs would be few, the wavefront kernel takes every pair (k_pair_route)
-	uint32_t route_giveup;        // generic steps in one of its segments beyond which a wavefront hands its pair back (scan_coop.hip: COOP_TRIAL_G; ANDI_COOP_GIVEUP: tests)
+	uint32_t route_giveup;        // generic steps in one of its segments beyond which a wavefront hands its pair back (coop_dev.h: coop_segment; ANDI_COOP_GIVEUP: tests)
 	unsigned long long *route_nt; // [3]: query nucleotides of the pairs whose pass A ran by wavefronts / by lanes, pairs handed back
 	int coop;            // pass A with one wavefront per chain (scan_coop.hip): one segment length, RAW/JC/Kimura, probe-table subjects
-	// ... with the windows' walks pooled through global memory (coop_pool.h: k_pool_cold; the models that split an anchor's length
+	// ... with the windows' walks pooled through global memory (coop_pool.h; scan_coop.hip: k_pool_cold; the models that split an anchor's length
 	// evenly): a scratch per resident wavefront, pool_waves of them; pool_ticket: the next segment to take (zeroed per launch)
 	void *pool_scratch;   // the wavefronts' scratches
 	uint32_t *pool_ticket;
@@ -179,7 +179,7 @@ hipError_t andi_launch_lane_cold(const ScanArgs &a, hipStream_t st);
 int andi_coop_enabled(void); // 0: off (ANDI_COOP=0); < 0: the engine chooses -- tiny calls every pair, others routed per pair (the default); n = 2, 4, 8: every pair, windows of 2048 n symbols
 hipError_t andi_launch_coop_cold(const ScanArgs &a, hipStream_t st);
 int andi_coop_wants_pool(const ScanArgs &a); // a launch of pass A by wavefronts that k_pool_cold would take if the context had its scratch
-int andi_coop_will_pool(const ScanArgs &a); // that launch is k_pool_cold's (coop_pool.h), not k_coop_cold's
+int andi_coop_will_pool(const ScanArgs &a); // that launch is k_pool_cold's (mode P, coop_pool.h), not k_coop_cold's
 size_t andi_pool_scratch_bytes(int device, uint32_t *waves); // the pooled kernels' scratch (4096 bytes for the ticket in front); 0: those kernels are off (ANDI_POOL=0)
 hipError_t andi_launch_lane_stitch(const ScanArgs &a, hipStream_t st);
 hipError_t andi_launch_lane_quad_small(const ScanArgs &a, uint32_t count, hipStream_t st); // k_lane_quad, one wavefront per block (scan_lane.hip compiled a second time)

@@ -500,6 +500,42 @@ __device__ __forceinline__ bool pos_in(const LWin &w, uint32_t p) {
 	return w.q0 != EMPTY && p >= w.q0 && p - w.q0 < WNT;
 }
 
+// Pass A's hand-off to pass B (scan.h: ColdMark, cold_exit), for k_lane_cold and lane_cold_quad.
+// The chain at `st` has just found its anchors-th anchor: the first one's record; after anchors 2, 3, 4 the state and the counts so far
+__device__ __forceinline__ void lane_note_anchor(const ScanArgs &a, size_t slot, uint32_t anchors, const ChainState &st, const Tally &tally) {
+	ColdMark *marks = a.marks + slot * ANDI_COLD_MARKS;
+	if (anchors == 1) *(uint4 *)marks[0].first = make_uint4(st.lastQ, st.lastS, st.lastLen, 0);
+	if (anchors >= 2 && anchors < 2 + ANDI_COLD_MARKS) { // remember the state after anchors 2, 3, 4
+		ColdMark *m = marks + (anchors - 2);
+		ChainState ms = st;
+		ms.pad[0] = 1;
+		m->st = ms;
+		uint32_t v[16];
+#pragma unroll
+		for (int t = 0; t < 16; ++t) v[t] = tally.hist[t * BLOCK];
+		v[0] += tally.quarter + tally.same[0], v[5] += tally.quarter + tally.same[1];
+		v[10] += tally.quarter + tally.same[2], v[15] += tally.quarter + tally.rest + tally.same[3];
+		uint4 *mc = (uint4 *)m->counts;
+#pragma unroll
+		for (int t = 0; t < 4; ++t) mc[t] = make_uint4(v[4 * t], v[4 * t + 1], v[4 * t + 2], v[4 * t + 3]);
+	}
+}
+// The chain has left its segment at `st` with `anchors` anchors: the marks it did not reach, its exit, its counts
+__device__ __forceinline__ void lane_finish(const ScanArgs &a, size_t slot, uint32_t anchors, ChainState &st, Tally &tally) {
+	ColdMark *marks = a.marks + slot * ANDI_COLD_MARKS;
+	for (uint32_t k = anchors < 2 ? 0 : anchors - 1; k < ANDI_COLD_MARKS; ++k) marks[k].st.pad[0] = 0; // unused marks
+	st.pad[1] = anchors < 255 ? anchors : 255;
+	a.cold_exit[slot] = st;
+	a.exit_p[slot] = st.p;
+	tally_finish<1>(tally);
+	uint32_t out[16];
+#pragma unroll
+	for (int t = 0; t < 16; ++t) out[t] = tally.hist[t * BLOCK];
+	uint4 *dst = (uint4 *)(a.cold_counts + slot * 16);
+#pragma unroll
+	for (int t = 0; t < 4; ++t) dst[t] = make_uint4(out[4 * t], out[4 * t + 1], out[4 * t + 2], out[4 * t + 3]);
+}
+
 // Pass A with ALL streaming along diagonals done by QUADS of lanes (ANDI_LANE_STREAM=2).
 //
 // The floors (k_stream_floor, profiles/r02_stream/floor.txt): a lane that reads its own two streams 16 bytes at a
@@ -527,7 +563,6 @@ __device__ __forceinline__ void lane_cold_quad(const ScanArgs &a, const LaneItem
 	LWin w;
 	w.q0 = EMPTY, w.dg = NO_DIAG;
 	const size_t slot = it.slot;
-	ColdMark *marks = a.marks + slot * ANDI_COLD_MARKS;
 	uint32_t anchors = 0;
 	uint4 Bq[4], Bs[4]; // 128 symbols of the query from b0 (even) and of the subject against them on diagonal bdg
 	uint32_t b0 = EMPTY;
@@ -691,41 +726,16 @@ __device__ __forceinline__ void lane_cold_quad(const ScanArgs &a, const LaneItem
 		}
 		st.p += curLen + 1;
 		mode = 0;
-		if (found && ++anchors == 1) {
-			*(uint4 *)marks[0].first = make_uint4(st.lastQ, st.lastS, st.lastLen, 0);
+		if (found) lane_note_anchor(a, slot, ++anchors, st, tally);
+		if (found && anchors == 1) {
 			fQ = st.lastQ, fS = st.lastS, fLen = st.lastLen;
 			if ((threadIdx.x & 63u) == 0 && fQ == it.start)
 				__hip_atomic_store(a.first_pub + slot, ((unsigned long long)fS << 32) | fLen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		}
-		if (found && anchors >= 2 && anchors < 2 + ANDI_COLD_MARKS) { // remember the state after anchors 2, 3, 4
-			ColdMark *m = marks + (anchors - 2);
-			ChainState ms = st;
-			ms.pad[0] = 1;
-			m->st = ms;
-			uint32_t v[16];
-#pragma unroll
-			for (int t = 0; t < 16; ++t) v[t] = tally.hist[t * BLOCK];
-			v[0] += tally.quarter + tally.same[0], v[5] += tally.quarter + tally.same[1];
-			v[10] += tally.quarter + tally.same[2], v[15] += tally.quarter + tally.rest + tally.same[3];
-			uint4 *mc = (uint4 *)m->counts;
-#pragma unroll
-			for (int t = 0; t < 4; ++t) mc[t] = make_uint4(v[4 * t], v[4 * t + 1], v[4 * t + 2], v[4 * t + 3]);
-		}
 		active = st.p < it.end;
 	}
 	if (!it.valid) return;
-	for (uint32_t k = anchors < 2 ? 0 : anchors - 1; k < ANDI_COLD_MARKS; ++k) marks[k].st.pad[0] = 0; // unused marks
-
-	st.pad[1] = anchors < 255 ? anchors : 255;
-	a.cold_exit[slot] = st;
-	a.exit_p[slot] = st.p;
-	tally_finish<1>(tally);
-	uint32_t out[16];
-#pragma unroll
-	for (int t = 0; t < 16; ++t) out[t] = tally.hist[t * BLOCK];
-	uint4 *dst = (uint4 *)(a.cold_counts + slot * 16);
-#pragma unroll
-	for (int t = 0; t < 4; ++t) dst[t] = make_uint4(out[4 * t], out[4 * t + 1], out[4 * t + 2], out[4 * t + 3]);
+	lane_finish(a, slot, anchors, st, tally);
 }
 
 template <bool EXACT>
@@ -773,7 +783,6 @@ __global__ __launch_bounds__(BLOCK, PER_PAIR ? 8 : 7) void k_lane_cold(ScanArgs 
 	LWin w;
 	w.q0 = EMPTY, w.dg = NO_DIAG;
 	const size_t slot = it.slot;
-	auto marks = [&]() { return a.marks + slot * ANDI_COLD_MARKS; }; // (formed where it is used: not held through the loop)
 	uint32_t anchors = 0;
 	while (st.p < it.end) {
 		bool found;
@@ -790,34 +799,9 @@ __global__ __launch_bounds__(BLOCK, PER_PAIR ? 8 : 7) void k_lane_cold(ScanArgs 
 		}
 #endif
 		st = lane_step<EXACT>(c, st, tally, w, found);
-		if (found && ++anchors == 1) *(uint4 *)marks()[0].first = make_uint4(st.lastQ, st.lastS, st.lastLen, 0);
-		if (found && anchors >= 2 && anchors < 2 + ANDI_COLD_MARKS) { // remember the state after anchors 2, 3, 4
-			ColdMark *m = marks() + (anchors - 2);
-			ChainState ms = st;
-			ms.pad[0] = 1;
-			m->st = ms;
-			uint32_t v[16];
-#pragma unroll
-			for (int t = 0; t < 16; ++t) v[t] = tally.hist[t * BLOCK];
-			v[0] += tally.quarter + tally.same[0], v[5] += tally.quarter + tally.same[1];
-			v[10] += tally.quarter + tally.same[2], v[15] += tally.quarter + tally.rest + tally.same[3];
-			uint4 *mc = (uint4 *)m->counts;
-#pragma unroll
-			for (int t = 0; t < 4; ++t) mc[t] = make_uint4(v[4 * t], v[4 * t + 1], v[4 * t + 2], v[4 * t + 3]);
-		}
+		if (found) lane_note_anchor(a, slot, ++anchors, st, tally); // (a and slot, not a pointer to the marks: it is not held through the loop)
 	}
-	for (uint32_t k = anchors < 2 ? 0 : anchors - 1; k < ANDI_COLD_MARKS; ++k) marks()[k].st.pad[0] = 0; // unused marks
-
-	st.pad[1] = anchors < 255 ? anchors : 255;
-	a.cold_exit[slot] = st;
-	a.exit_p[slot] = st.p;
-	tally_finish<1>(tally);
-	uint32_t out[16];
-#pragma unroll
-	for (int t = 0; t < 16; ++t) out[t] = tally.hist[t * BLOCK];
-	uint4 *dst = (uint4 *)(a.cold_counts + slot * 16);
-#pragma unroll
-	for (int t = 0; t < 4; ++t) dst[t] = make_uint4(out[4 * t], out[4 * t + 1], out[4 * t + 2], out[4 * t + 3]);
+	lane_finish(a, slot, anchors, st, tally);
 }
 
 // ------------------------------------------------------------------ pass B
@@ -1254,7 +1238,7 @@ __device__ __forceinline__ void planes_of(const uint4 v, uint32_t *out) {
 }
 
 // ... and, for the queries, bits 0 and 1 of each symbol once more as interleaved 2-bit codes (symbol k of a half block: bits 2k, 2k + 1), two
-// words per block: what a window of pass A by wavefronts keeps of the query in LDS (scan_coop.hip: coop_window).  They are made from the
+// words per block: what a window of pass A by wavefronts keeps of the query in LDS (coop_window.h: coop_window).  They are made from the
 // plane words themselves, so separators, padding and a ragged last block read as they do in the planes.
 __global__ __launch_bounds__(256) void k_pack_planes(const uint4 *__restrict__ N0, int64_t blocks, uint32_t *__restrict__ planes, uint32_t *__restrict__ codes) {
 	const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -108,7 +108,7 @@ LEAD_IN = np.concatenate([np.arange(1000, REGION[0] - 999, 1000), [REGION[0] - 5
 
 def _pairs_every(period):
     """pairs of adjacent substitutions every `period` positions of the region -- and single ones every 1000 positions in
-    front of it: a window begins behind a lucky anchor only (coop_pool.h: pool_segment), and in the region the chain finds
+    front of it: a window begins behind a lucky anchor only (coop_dev.h: coop_segment), and in the region the chain finds
     next to none, so the window that meets the region's heads is one that began at these"""
     x = np.arange(REGION[0], REGION[1] - 1, period)
     return np.concatenate([LEAD_IN, x, x + 1])

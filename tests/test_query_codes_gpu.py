@@ -1,5 +1,5 @@
 """The queries' 2-bit codes are staged once (andi_amd/csrc/scan_lane.hip: k_pack_planes writes them beside the planes; ScanArgs.qcodes)
-and the windows of pass A by wavefronts load them instead of making them from the planes for every pair (scan_coop.hip:
+and the windows of pass A by wavefronts load them instead of making them from the planes for every pair (coop_window.h:
 coop_window).  The staged words against numpy, through a hook of the suite's library; the kernel with windows of five chunks
 (ANDI_COOP=5) against the oracle and the lane scan (ANDI_COOP=0) on queries whose lengths lie around the edges of a block of 32
 symbols, of a chunk of 2048 and of a window of 10240."""

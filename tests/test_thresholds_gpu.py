@@ -3,7 +3,7 @@
 The threshold (min_anchor_length, the user's -p) decides every count; the rest of the suite runs five p-values, which
 give thresholds of about 9 to 20.  Here a ladder (tests/threshold_cases.py: LADDER): both bounds of the range plan_call
 admits the wavefront kernels for (2 and 30) and the first threshold they refuse (31); powers of two, at which the smear
-of the head rule (coop_pool.h: pool_stream, scan_coop.hip: coop_window) takes no remainder step, and thresholds whose
+of the head rule (coop_pool.h: pool_stream, coop_window.h: coop_window) takes no remainder step, and thresholds whose
 remainder step is 1, 3, 7, 13 and 14 positions; thresholds below the probe table's depth K on texts of normal size
 (coop_probe_codes' branch for K >= thr).  One test per threshold over every path of pass A: the lane scan, k_lane_quad,
 k_coop_cold at windows of 2, 4 and 5 chunks, k_pool_cold, the reference's own walk, pass C's fix-ups -- hook-free paths
