@@ -4,7 +4,7 @@
 // over the replicates (Lemoine et al. 2018: the transfer bootstrap expectation is 1 - sum / (used * (depth - 1))).
 //
 // The host's validation of the records, the replicates' groups and k_sets are nj_sets.h's, shared with nj_support.hip and
-// nj_splits.hip.  A tree's leaf sets are bitsets of W = ceil(n / 64) words (the padding bits of the last word are zero),
+// nj_splits.hip; the tile's constants and stage, col and bcnt_add are nj_tile.h's, shared with nj_taxa.hip.  A tree's leaf sets are bitsets of W = ceil(n / 64) words (the padding bits of the last word are zero),
 // so h(A, B) = |A xor B| is a sum of popcounts and the transfer distance is min(h, n - h).  This call's own: a set costs
 // its record's two children and one index of per beside its words, there is a point tree, and a group's sets go through
 // k_transfer and, if per is asked for, one copy of the group's rows to the host:
@@ -27,14 +27,9 @@
 #include <vector>
 
 #include "nj_sets.h"
+#include "nj_tile.h"
 
 namespace {
-
-constexpr uint32_t TS = 128, TT = 128; // sets of the point tree / of the replicate per tile
-constexpr uint32_t WC = 8;             // words per chunk in LDS
-constexpr uint32_t MS = 8, MT = 8;     // a thread's micro-tile: point sets col(ty, i), replicate sets col(tx, j)
-constexpr uint32_t LDP = TS + 4;       // words per LDS row (the staging stores of a wavefront spread over the banks)
-static_assert(TS == 16 * MS && TT == 16 * MT && TS == TT && LDP % 2 == 0, "256 threads as 16 x 16 micro-tiles; 16-byte LDS reads");
 
 // depth[s] = min(|L_s|, n - |L_s|).  One wavefront per set.
 __global__ __launch_bounds__(256) void k_depth(const uint64_t *__restrict__ sets, uint32_t n, uint32_t nsets, uint32_t W,
@@ -46,28 +41,6 @@ __global__ __launch_bounds__(256) void k_depth(const uint64_t *__restrict__ sets
 	for (uint32_t w = lane; w < W; w += 64) c += (uint32_t)__builtin_popcountll(set[w]);
 	for (int m = 32; m > 0; m >>= 1) c += __shfl_xor(c, m);
 	if (lane == 0) depth[s] = c < n - c ? c : n - c;
-}
-
-// popcount(x) + sum as the one instruction it is (the compiler's own choice is two counts from zero and a three-way add)
-__device__ inline uint32_t bcnt_add(uint32_t x, uint32_t sum) {
-	uint32_t r;
-	asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(sum));
-	return r;
-}
-
-// the tile row of micro-tile entry i of the thread with coordinate c (0 .. 15): pairs of neighbours, 32 apart
-__device__ inline uint32_t col(uint32_t c, uint32_t i) { return 2 * c + (i & 1) + 16 * (i & ~1u); }
-
-// rows first .. first + TS of sets (nsets x W), words w0 .. w0 + wc, to tile[word][row]; rows past nsets are zero
-__device__ inline void stage(uint64_t (*tile)[LDP], const uint64_t *__restrict__ sets, uint32_t first, uint32_t nsets,
-							 uint32_t W, uint32_t w0, uint32_t wc) {
-	const uint32_t w = threadIdx.x % WC;
-	if (w >= wc) return;
-#pragma unroll
-	for (uint32_t row = threadIdx.x / WC; row < TS; row += 256 / WC) {
-		const uint32_t s = first + row;
-		tile[w][row] = s < nsets ? sets[(size_t)s * W + w0 + w] : 0ull;
-	}
 }
 
 // Block (x, y): point sets x * TS ..., replicate y of the group.  per (may be null) and transfer as in the header;

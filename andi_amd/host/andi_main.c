@@ -397,6 +397,11 @@ static void usage(int status) {
 		"                       each inner branch labelled with the number of those trees that have it\n"
 		"      --transfer=FILE  With -b: write the tree of the first matrix to FILE, each inner branch labelled with its\n"
 		"                       transfer bootstrap expectation (TBE, between 0 and 1) over the bootstrap matrices' trees\n"
+		"      --rogues=FILE    With -b: write one line per sequence to FILE: in how many pairs of a branch of the first\n"
+		"                       matrix's tree and the nearest branch of a bootstrap matrix's tree the sequence is one of\n"
+		"                       those that have to move (its transfer score), and that number per counted pair\n"
+		"      --rogue-cutoff=X With --rogues: count a pair of branches up to the transfer distance X * (depth - 1), with\n"
+		"                       X from 0 to 1; default: 0.3\n"
 		"      --trees-only     With -b and at least one of --tree, --support, --consensus, --transfer: do not print the\n"
 		"                       bootstrap matrices; their trees are drawn, estimated and joined on the GPU, for any number\n"
 		"                       of replicates.  These trees come from the portable estimator (its own logarithm, within\n"
@@ -483,6 +488,13 @@ static tree_file outs[OUT_COUNT] = {
 	{"transfer", "Transfer support (--transfer) is" WITH_REFERENCE, "Transfer support (--transfer) needs" NEEDS_B, NULL, NULL},
 };
 
+/* --rogues: the table of the genomes' transfer scores; not one of the four files of trees, but written from the same state */
+typedef struct {
+	const char *path, *cutoff_arg;
+	FILE *f;
+	double cutoff;
+} rogue_out;
+
 /* what one Newick line is made of: the consensus tree's nodes; or the records J with the transfer bootstrap expectation
  * (depth, transfer, used) or the support values (NULL: none) as inner labels */
 typedef struct {
@@ -558,6 +570,7 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
  * andi_hip_nj_splits call behind the loop.
  * --transfer (tf): the point estimate's tree again, labelled with the transfer bootstrap expectation: per chunk one
  * andi_hip_nj_transfer call next to the support count's, on the same records; the chunks' sums add up.
+ * --rogues (rf): per chunk one andi_hip_nj_transfer_taxa call on the same records again; the chunks' counts add up.
  *
  * One state over the run: support_begin (the point estimate's tree), support_chunk for every chunk of replicates main
  * draws -- as matrices B, or, under --trees-only, as nothing: andi_hip_bootstrap_nj draws, estimates and joins them on the
@@ -570,6 +583,7 @@ typedef struct { /* what a run gives them */
 	unsigned long replicates;
 	int model, truncate, trees_only;
 	uint64_t seed;
+	const rogue_out *rogues;
 } boot_run;
 
 typedef struct {
@@ -582,14 +596,14 @@ typedef struct {
 	int64_t *bad;
 	uint8_t *skipall;
 	uint32_t *total, *part, *depth;
-	uint64_t *ttotal, *tpart;
-	int point_ok, trans_ok, cons_ok, stopped;
+	uint64_t *ttotal, *tpart, *moved, *mpart, pairs;
+	int point_ok, trans_ok, cons_ok, rogue_ok, stopped;
 } support_state;
 
 static void support_begin(support_state *s, const tree_file *o, const boot_run *r, const andi_hip_model *M) {
 	memset(s, 0, sizeof *s);
 	s->r = *r, s->o = o;
-	FILE *f = o[OUT_SUPPORT].f, *cf = o[OUT_CONSENSUS].f, *tf = o[OUT_TRANSFER].f;
+	FILE *f = o[OUT_SUPPORT].f, *cf = o[OUT_CONSENSUS].f, *tf = o[OUT_TRANSFER].f, *rf = r->rogues->f;
 	const genome *g = r->g;
 	const size_t n = r->n, replicates = r->replicates;
 	const int trees_only = r->trees_only;
@@ -605,22 +619,25 @@ static void support_begin(support_state *s, const tree_file *o, const boot_run *
 	s->skipall = malloc(kept);
 	s->total = calloc(nsup, sizeof *s->total), s->part = calloc(nsup, sizeof *s->part), s->depth = calloc(nsup, sizeof *s->depth);
 	s->ttotal = calloc(nsup, sizeof *s->ttotal), s->tpart = calloc(nsup, sizeof *s->tpart);
+	s->moved = calloc(n, sizeof *s->moved), s->mpart = calloc(n, sizeof *s->mpart);
 	if (!D || !s->J || !s->Rall || !s->bad || !s->skipall || !s->total || !s->part || !s->depth || !s->ttotal || !s->tpart ||
-		((f || tf) && andi_hip_distances(M, n, r->model, D)))
+		!s->moved || !s->mpart || ((f || tf || rf) && andi_hip_distances(M, n, r->model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
-	s->point_ok = f != NULL, s->trans_ok = tf != NULL, s->cons_ok = cf != NULL;
-	for (size_t i = 0; i < n && (s->point_ok || s->trans_ok); i++)
+	s->point_ok = f != NULL, s->trans_ok = tf != NULL, s->cons_ok = cf != NULL, s->rogue_ok = rf != NULL;
+	for (size_t i = 0; i < n && (s->point_ok || s->trans_ok || s->rogue_ok); i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
 				if (f) soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
 				if (tf) soft_warnx("No transfer support: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
-				s->point_ok = s->trans_ok = 0;
+				if (rf) soft_warnx("No rogue table: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
+				s->point_ok = s->trans_ok = s->rogue_ok = 0;
 				break;
 			}
-	if ((s->point_ok || s->trans_ok) && andi_hip_nj(r->ctx, D, n, s->J)) {
+	if ((s->point_ok || s->trans_ok || s->rogue_ok) && andi_hip_nj(r->ctx, D, n, s->J)) {
 		if (f) soft_warnx("No support values: %s", andi_hip_last_error(r->ctx));
 		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(r->ctx));
-		s->point_ok = s->trans_ok = 0;
+		if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(r->ctx));
+		s->point_ok = s->trans_ok = s->rogue_ok = 0;
 	}
 }
 
@@ -629,7 +646,7 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 	const size_t n = s->r.n, nrec = s->nrec;
 	const genome *g = s->r.g;
 	andi_hip_ctx *ctx = s->r.ctx;
-	FILE *f = s->o[OUT_SUPPORT].f, *cf = s->o[OUT_CONSENSUS].f, *tf = s->o[OUT_TRANSFER].f;
+	FILE *f = s->o[OUT_SUPPORT].f, *cf = s->o[OUT_CONSENSUS].f, *tf = s->o[OUT_TRANSFER].f, *rf = s->r.rogues->f;
 	for (unsigned long first = start; first < start + count && !s->stopped; first += s->cap) {
 		const size_t c = start + count - first < s->cap ? start + count - first : s->cap;
 		andi_hip_nj_join *R = cf ? s->Rall + first * nrec : s->Rall;
@@ -647,8 +664,9 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
 			if (cf) soft_warnx("No consensus tree: %s", andi_hip_last_error(ctx));
 			if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(ctx));
-			if (!f && !cf && !tf) soft_warnx("No trees: %s", andi_hip_last_error(ctx));
-			s->point_ok = s->cons_ok = s->trans_ok = 0;
+			if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(ctx));
+			if (!f && !cf && !tf && !rf) soft_warnx("No trees: %s", andi_hip_last_error(ctx));
+			s->point_ok = s->cons_ok = s->trans_ok = s->rogue_ok = 0;
 			s->stopped = 1;
 			break;
 		}
@@ -675,6 +693,16 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			} else
 				for (size_t k = 0; k + 3 < n; k++) s->ttotal[k] += s->tpart[k];
 		}
+		if (s->rogue_ok) {
+			uint64_t pairs = 0;
+			if (andi_hip_nj_transfer_taxa(ctx, s->J, R, n, c, skip, s->r.rogues->cutoff, s->mpart, &pairs, NULL, NULL)) {
+				soft_warnx("No rogue table: %s", andi_hip_last_error(ctx));
+				s->rogue_ok = 0;
+			} else {
+				for (size_t i = 0; i < n; i++) s->moved[i] += s->mpart[i];
+				s->pairs += pairs;
+			}
+		}
 	}
 }
 
@@ -684,7 +712,7 @@ static void support_end(support_state *s, int complete) {
 	const char **names = s->r.names;
 	andi_hip_ctx *ctx = s->r.ctx;
 	const unsigned long counted = s->counted, replicates = s->r.replicates;
-	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = 0;
+	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = s->rogue_ok = 0;
 	if (s->point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
 		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total}, names, n, s->r.truncate);
@@ -697,6 +725,21 @@ static void support_end(support_state *s, int complete) {
 		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
 		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted}, names, n,
 				   s->r.truncate);
+	}
+	if (s->rogue_ok && counted == 0) {
+		soft_warnx("No rogue table: no bootstrap matrix has a tree.");
+		s->rogue_ok = 0;
+	}
+	if (s->rogue_ok) {
+		const rogue_out *ro = s->r.rogues;
+		if (counted < replicates) soft_warnx("Rogue table from %lu of %lu bootstrap matrices.", counted, replicates);
+		if (s->pairs == 0) warnx("Rogue table: no branch of a bootstrap matrix's tree is within the cutoff; every index is 0.");
+		const int w = s->r.truncate ? 10 : INT_MAX;
+		int bad = fputs("#name\tmoved\tindex\n", ro->f) == EOF;
+		for (size_t i = 0; i < n && !bad; i++)
+			bad = fprintf(ro->f, "%.*s\t%llu\t%.6g\n", w, names[i], (unsigned long long)s->moved[i],
+						  s->pairs ? (double)s->moved[i] / (double)s->pairs : 0.0) < 0;
+		if (bad) err(1, "%s", ro->path);
 	}
 	if (s->cons_ok && counted == 0) {
 		soft_warnx("No consensus tree: no bootstrap matrix has a tree.");
@@ -720,7 +763,7 @@ static void support_end(support_state *s, int complete) {
 		free(ids), free(nodes);
 	}
 	free(s->D), free(s->J), free(s->Rall), free(s->bad), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
-		free(s->tpart);
+		free(s->tpart), free(s->moved), free(s->mpart);
 }
 
 /* --dendrogram, --clusters: agglomerative clustering (andi_hip_linkage) of every printed matrix, from the averaged distances
@@ -1074,6 +1117,8 @@ int main(int argc, char *argv[]) {
 												 {"support", required_argument, NULL, 0},
 												 {"consensus", required_argument, NULL, 0},
 												 {"transfer", required_argument, NULL, 0},
+												 {"rogues", required_argument, NULL, 0},
+												 {"rogue-cutoff", required_argument, NULL, 0},
 												 {"trees-only", no_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
@@ -1104,6 +1149,7 @@ int main(int argc, char *argv[]) {
 	name_list files = {0}, ref_files = {0}; /* ref_files: --reference, --reference-list, the query-versus-reference mode */
 	int rect = 0, bootstrap_given = 0, trees_only = 0;
 	tree_out tree = {.o = &outs[OUT_TREE]};
+	rogue_out rogues = {.cutoff = 0.3}; /* (booster's default for the same cutoff) */
 	cluster_out clus = {.method = ANDI_LINK_AVERAGE};
 	place_out place = {.method = ANDI_PLACE_FM};
 	screen_opts screen = {.k = 21, .scale = 1000, .min = 1};
@@ -1122,6 +1168,8 @@ int main(int argc, char *argv[]) {
 				for (int k = 0; k < OUT_COUNT; k++)
 					if (!strcmp(o, outs[k].option)) outs[k].path = optarg;
 				if (!strcmp(o, "trees-only")) trees_only = 1;
+				if (!strcmp(o, "rogues")) rogues.path = optarg;
+				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
 				if (!strcmp(o, "clusters")) clus.clusters_path = optarg;
 				if (!strcmp(o, "linkage")) {
@@ -1259,8 +1307,19 @@ int main(int argc, char *argv[]) {
 	if (trees_only && !bootstrap) errx(1, "Trees without matrices (--trees-only) need bootstrap replicates: give -b N with N of at least 2.");
 	if (trees_only && !any_out)
 		errx(1, "Trees without matrices (--trees-only) need somewhere to go: give at least one of --tree, --support, --consensus, --transfer.");
+	if (rogues.path && rect) errx(1, "Rogue genomes (--rogues) are" WITH_REFERENCE);
+	if (rogues.path && !bootstrap) errx(1, "Rogue genomes (--rogues) need" NEEDS_B);
+	if (rogues.cutoff_arg && !rogues.path) errx(1, "A cutoff (--rogue-cutoff) needs somewhere to go: give --rogues=FILE.");
+	if (rogues.cutoff_arg) {
+		errno = 0;
+		char *end;
+		rogues.cutoff = strtod(rogues.cutoff_arg, &end);
+		if (errno || end == rogues.cutoff_arg || *end || !(rogues.cutoff >= 0.0 && rogues.cutoff <= 1.0))
+			errx(1, "Expected a number from 0 to 1 for --rogue-cutoff, but '%s' was given.", rogues.cutoff_arg);
+	}
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
+	if (rogues.path && !(rogues.f = fopen(rogues.path, "w"))) err(1, "%s", rogues.path);
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
 	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
@@ -1336,7 +1395,7 @@ int main(int argc, char *argv[]) {
 		andi_hip_model *B = trees_only ? NULL : malloc(chunk * n * n * sizeof *B);
 		/* the reference seeds its generator from the clock; ANDI_HIP_SEED=k draws the same matrices on every run */
 		const uint64_t seed = getenv("ANDI_HIP_SEED") ? strtoull(getenv("ANDI_HIP_SEED"), NULL, 10) : (uint64_t)time(NULL);
-		const int trees = outs[OUT_SUPPORT].f || outs[OUT_CONSENSUS].f || outs[OUT_TRANSFER].f || trees_only;
+		const int trees = outs[OUT_SUPPORT].f || outs[OUT_CONSENSUS].f || outs[OUT_TRANSFER].f || rogues.f || trees_only;
 		support_state st;
 		int begun = 0, ok = 1;
 		if ((!trees_only && !B) || andi_hip_ctx_create(&ctx, opts.device, msg, sizeof msg)) ok = 0;
@@ -1355,7 +1414,7 @@ int main(int argc, char *argv[]) {
 			if (clus.df || clus.cf) cluster_chunk(&clus, B, first, c, all.v, names, n, opts.model, truncate);
 			if (!trees) continue;
 			if (!begun) {
-				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed};
+				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed, &rogues};
 				support_begin(&st, outs, &run, M);
 			}
 			begun = 1;
@@ -1371,6 +1430,7 @@ int main(int argc, char *argv[]) {
 	if (tree.ctx) andi_hip_ctx_destroy(tree.ctx);
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].f && fclose(outs[k].f)) err(1, "%s", outs[k].path);
+	if (rogues.f && fclose(rogues.f)) err(1, "%s", rogues.path);
 	free(M);
 	free(in);
 	free(names);

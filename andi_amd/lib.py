@@ -121,6 +121,7 @@ SYMBOLS = {
     "andi_hip_nj_splits": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_size_t), C.POINTER(_P),
                                      C.POINTER(_P)]),
     "andi_hip_nj_transfer": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P, _P, _P]),
+    "andi_hip_nj_transfer_taxa": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, C.c_double, _P, _P, _P, _P]),
     "andi_hip_linkage": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "andi_hip_linkage_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P]),
     "andi_hip_linkage_cut": (C.c_int, [_P, C.c_size_t, C.c_double, _P, C.POINTER(C.c_size_t)]),
@@ -1022,6 +1023,29 @@ def nj_transfer(ctx: Context, J, reps, skip=None, per=False):
                                            skip.ctypes.data if skip is not None else None, depth.ctypes.data,
                                            transfer.ctypes.data, each.ctypes.data if per else None), "nj_transfer")
     return (depth, transfer, each) if per else (depth, transfer)
+
+
+def nj_transfer_taxa(ctx: Context, J, reps, skip=None, cutoff=0.3, detail=False):
+    """The rogue genomes of a bootstrap (andi_hip_nj_transfer_taxa): (moved, pairs) -- uint64[n], for every leaf the number
+    of counted pairs (replicate, branch of J) in which it is one of the leaves that have to move, and the number of counted
+    pairs; a pair counts iff its transfer distance is at most floor(cutoff * (depth - 1)).  With detail=True also match
+    and dist, (count, n - 3) uint32: the replicate's nearest pair record (the least in a tie) and its uncapped distance
+    (0xFFFFFFFF in a skipped replicate's row)."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    reps = np.ascontiguousarray(reps, dtype=NJ_JOIN)
+    n = len(J) + 2
+    assert reps.ndim == 2 and reps.shape[1] == len(J)
+    count = reps.shape[0]
+    skip = _skip(skip, count)
+    moved = np.zeros(n, np.uint64)
+    pairs = C.c_uint64(0)
+    match = np.zeros((count, max(n - 3, 0)), np.uint32) if detail else None
+    dist = np.zeros((count, max(n - 3, 0)), np.uint32) if detail else None
+    ctx._check(load().andi_hip_nj_transfer_taxa(ctx._h, J.ctypes.data, reps.ctypes.data, n, count,
+                                                skip.ctypes.data if skip is not None else None, float(cutoff),
+                                                moved.ctypes.data, C.addressof(pairs), match.ctypes.data if detail else None,
+                                                dist.ctypes.data if detail else None), "nj_transfer_taxa")
+    return (moved, int(pairs.value), match, dist) if detail else (moved, int(pairs.value))
 
 
 def nj_splits(ctx: Context, reps, skip=None):

@@ -19,7 +19,8 @@
  * andi_hip_distances, andi_hip_nj and andi_hip_format_newick (additions only as well); and bootstrap support on that
  * tree: andi_hip_nj_batch, andi_hip_nj_support and andi_hip_format_newick_support (additions only); and the majority-rule
  * consensus tree of the bootstrap: andi_hip_nj_splits, andi_hip_consensus and andi_hip_format_newick_consensus (additions only);
- * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only); and bootstrap
+ * and transfer bootstrap support: andi_hip_nj_transfer and andi_hip_format_newick_transfer (additions only), and the genomes
+ * behind it: andi_hip_nj_transfer_taxa (an addition only); and bootstrap
  * trees without matrices: andi_hip_estimate_portable, andi_hip_bootstrap_range and andi_hip_bootstrap_nj (additions only); and linkage
  * clustering: andi_hip_linkage, andi_hip_linkage_batch, andi_hip_linkage_cut, andi_hip_cluster_medoids,
  * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only); and placement of queries on a tree:
@@ -489,6 +490,32 @@ int andi_hip_nj_splits(andi_hip_ctx *ctx, const andi_hip_nj_join *reps, size_t n
  * does not fail on size while one tree's sets fit.  Work: (n - 3)^2 * used * ceil(n / 64) word pairs.  Synchronous. */
 int andi_hip_nj_transfer(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
 						 size_t count, const uint8_t *skip, uint32_t *depth, uint64_t *transfer, uint32_t *per);
+/* The rogue genomes of the bootstrap: per leaf, how often it is one of the leaves that have to move (the per-taxon
+ * transfer score of Lemoine et al. 2018 and their booster).  tree, reps, n, count, skip, L_s, the validation of the records
+ * and the grouping of the replicates are those of andi_hip_nj_transfer.  For a used replicate k and a pair record s of the
+ * tree (0 <= s < n - 3):
+ *  - for every pair record t of replicate k, h = |L_s xor L_{k,t}| over the n leaves and d = min(h, n - h);
+ *  - dist[k*(n-3) + s] = the least d over t.  It is NOT capped: the replicate's leaf branches are no candidates;
+ *  - match[k*(n-3) + s] = the LEAST t that attains it.  In a tie the result therefore depends on the order of the
+ *    replicate's records (as booster's depends on its traversal): another writing of the same replicate tree can name
+ *    another branch and so other leaves;
+ *  - flip = h > n - h at that t (none at h == n - h); M(k, s) = L_s xor L_{k,match}, with flip its complement within the
+ *    n leaves (the padding bits of the last word stay zero): |M(k, s)| = dist[k][s], the leaves that have to move;
+ *  - limit[s] = (uint32_t)floor(cutoff * (double)(depth[s] - 1)), one rounded multiplication, depth as in
+ *    andi_hip_nj_transfer; the pair (k, s) is COUNTED iff dist[k][s] <= limit[s].  A counted pair has dist <= depth - 1,
+ *    so its dist is andi_hip_nj_transfer's per;
+ *  - moved[i] (n values) = the number of counted pairs with leaf i in M(k, s); *pairs = the number of counted pairs.
+ * match and dist are count * (n - 3) values each; either may be NULL; a skipped replicate's row is 0xFFFFFFFF in both.
+ * What follows: min(dist, depth - 1) is andi_hip_nj_transfer's per; the sum of moved is the sum of dist over the counted
+ * pairs; cutoff = 0 gives moved all 0 and *pairs = the sum of andi_hip_nj_support's support; the moved and pairs of calls
+ * over disjoint chunks of replicates add up to those of one call; nothing depends on the grouping.  Everything is an
+ * integer and exact.  n < 4: moved[0 .. n) and *pairs are set to 0, match and dist are not written, returns 0.  Every
+ * replicate skipped: zeros, the rows 0xFFFFFFFF, returns 0.  Bad arguments (a NULL ctx, tree, reps, moved or pairs, count
+ * == 0, n outside 2 ... 65535, a cutoff that is NaN or outside [0, 1]) and records that are not andi_hip_nj's return 1
+ * through the context's error, on the host before any HIP call.  Synchronous, on the context's stream. */
+int andi_hip_nj_transfer_taxa(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, const andi_hip_nj_join *reps, size_t n,
+							  size_t count, const uint8_t *skip, double cutoff, uint64_t *moved, uint64_t *pairs,
+							  uint32_t *match, uint32_t *dist);
 
 /* Agglomerative (linkage) clustering of the n x n distance matrix D (host memory, row-major) on the context's device:
  * single, complete or average linkage (UPGMA, the other mode of PHYLIP's neighbor).  Unlike neighbor-joining it takes a
