@@ -15,16 +15,28 @@ constexpr uint32_t COOP_TRIAL_LCP = 16;  // routed calls: a match followed throu
 constexpr uint32_t COOP_PARK = 16; // parked lanes (their probe needs lane_probe) that are served together
 constexpr uint32_t COOP_MAX_X = 3;  // anchors off the window's diagonal a walk follows before it gives up
 constexpr uint32_t NOPOS = 0xffffffffu;
+// Mode G where the block of probes has no answer for the chain's position: that position alone first, by one lane and COOP_SOLO_CAP symbols deep
+// (a unique match that reaches the cap is finished by coop_lcp; several that reach it: the block).  After COOP_SOLO_MAX such steps in a row
+// without an anchor the chain is in a stretch without homology, and the block of 64 probes takes over until the next anchor.
+// Neither changes a result.  Measured (profiles/r12_cold_start.md): caps of 32, 64 and 128 are level; with 2 steps in a row the bench set is
+// where it is with 1, and a routed call of 12 x 1 Mbp, whose pairs up to 6 % apart start most segments on a probe that finds no anchor, loses 5 %.
+#ifndef COOP_SOLO_CAP
+#define COOP_SOLO_CAP 64u
+#endif
+#ifndef COOP_SOLO_MAX
+#define COOP_SOLO_MAX 1u
+#endif
 
 // -DANDI_COOP_STATS: how the kernel's work splits (diagnostic builds only; ANDI_COOP_STATS=1 prints)
 #ifdef ANDI_COOP_STATS
-__device__ unsigned long long g_coop_stats[24];
+__device__ unsigned long long g_coop_stats[28];
 #define CSTAT(k, v)                                                              \
 	do {                                                                         \
 		if (__lane_id() == 0) atomicAdd(&g_coop_stats[k], (unsigned long long)(v)); \
 	} while (0)
 // wave-cycles (s_memtime) spent per phase: TICK(t) starts the clock, TOCK(t, phase) charges the time since to `phase`
-__device__ unsigned long long g_coop_cycles[8];
+// (slots 0 ... 6: the window's phases, 7: the segment's loop as a whole, 8 ...: mode G's parts and what lies around the loop)
+__device__ unsigned long long g_coop_cycles[16];
 #define TICK(t) unsigned long long t = __builtin_readcyclecounter()
 #define TOCK(t, ph)                                                                        \
 	do {                                                                                   \
@@ -41,9 +53,10 @@ __device__ unsigned long long g_coop_cycles[8];
 __device__ unsigned int g_coop_max[4];
 __device__ unsigned long long g_coop_trip_lanes[2][8]; // trips by lanes at work: 0, 1, 2-3, 4-7, 8-15, 16-31, 32-63, 64 (plain trips, service trips)
 #endif
-enum { PH_G, PH_STREAM, PH_HEADS, PH_WALKS, PH_HOPS, PH_STRETCH, PH_FINAL };
+enum { PH_G, PH_STREAM, PH_HEADS, PH_WALKS, PH_HOPS, PH_STRETCH, PH_FINAL, PH_LOOP, PH_G_LCP, PH_G_BLOCK, PH_G_SOLO, PH_G_SOLO_LCP, PH_G_NOTES, PH_PROLOGUE, PH_EPILOGUE };
 enum { CS_SEGMENTS, CS_G_STEPS, CS_BLOCKS, CS_LCP, CS_WINDOWS, CS_MOVED, CS_HEADS, CS_TRIPS, CS_LANE_STEPS, CS_PROBES, CS_ONPATH,
-	   CS_HOPS, CS_G_GAPS, CS_COVERED, CS_DROPPED, CS_X, CS_LCP_ROUNDS, CS_NODES, CS_SERVICE, CS_SERVICE_LANES, CS_WHY_PRE, CS_WHY_MULTI, CS_WHY_LONG, CS_WHY_OTHER };
+	   CS_HOPS, CS_G_GAPS, CS_COVERED, CS_DROPPED, CS_X, CS_LCP_ROUNDS, CS_NODES, CS_SERVICE, CS_SERVICE_LANES, CS_WHY_PRE, CS_WHY_MULTI, CS_WHY_LONG, CS_WHY_OTHER,
+	   CS_G_FIRST, CS_SOLO, CS_SOLO_LCP, CS_SOLO_BLOCK };
 
 // how a head's walk ended
 enum : uint32_t { W_OK = 1, W_OPEN = 2, W_EXIT = 3, W_BREAK = 4, W_STATUS = 7u, W_HADX = 8u, W_LUCKY = 16u, W_NX_SHIFT = 8, W_ONPATH = 1u << 12 };
@@ -137,6 +150,7 @@ struct Chain { // the chain of the wavefront: everything wave-uniform
 	uint32_t blk_base; // the block of probes in LDS answers positions blk_base ... blk_base + 63 (NOPOS: none)
 	uint32_t stuck;    // the last window ended at a head whose walk gave up (W_BREAK: the chain leaves the diagonal there): the next step is mode G's --
 					   // a window opened at that head again would stream, walk all its heads and not move (one such window per contig end, round 6)
+	uint32_t solo;     // mode G steps in a row that settled their position alone and found no anchor (COOP_SOLO_MAX)
 };
 
 // lcp(Q + p, S + s, maxlen) (src/process.c:59-65) with all lanes: 2048 symbols per round trip
@@ -624,55 +638,110 @@ __device__ __forceinline__ void coop_segment(const ScanArgs &a, LDS &L, uint32_t
 		if (lane == 0) __hip_atomic_store(route, (uint8_t)(__hip_atomic_load(route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) | ANDI_ROUTE_LEFT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	};
 	auto given_up = [&]() { return route && (uni(__hip_atomic_load(route, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & (ANDI_ROUTE_COOP | ANDI_ROUTE_LEFT)) != ANDI_ROUTE_COOP; };
+	TICK(tpro);
 	if (given_up()) return;
 	wave_sync();
 	if (lane < 16) L.hist[lane] = 0;
 	Chain ch;
 	ch.st = seg_in_q == 0 ? initial_state() : cold_state(start, n);
-	ch.quarter = ch.rest = ch.anchors = ch.marked = 0, ch.blk_base = NOPOS, ch.stuck = 0;
+	ch.quarter = ch.rest = ch.anchors = ch.marked = 0, ch.blk_base = NOPOS, ch.stuck = 0, ch.solo = 0;
 	ChainState &st = ch.st;
 	wave_sync();
 
 	CSTAT(CS_SEGMENTS, 1);
+	TOCK(tpro, PH_PROLOGUE);
 	TICK(tall);
 	uint32_t my_g = 0;
 	while (st.p < end) {
 		CSTAT(CS_G_STEPS, 1);
+		CSTAT(CS_G_FIRST, my_g == 0);
 		++my_g;
 		if (route) {
 			if (my_g > a.route_giveup + (a.seg >> 12)) return give_up(); // (a few more per window the segment holds)
 			if (given_up()) return;
 		}
 		// ---- one step of mode G (src/process.c:153-197)
+		TICK(tg);
 		bool found = false, lucky = false;
 		uint32_t curS = 0, curLen = 0;
-		if (lucky_applies(st, n, thr)) {
-			curS = st.lastS + (st.p - st.lastQ);
-			curLen = coop_lcp(c, st.p, curS, c.qlen - st.p, route ? COOP_TRIAL_LCP : ~0u);
-			if (curLen == NOPOS) return give_up();
-			found = lucky = curLen >= thr;
-		}
-		if (!found) {
-			if (ch.blk_base == NOPOS || st.p < ch.blk_base || st.p - ch.blk_base >= 64) { // the next 64 positions' answers at once
-				const uint32_t p = st.p + lane;
-				CSTAT(CS_BLOCKS, 1);
+		// The step follows at most one diagonal with all lanes (tryS: where st.p lies on it; NOPOS: none) -- the last anchor's (lucky_anchor),
+		// or that of the one occurrence a probe of st.p alone found (`probed`).  Without an answer for st.p in the block, st.p alone comes first
+		// (COOP_SOLO_CAP symbols deep, as k_lane_cold's own probe, scan_lane.hip; every lane takes the same probe, which costs the wavefront what
+		// one lane's would and needs no mask of its own -- with lane 0 alone k_coop_cold<5, false> spilled one register more): at a segment's
+		// start in homologous sequence the answer is a unique long match, and the chain jumps past what the probes of the 63 positions
+		// behind it would have found, each followed to its end -- the wavefront executes the union of what its lanes do.  The 64
+		// probes of the next 64 positions at once (the chain then hops through the answers) where that is of no use: several occurrences match
+		// as far as the cap, or the last COOP_SOLO_MAX such steps found no anchor.  ONE place where the wavefront follows a diagonal and ONE
+		// where it probes, whichever way the step takes.
+		// The loop's trips, two at the most -- a trip ends the step (break) or says what the next one does (continue):
+		//   1. the lucky attempt, if one applies (tryS); an anchor ends the step.  Else the probe: from the block if it answers st.p; of st.p alone
+		//      (`alone`), which ends the step unless its match reaches the cap; or the block of 64 made now, which ends it.
+		//   2. behind a probe of st.p alone that reached the cap -- one occurrence did: tryS is its diagonal, coop_lcp follows it and ends the step
+		//      (`probed`); several did: `alone` is off, and the trip makes the block and ends the step.
+		// (Every lane of a probe of st.p alone runs lane_probe whole, sa_range_match included: a separator inside the K-mer, fewer than K symbols
+		// left of the query and K-mers with more than MULTI_MAX occurrences are not held back for the block -- a capped probe is exact below the
+		// cap whichever way lane_probe takes, and such steps are rare; profiles/r12_cold_start.md.)
+		uint32_t tryS = lucky_applies(st, n, thr) ? st.lastS + (st.p - st.lastQ) : NOPOS;
+		bool probed = false, alone = ch.solo < COOP_SOLO_MAX; // alone: this step may probe st.p by itself (ch.solo counts such steps in a row)
+		for (;;) {
+			if (tryS != NOPOS) {
+				curS = tryS;
+				curLen = coop_lcp(c, st.p, curS, c.qlen - st.p, route ? COOP_TRIAL_LCP : ~0u);
+				if (curLen == NOPOS) return give_up();
+				found = curLen >= thr;
+				if (probed) {
+					TOCK(tg, PH_G_SOLO_LCP);
+					break; // the probe's one occurrence, followed to its end
+				}
+				TOCK(tg, PH_G_LCP);
+				lucky = found;
+				if (found) break;
+				tryS = NOPOS;
+			}
+			const bool answered = ch.blk_base != NOPOS && st.p >= ch.blk_base && st.p - ch.blk_base < 64;
+			if (answered) alone = false;
+			if (!answered) {
+				const uint32_t p = st.p + (alone ? 0u : lane);
 				Probe pr;
 				pr.len = 0, pr.pos = 0, pr.unique = false;
 				if (p < c.qlen) {
 					LWin w;
 					w.q0 = EMPTY, w.dg = NO_DIAG;
-					pr = lane_probe(c, p, w);
+					pr = lane_probe(c, p, w, alone ? COOP_SOLO_CAP : ~0u);
 				}
+				if (alone) {
+					CSTAT(CS_SOLO, 1);
+					++ch.solo;
+					curLen = uni(pr.len), curS = uni(pr.pos);
+					const bool uq = uni(pr.unique ? 1u : 0u) != 0;
+					TOCK(tg, PH_G_SOLO);
+					if (curLen >= COOP_SOLO_CAP && COOP_SOLO_CAP < c.qlen - st.p) {
+						if (uq) { // the one occurrence that matches that far: its match to its end, with all lanes
+							CSTAT(CS_SOLO_LCP, 1);
+							tryS = curS, probed = true;
+						} else { // several do: the whole answer is the block's
+							CSTAT(CS_SOLO_BLOCK, 1);
+							alone = false;
+						}
+						continue;
+					}
+					found = uq && curLen >= thr;
+					break;
+				}
+				CSTAT(CS_BLOCKS, 1); // the next 64 positions' answers at once
 				wave_sync();
 				L.pl[lane] = pr.len | (pr.unique ? 0x80000000u : 0u), L.pp[lane] = pr.pos;
 				ch.blk_base = st.p;
 				wave_sync();
+				TOCK(tg, PH_G_BLOCK);
 			}
 			const uint32_t v = uni(L.pl[st.p - ch.blk_base]);
 			curLen = v & 0x7fffffffu, curS = uni(L.pp[st.p - ch.blk_base]);
 			found = (v >> 31) && curLen >= thr;
+			break;
 		}
 		if (found) {
+			ch.solo = 0;
 			coop_account<EXACT>(c, ch, L, curS);
 			st.lastS = curS, st.lastQ = st.p, st.lastLen = curLen;
 		}
@@ -681,6 +750,7 @@ __device__ __forceinline__ void coop_segment(const ScanArgs &a, LDS &L, uint32_t
 			wave_sync();
 			coop_note_anchor(a, slot_of(), ch, L);
 		}
+		TOCK(tg, PH_G_NOTES);
 		// ---- windows one after the other while the chain stays canonical on the diagonal and moves
 		if (found && lucky) {
 			win.begin(ch);
@@ -691,7 +761,8 @@ __device__ __forceinline__ void coop_segment(const ScanArgs &a, LDS &L, uint32_t
 		}
 	}
 
-	TOCK(tall, 7);
+	TOCK(tall, PH_LOOP);
+	TICK(tepi);
 	wave_sync();
 #ifdef ANDI_COOP_STATS
 	if (lane == 0) atomicMax(&g_coop_max[0], my_g);
@@ -714,6 +785,7 @@ __device__ __forceinline__ void coop_segment(const ScanArgs &a, LDS &L, uint32_t
 		if constexpr (Windows::COUNTS_EQUAL) v += lane == 0 ? win.same[0] : lane == 5 ? win.same[1] : lane == 10 ? win.same[2] : lane == 15 ? win.same[3] : 0u;
 		a.cold_counts[slot * 16 + lane] = v;
 	}
+	TOCK(tepi, PH_EPILOGUE);
 }
 
 } // namespace

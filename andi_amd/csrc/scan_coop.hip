@@ -152,13 +152,14 @@ hipError_t andi_launch_coop_cold(const ScanArgs &a, hipStream_t st) { // one seg
 	}
 #ifdef ANDI_COOP_STATS
 	if (andi_knob(KNOB_COOP_STATS)) {
-		static const char *names[24] = {"segments", "G steps", "probe blocks", "coop_lcp calls", "windows", "windows that moved", "heads", "walk trips",
+		static const char *names[28] = {"segments", "G steps", "probe blocks", "coop_lcp calls", "windows", "windows that moved", "heads", "walk trips",
 										"walk lane-steps", "walk probes", "heads on the path", "hops", "gaps counted in G", "positions covered by windows",
-										"heads dropped", "walks with anchors off the diagonal", "coop_lcp rounds", "nodes", "service trips (lane_probe)", "lanes served", "parked: window edge / separators / plain table", "parked: K-mer occurs several times", "parked: long match off the diagonal", "parked: other"};
-		unsigned long long h[24];
+										"heads dropped", "walks with anchors off the diagonal", "coop_lcp rounds", "nodes", "service trips (lane_probe)", "lanes served", "parked: window edge / separators / plain table", "parked: K-mer occurs several times", "parked: long match off the diagonal", "parked: other",
+										"G steps that are their segment's first", "G steps settled by one lane", "... finished by coop_lcp", "... handed to the block (not unique at the cap)"};
+		unsigned long long h[28];
 		(void)hipStreamSynchronize(st);
 		(void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_coop_stats), sizeof h);
-		for (int k = 0; k < 24; ++k) fprintf(stderr, "coop_stats %-36s %llu\n", names[k], h[k]);
+		for (int k = 0; k < 28; ++k) fprintf(stderr, "coop_stats %-36s %llu\n", names[k], h[k]);
 		memset(h, 0, sizeof h);
 		(void)hipMemcpyToSymbol(HIP_SYMBOL(g_coop_stats), h, sizeof h);
 		unsigned long long tl[2][8];
@@ -172,13 +173,18 @@ hipError_t andi_launch_coop_cold(const ScanArgs &a, hipStream_t st) { // one seg
 		fprintf(stderr, "coop_stats most G steps of a segment          %u\n", mx[0]);
 		memset(mx, 0, sizeof mx);
 		(void)hipMemcpyToSymbol(HIP_SYMBOL(g_coop_max), mx, sizeof mx);
-		unsigned long long cy[8];
+		unsigned long long cy[16];
 		(void)hipMemcpyFromSymbol(cy, HIP_SYMBOL(g_coop_cycles), sizeof cy);
 		static const char *ph[7] = {"(mode G: the rest)", "window: bits", "window: heads", "window: walks", "window: hops", "window: stretches", "window: counting"};
 		unsigned long long in_w = 0;
 		for (int k = 1; k < 7; ++k) in_w += cy[k];
-		for (int k = 1; k < 7; ++k) fprintf(stderr, "coop_cycles %-24s %6.2f %%\n", ph[k], 100.0 * (double)cy[k] / (double)cy[7]);
-		fprintf(stderr, "coop_cycles %-24s %6.2f %%\n", ph[0], 100.0 * (double)(cy[7] - in_w) / (double)cy[7]);
+		for (int k = 1; k < 7; ++k) fprintf(stderr, "coop_cycles %-24s %6.2f %%\n", ph[k], 100.0 * (double)cy[k] / (double)cy[PH_LOOP]);
+		fprintf(stderr, "coop_cycles %-24s %6.2f %%\n", ph[0], 100.0 * (double)(cy[PH_LOOP] - in_w) / (double)cy[PH_LOOP]);
+		// mode G's parts, and what a segment costs around its loop (all as shares of the loop's cycles; what is left of "the rest": the
+		// loop's own tests, the routed call's look at the pair's mark, win.begin and the test between two windows)
+		static const char *gp[7] = {"G: coop_lcp (lucky)", "G: block of 64 probes", "G: one lane's probe", "G: its coop_lcp", "G: accounting, notes", "segment: prologue", "segment: epilogue"};
+		for (int k = 0; k < 7; ++k) fprintf(stderr, "coop_cycles %-24s %6.2f %%\n", gp[k], 100.0 * (double)cy[PH_G_LCP + k] / (double)cy[PH_LOOP]);
+		fprintf(stderr, "coop_cycles %-24s %.4f G (100 %%; shares of two builds compare through this)\n", "the segments' loops", 1e-9 * (double)cy[PH_LOOP]);
 		memset(cy, 0, sizeof cy);
 		(void)hipMemcpyToSymbol(HIP_SYMBOL(g_coop_cycles), cy, sizeof cy);
 	}
