@@ -814,6 +814,35 @@ extern "C" int andi_hip_test_coop_items(andi_hip_ctx *ctx, uint32_t *items, size
 	if (pair_cost && l.pair_cost && np) HIP_TRY(ctx, hipMemcpy(pair_cost, l.pair_cost, np, hipMemcpyDeviceToHost));
 	return 0;
 }
+// The per-slot records of the context's last scan call that used ONE segment length (not routed, no per-pair lengths), as they lie in lane
+// layout a of the call's scratch after the call: pass A's cold_exit, cold_counts and marks, pass B's used_entry, true_exit and owned (pass C
+// only reads them: after the call they are pass B's result), `slots` slots of each at most, and the 16 words of restitch_count.
+// info = { subjects, segments per subject, segment length, 1 if such a call is on record }.  The slot of segment k of query q under subject s
+// is s * total_segs + qseg_start[q] + k, qseg_start the running sum of ceil(qlen / seg) over the queries; the slots of a subject's own query
+// are not written.  Any pointer may be NULL; with arrays asked for and no call on record it is an error (nothing stale is handed out).
+extern "C" int andi_hip_test_stitch_slots(andi_hip_ctx *ctx, ChainState *cold_exit, ChainState *true_exit, ChainState *used_entry, uint32_t *cold_counts,
+										  uint32_t *owned, ColdMark *marks, size_t slots, uint32_t *restitch_count, uint32_t *info) {
+	if (!ctx) return 1;
+	const auto &l = ctx->last_slots;
+	const bool have = l.cold_exit != nullptr;
+	if (info) info[0] = l.nsub, info[1] = l.total_segs, info[2] = l.seg, info[3] = have ? 1u : 0u;
+	const bool wants = cold_exit || true_exit || used_entry || cold_counts || owned || marks || restitch_count;
+	if (!wants) return 0;
+	if (!have || slots > (size_t)l.nsub * l.total_segs) {
+		ctx->err = have ? "andi_hip_test_stitch_slots: more slots than the call had" : "andi_hip_test_stitch_slots: no scan call with one segment length on record";
+		return 1;
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (cold_exit && slots) HIP_TRY(ctx, hipMemcpy(cold_exit, l.cold_exit, slots * sizeof(ChainState), hipMemcpyDeviceToHost));
+	if (true_exit && slots) HIP_TRY(ctx, hipMemcpy(true_exit, l.true_exit, slots * sizeof(ChainState), hipMemcpyDeviceToHost));
+	if (used_entry && slots) HIP_TRY(ctx, hipMemcpy(used_entry, l.used_entry, slots * sizeof(ChainState), hipMemcpyDeviceToHost));
+	if (cold_counts && slots) HIP_TRY(ctx, hipMemcpy(cold_counts, l.cold_counts, slots * 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (owned && slots) HIP_TRY(ctx, hipMemcpy(owned, l.owned, slots * 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (marks && slots) HIP_TRY(ctx, hipMemcpy(marks, l.marks, slots * ANDI_COLD_MARKS * sizeof(ColdMark), hipMemcpyDeviceToHost));
+	if (restitch_count) HIP_TRY(ctx, hipMemcpy(restitch_count, l.restitch_count, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
 // The index build's pack kernel alone on a staged subject (no table: the text may be any bytes); forms: bit 0 with N1, bit 1 with P
 extern "C" int andi_hip_test_pack_text(andi_hip_ctx *ctx, andi_hip_esa *e, int forms) {
 	if (!ctx || !e) return 1;

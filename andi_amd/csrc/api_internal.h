@@ -77,6 +77,18 @@ struct andi_hip_ctx {
 	unsigned long long *d_route = nullptr; // routed scan calls: query nucleotides whose pass A ran by wavefronts / by lanes, pairs handed back (read with the timings)
 	std::vector<EventPair> pending;
 	andi_hip_timings acc{};
+#ifdef ANDI_TEST_HOOKS
+	// (the suite's library only: every translation unit that sees this struct is compiled a second time for it, Makefile: HOOKOBJ)
+	// the last scan call that used ONE segment length (not routed, no per-pair lengths): the per-slot arrays of lane layout a in the call's
+	// scratch and their geometry -- what the suite's hook andi_hip_test_stitch_slots reads.  Cleared at every call's start, so by a call that
+	// takes another path and before the scratch is regrown; the scratch is freed only with the context.
+	struct {
+		const ChainState *cold_exit = nullptr, *true_exit = nullptr, *used_entry = nullptr;
+		const uint32_t *cold_counts = nullptr, *owned = nullptr, *restitch_count = nullptr;
+		const ColdMark *marks = nullptr;
+		uint32_t nsub = 0, total_segs = 0, seg = 0;
+	} last_slots;
+#endif
 };
 
 struct andi_hip_esa {

@@ -398,6 +398,13 @@ hipError_t launch_direct(andi_hip_ctx *ctx, ScanArgs &a, const char *&what) {
 	if (e == hipSuccess) e = andi_launch_scan_reduce(a, ctx->stream);
 	t.stop();
 	if (e != hipSuccess) what = "scan passes B/C";
+#ifdef ANDI_TEST_HOOKS
+	if (e == hipSuccess && !a.adaptive) { // one segment length: the slots the suite's hook hands out (api.hip: andi_hip_test_stitch_slots)
+		auto &l = ctx->last_slots;
+		l.cold_exit = a.cold_exit, l.true_exit = a.true_exit, l.used_entry = a.used_entry, l.cold_counts = a.cold_counts, l.owned = a.owned;
+		l.marks = a.marks, l.restitch_count = a.restitch_count, l.nsub = a.nsub, l.total_segs = a.total_segs, l.seg = a.seg;
+	}
+#endif
 	return e;
 }
 
@@ -527,6 +534,9 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 	if (!ctx->coop_stream) HIP_TRY(ctx, host_pool::stream_get(&ctx->coop_stream, ctx->device, 0));
 
 	ctx->last_items = {}; // (what the test hook reads points into this call's scratch: nothing of an earlier call's outlives it)
+#ifdef ANDI_TEST_HOOKS
+	ctx->last_slots = {}; // (likewise: before the scratch may be regrown, and for a call that is routed or takes per-pair lengths)
+#endif
 	ScanPlan P = plan_call(subjects, nsub, q, model, segment);
 	if (ensure_segmentation(ctx, q, P.segment)) return 1;
 	int any_reference = 0;

@@ -185,6 +185,7 @@ HOOK_SYMBOLS = {
     "andi_hip_test_pack_text": (C.c_int, [_P, _P, C.c_int]),
     "andi_hip_test_coop_items": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "andi_hip_test_query_codes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
+    "andi_hip_test_stitch_slots": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
 }
 
 _lib = None
@@ -600,6 +601,27 @@ class Context:
         items, cls, cost = np.zeros(int(info[0]), np.uint32), np.zeros(int(info[1]), np.uint8), np.zeros(int(info[1]), np.uint8)
         self._check(hook(self._h, items.ctypes.data, len(items), cls.ctypes.data, cost.ctypes.data, len(cls), info.ctypes.data), "test_coop_items")
         return (items if info[3] else None), cls, cost, int(info[2])
+
+    def stitch_slots(self):
+        """(a test hook) the per-slot records of the last scan call that used one segment length (not routed, no per-pair lengths),
+        as passes A and B left them in the call's scratch: a dict of uint32 arrays -- cold_exit, true_exit, used_entry (slots, 8:
+        p, lastS, lastQ, lastLen, lwra, pad[3]), cold_counts, owned (slots, 16), marks (slots, 28: the mark's state, its 16 counts,
+        the first anchor's pos_Q, pos_S, length, 0), restitch_count (16) -- and nsub, total_segs, seg.  The slot of segment k of
+        query q under subject s is s * total_segs + qseg_start[q] + k, qseg_start the running sum of ceil(qlen / seg)."""
+        hook = _hook("andi_hip_test_stitch_slots")
+        info = np.zeros(4, np.uint32)
+        self._check(hook(self._h, None, None, None, None, None, None, 0, None, info.ctypes.data), "test_stitch_slots")
+        if not info[3]:
+            raise AndiHipError("test_stitch_slots: no scan call with one segment length on record")
+        n = int(info[0]) * int(info[1])
+        out = {"cold_exit": np.zeros((n, 8), np.uint32), "true_exit": np.zeros((n, 8), np.uint32), "used_entry": np.zeros((n, 8), np.uint32),
+               "cold_counts": np.zeros((n, 16), np.uint32), "owned": np.zeros((n, 16), np.uint32), "marks": np.zeros((n, 28), np.uint32),
+               "restitch_count": np.zeros(16, np.uint32)}
+        p = {k: v.ctypes.data for k, v in out.items()}
+        self._check(hook(self._h, p["cold_exit"], p["true_exit"], p["used_entry"], p["cold_counts"], p["owned"], p["marks"], n,
+                         p["restitch_count"], info.ctypes.data), "test_stitch_slots")
+        out.update(nsub=int(info[0]), total_segs=int(info[1]), seg=int(info[2]))
+        return out
 
     def alloc(self, nbytes):
         p = _P()

@@ -26,8 +26,11 @@ from oracle import orc
 
 
 class Pair:
-    def __init__(self, subject: bytes, query: bytes, p_value=0.025):
-        self.E = orc.OracleEsa(subject, p_value)
+    def __init__(self, subject: bytes, query: bytes, p_value=0.025, esa=None, exact=False):
+        """esa: the subject's OracleEsa if the caller keeps one; exact: LogDet/ANI, an anchor's equal run is counted
+        symbol by symbol (count_anchor)"""
+        self.E = esa if esa is not None else orc.OracleEsa(subject, p_value)
+        self.exact = exact
         self.q = query
         self.qlen = len(query)
         self.n = self.E.n
@@ -80,6 +83,19 @@ def count_equal(counts, ln):
     counts[15] += (ln >> 2) + (ln & 3)
 
 
+def count_anchor(P, counts, q, ln):
+    """model_count_equal (src/model.c:246-279) of the anchor query[q, q + ln): the even split, or -- LogDet, ANI
+    (P.exact) -- every nucleotide by itself, symbols below 'A' skipped"""
+    if not P.exact:
+        return count_equal(counts, ln)
+    a = P.Q[q:q + ln]
+    b = np.bincount((a[a >= 65] >> 1) & 3, minlength=4)  # A 0, C 1, T 2, G 3 (src/model.c:270-272)
+    counts[0] += int(b[0])
+    counts[5] += int(b[1])
+    counts[10] += int(b[3])
+    counts[15] += int(b[2])
+
+
 class State:
     __slots__ = ("p", "lastS", "lastQ", "lastLen", "lwra")
 
@@ -128,12 +144,12 @@ def account(P, st, rec, curS):
     """src/process.c:157-190, before last_match = this_match"""
     endS, endQ = st.lastS + st.lastLen, st.lastQ + st.lastLen
     if curS > endS and st.p - endQ == curS - endS and (curS < P.border) == (st.lastS < P.border):
-        count_equal(rec.counts, st.lastLen)
+        count_anchor(P, rec.counts, st.lastQ, st.lastLen)
         P.count_gap(rec.counts, endQ, endS, st.p - endQ)
         st.lwra = 1
     else:
         if st.lwra or st.lastLen >= 2 * P.thr:
-            count_equal(rec.counts, st.lastLen)
+            count_anchor(P, rec.counts, st.lastQ, st.lastLen)
         st.lwra = 0
 
 
