@@ -366,8 +366,10 @@ __device__ __forceinline__ uint32_t first_code(bool has, uint32_t L, int K) {
 	return has ? c : 0u;
 }
 
-__device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0, const int32_t *__restrict__ SA,
-												  const uint32_t *__restrict__ REC, const uint16_t *__restrict__ REC2, uint2 *__restrict__ deep,
+// (the arrays through the global address space, as the scans address the index: k_probe_table_batch reads its pointers from memory, and
+// what the compiler cannot prove global becomes flat_load and flat_store, which every wait for LDS waits for as well)
+__device__ __forceinline__ void probe_table_block(g_u8p __restrict__ N0, g_i32p __restrict__ SA,
+												  g_u32p __restrict__ REC, g_u16p __restrict__ REC2, ANDI_GLOBAL uint2 *__restrict__ deep,
 												  int32_t *__restrict__ flags, int32_t n, int K, int single_ext, uint32_t block) {
 	__shared__ uint32_t s_first[PT_TILE];   // first code a gap owns (one that owns nothing: its successor's)
 	__shared__ uint32_t s_absent[PT_TILE];  // number of absent codes it owns (they come first)
@@ -382,8 +384,9 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 	const uint32_t r0 = block * PT_TILE; // (n < 2^31: gaps and suffixes in 32 bits)
 	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 	// the suffixes' records: read in order if the device sorter left them (REC), else made here from one gather each
-	auto make_rec = [&](int32_t j) { return REC ? REC[j] : suffix_rec(N0, SA, j, K); };
+	auto make_rec = [&](int32_t j) { return REC ? REC[j] : suffix_rec((const uint8_t *)N0, (const int32_t *)SA, j, K); };
 	uint32_t mine2[PT_GAPS]; // the short extended form: what the sorter's keys held behind this thread's suffixes' K-mers (read with the records)
+	uint32_t not_whole = 0;  // bits 5..0: a record this thread staged is not "K nucleotides, nothing behind them" (see `whole` below)
 	{
 		uint32_t mine[PT_GAPS];
 #pragma unroll
@@ -393,12 +396,33 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 			mine2[u] = (single_ext == 2 && REC2 && g < (uint32_t)n) ? REC2[g] : 0u;
 		}
 #pragma unroll
-		for (int u = 0; u < PT_GAPS; ++u) s_rec[threadIdx.x + u * PT_BLOCK + 2] = mine[u];
+		for (int u = 0; u < PT_GAPS; ++u) s_rec[threadIdx.x + u * PT_BLOCK + 2] = mine[u], not_whole |= mine[u] ^ (uint32_t)K;
 	}
-	if (threadIdx.x < 2) s_rec[threadIdx.x] = r0 + threadIdx.x >= 2 ? make_rec((int32_t)(r0 + threadIdx.x - 2)) : 0u;
-	if (threadIdx.x == 2) s_rec[PT_TILE + 2] = r0 + PT_TILE < (uint32_t)n ? make_rec((int32_t)(r0 + PT_TILE)) : 0u;
+	if (threadIdx.x < 3) { // the halo: the records of the suffixes r0 - 2, r0 - 1 and r0 + PT_TILE
+		const uint32_t halo = threadIdx.x < 2 ? (r0 + threadIdx.x >= 2 ? make_rec((int32_t)(r0 + threadIdx.x - 2)) : 0u)
+		                                      : (r0 + PT_TILE < (uint32_t)n ? make_rec((int32_t)(r0 + PT_TILE)) : 0u);
+		s_rec[threadIdx.x < 2 ? threadIdx.x : PT_TILE + 2] = halo, not_whole |= halo ^ (uint32_t)K;
+	}
 	if (threadIdx.x < PT_RANKED / 32) s_bits[threadIdx.x] = 0;
+	// A tile is WHOLE when it lies inside the text (r0 >= 2, r0 + PT_TILE < n) and every record it stages, the halo
+	// included, is a full K-mer with no separator class: code << 6 | K.  Then every gap has both neighbours, comparing
+	// records is comparing codes, and (c) has nothing to find: the gap phase and the entries below run as straight-line
+	// code.  On a genome that is every tile but the few with a suffix that starts within K characters of a contig's or the
+	// text's end; those, the text's first and last tile, and tables shallower than their records take the general code.
+	// The verdict rides on the barrier that is here anyway: a word per wavefront in s_owner, which nothing else uses
+	// before the next barrier.
+	{
+		const uint64_t some_not = __ballot((not_whole & 63u) != 0);
+		if (lane == 0) s_owner[wave] = (uint16_t)(some_not != 0);
+	}
 	__syncthreads();
+	bool whole;
+	{
+		uint32_t v = r0 >= 2 && r0 + PT_TILE < (uint32_t)n ? 0u : 1u;
+#pragma unroll
+		for (int w = 0; w < PT_BLOCK / 64; ++w) v |= s_owner[w];
+		whole = __builtin_amdgcn_readfirstlane((int)v) == 0; // (block-uniform: a scalar branch)
+	}
 	auto rec = [&](int32_t j) { // 0 <= j < n; inside the block's range from LDS
 		const uint32_t k = (uint32_t)j - r0 + 2; // (j >= r0 - 2 wraps to a small number; anything else to a large one)
 		return k < PT_TILE + 3 ? s_rec[k] : make_rec(j);
@@ -408,6 +432,64 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 	if (threadIdx.x == 1) s_h[PT_TILE + 1] = (uint8_t)(r0 + PT_TILE < (uint32_t)n ? rec_lcp(s_rec[PT_TILE + 1], s_rec[PT_TILE + 2], K) : 0u);
 
 	uint32_t counts[PT_GAPS], firsts[PT_GAPS];
+	// The gaps of a whole tile (the general code's (a) and (b) with live, hasL, hasR true, every REC_V == K and every
+	// REC_SEP == 0; (c) looks at nothing when no record has a separator class).  Records differ in their codes alone, so
+	// R - L >> 6 is the distance of the codes: what the gap owns, its suffix's K-mer last.
+	auto gaps_whole = [&]() {
+		uint32_t sa[PT_GAPS]; // (the suffixes' positions: the loads of all gaps in flight together, used below without a branch around them)
+#pragma unroll
+		for (int u = 0; u < PT_GAPS; ++u) sa[u] = (uint32_t)SA[r0 + threadIdx.x + u * PT_BLOCK];
+#pragma unroll
+		for (int u = 0; u < PT_GAPS; ++u) {
+			const uint32_t i = threadIdx.x + u * PT_BLOCK; // gap r0 + i
+			const int32_t r = (int32_t)(r0 + i);
+			const uint32_t L = s_rec[i + 1], R = s_rec[i + 2], a1 = s_rec[i + 3], a2 = s_rec[i + 4], a3 = s_rec[i + 5];
+			const uint32_t same = ((uint32_t)__clz((int)(L ^ R)) >> 1) - (13u - full); // (L == R: 32 leading zeros, K + 3)
+			s_h[i + 1] = (uint8_t)(same < full ? same : full);
+			const uint32_t owned = (R - L) >> 6, first = REC_CODE(L) + 1u;
+			// the run that suffix r starts, if it starts one (as in the general code below: three records ahead, then a short walk, then binary search)
+			const bool in_tile = i + 5 < PT_TILE + 3;
+			const int32_t m = a1 != R ? 0 : (a2 != R ? 1 : (a3 != R ? 2 : 3));
+			int32_t j = in_tile ? r + m : r;
+			if (owned != 0 && (!in_tile || m == 3)) {
+				while (j + 1 < n && j - r < 16 && rec(j + 1) == R) ++j;
+				if (j - r == 16 && j + 1 < n && rec(j + 1) == R) {
+					int32_t lo = j + 1, hi = n - 1;
+					while (lo < hi) {
+						const int32_t mid = lo + ((hi - lo + 1) >> 1);
+						if (rec(mid) == R) lo = mid; else hi = mid - 1;
+					}
+					j = lo;
+				}
+			}
+			const bool fits = (uint32_t)(j - r) < (1u << 24);
+			const uint2 multi = make_uint2(fits ? (uint32_t)r : 0u, fits ? DEEP_MULTI | ((uint32_t)(j - r) << 8) : (uint32_t)DEEP_SEARCH);
+			uint32_t single = DEEP_SINGLE | (1u << 2) | (full << 8);
+			if (single_ext == 2 && REC2) {
+				single = DEEP_SINGLE | ((mine2[u] >> 8) << 2) | ((mine2[u] & 0xffu) << 6);
+			} else if (single_ext == 1 && owned != 0 && j == r) {
+				const uint32_t e0 = sa[u] + full;
+				const uint64_t w = ld_u64_unaligned((g_u8p)N0 + (e0 >> 1)) >> (4 * (e0 & 1u)); // 15 symbols from e0 on
+				const uint32_t nval = (uint32_t)__builtin_ctzll((w & 0x4444444444444444ull) | (1ull << 52)) >> 2; // <= 13
+				auto squeeze = [](uint32_t x) { // 8 nibbles -> 8 x 2 bits, first symbol in the low bits
+					x &= 0x33333333u;
+					x = (x | (x >> 2)) & 0x0f0f0f0fu;
+					x = (x | (x >> 4)) & 0x00ff00ffu;
+					x = (x | (x >> 8)) & 0x0000ffffu;
+					return x;
+				};
+				const uint32_t ext = (squeeze((uint32_t)w) | (squeeze((uint32_t)(w >> 32)) << 16)) & ((1u << (2 * nval)) - 1u);
+				single = DEEP_SINGLE | (nval << 2) | (ext << 6);
+			}
+			const uint2 present = owned == 0 ? make_uint2(0, 0) : (j != r ? multi : make_uint2(sa[u], single));
+			s_first[i] = first, s_absent[i] = owned - (owned != 0 ? 1u : 0u), s_present[i] = present;
+			counts[u] = owned, firsts[u] = first;
+			const uint64_t b = __ballot(owned != 0);
+			if (lane == 0) s_some[u * (PT_BLOCK / 64) + wave] = b;
+		}
+	};
+	if (whole) gaps_whole();
+	else
 #pragma unroll
 	for (int u = 0; u < PT_GAPS; ++u) {
 		const uint32_t i = threadIdx.x + u * PT_BLOCK; // gap r0 + i
@@ -564,6 +646,30 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 	};
 	// (two loops: the ranked entries -- all of them, as a rule -- in one without the binary search's branch and inner loop)
 	const uint32_t ranked = total < PT_RANKED ? total : PT_RANKED;
+	// an entry of a whole tile (the ranked ones and, behind the binary search, the others): both neighbours exist and are full K-mers, so the characters a code shares with
+	// one are the leading zeros of the xor alone (an absent code differs from both; for the suffix's own K-mer the value
+	// is not used), no suffix index leaves the text, and n > 1.  (c << 6) ^ record keeps the record's shift: six
+	// leading zeros fewer, three off both lengths, so 13 - K comes off in place of 16 - K.
+	auto write_entry_whole = [&](uint32_t t, uint32_t a) {
+		const uint32_t c = base + t;
+		const bool is_present = c - s_first[a] >= s_absent[a];
+		const uint2 pres = s_present[a];
+		const uint32_t rr = r0 + a;
+		const uint32_t gl = s_rec[a + 1], gr = s_rec[a + 2], hll = s_h[a], hrr = s_h[a + 2];
+		const uint32_t pL = (uint32_t)__builtin_clz((c << 6) ^ gl) >> 1, pR = (uint32_t)__builtin_clz((c << 6) ^ gr) >> 1; // (never 0: the records' low bits are K)
+		const bool left = pL > pR, right = pR > pL;
+		const uint32_t l = (left ? pL : pR) - (13u - full);
+		const uint32_t idx = left ? rr - 1 : (right ? rr : 0u);
+		const uint32_t uniq = (left || right) && (left ? hll : hrr) < l ? 1u : 0u;
+		const uint2 val = is_present ? pres : make_uint2(idx, DEEP_FINAL | (uniq << 2) | (l << 8));
+		__builtin_nontemporal_store(((unsigned long long)val.y << 32) | val.x, (unsigned long long *)(deep + c));
+	};
+	if (whole) {
+		for (uint32_t t = threadIdx.x; t < ranked; t += PT_BLOCK) {
+			const uint32_t word = t >> 5;
+			write_entry_whole(t, s_owner[s_before[word] + (uint32_t)__builtin_popcount(s_bits[word] & (0xffffffffu >> (31u - (t & 31u)))) - 1u]);
+		}
+	} else
 	for (uint32_t t = threadIdx.x; t < ranked; t += PT_BLOCK) {
 		const uint32_t word = t >> 5;
 		write_entry(t, s_owner[s_before[word] + (uint32_t)__builtin_popcount(s_bits[word] & (0xffffffffu >> (31u - (t & 31u)))) - 1u]);
@@ -576,21 +682,21 @@ __device__ __forceinline__ void probe_table_block(const uint8_t *__restrict__ N0
 			const uint32_t mid = (a + b) >> 1;
 			if (s_first[mid] <= c) a = mid; else b = mid;
 		}
-		write_entry(t, a);
+		if (whole) write_entry_whole(t, a); else write_entry(t, a);
 	}
 }
 
 __global__ __launch_bounds__(PT_BLOCK) void k_probe_table(const uint8_t *__restrict__ N0, const int32_t *__restrict__ SA,
 														  const uint32_t *__restrict__ rec, const uint16_t *__restrict__ rec2, uint2 *__restrict__ deep,
 														  int32_t *__restrict__ flags, int32_t n, int K, int single_ext) {
-	probe_table_block(N0, SA, rec, rec2, deep, flags, n, K, single_ext, blockIdx.x);
+	probe_table_block((g_u8p)N0, (g_i32p)SA, (g_u32p)rec, (g_u16p)rec2, (ANDI_GLOBAL uint2 *)deep, flags, n, K, single_ext, blockIdx.x);
 }
 
 // the tables of several subjects in one launch (blockIdx.y = subject): no launch gaps, one tail
 __global__ __launch_bounds__(PT_BLOCK) void k_probe_table_batch(const AndiIndexBatchItem *__restrict__ items) {
 	const AndiIndexBatchItem it = items[blockIdx.y];
 	if ((uint64_t)blockIdx.x * PT_TILE > (uint64_t)it.n) return;
-	probe_table_block(it.N0, it.SA, it.rec, it.rec2, it.deep, it.flags, it.n, it.deepK, it.single_ext, blockIdx.x);
+	probe_table_block((g_u8p)it.N0, (g_i32p)it.SA, (g_u32p)it.rec, (g_u16p)it.rec2, (ANDI_GLOBAL uint2 *)it.deep, it.flags, it.n, it.deepK, it.single_ext, blockIdx.x);
 }
 
 // (c) for a table shallower than CR_K: the closed runs of words of K..8 nucleotides, which records capped at K cannot show.
