@@ -1,5 +1,6 @@
 // rep_groups.h — the one host driver of the calls that build a tree per distance matrix, REPLICATES of one n taken a
-// group at a time as their grids' second dimension: andi_hip_nj, andi_hip_nj_batch and andi_hip_bootstrap_nj (nj.hip),
+// group at a time as their grids' second dimension: andi_hip_nj, andi_hip_nj_batch and andi_hip_bootstrap_nj and their
+// method-taking forms andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (nj.hip),
 // andi_hip_linkage and andi_hip_linkage_batch (linkage.hip).  Private, host code only.  In the order a call uses it:
 //   alloc_group  the group's size (nj_group_size, api_internal.h: GROUP_BYTES of device memory) and its buffers, in the
 //                call's DevScope -- so every exit of a call, an error exit too, waits for the stream before a buffer goes
@@ -31,10 +32,11 @@ struct Entry {
 inline Entry bad_entry(unsigned long long bad, size_t n) { return Entry{(size_t)(bad / n), (size_t)(bad % n)}; }
 
 // The buffers of a call's group in dev: as many replicates as GROUP_BYTES hold, as there are; G receives the group's
-// size.  Buffers says what a replicate costs (replicate_bytes(n)) and how g of them are allocated (alloc(dev, n, g)).
+// size.  b says what a replicate costs (replicate_bytes(n): nj.hip's depends on the tree method) and how g of them are
+// allocated (alloc(dev, n, g)).
 template <typename Buffers>
 hipError_t alloc_group(DevScope &dev, Buffers &b, size_t n, size_t count, size_t &G) {
-	G = nj_group_size(KNOB_NJ_GROUP, 65535, GROUP_BYTES, Buffers::replicate_bytes(n));
+	G = nj_group_size(KNOB_NJ_GROUP, 65535, GROUP_BYTES, b.replicate_bytes(n));
 	if (G > count) G = count;
 	hipError_t e = b.alloc(dev, n, G);
 	while (e != hipSuccess && G > 1) { // the memory is not there: smaller groups, down to the one matrix a single call needs too

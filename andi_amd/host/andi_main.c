@@ -407,6 +407,8 @@ static void usage(int status) {
 		"                       of replicates.  These trees come from the portable estimator (its own logarithm, within\n"
 		"                       an ulp of the C library's); in a rare tie they can differ from those of a run that\n"
 		"                       prints the matrices\n"
+		"      --tree-method=M  Build the trees of --tree, --support, --consensus, --transfer and --rogues by 'nj'\n"
+		"                       (neighbor-joining) or 'bionj' (BIONJ, Gascuel 1997); default: nj\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -524,10 +526,27 @@ static void put_newick(const tree_file *o, const newick_src *w, const char **nam
 	free(text);
 }
 
-/* --tree: the neighbor-joining tree of the K-th printed matrix (1 = the point estimate) as one Newick line, from the
- * averaged distances whatever -vv asks the matrix to print */
+/* --tree-method: the builder of every joined tree.  Neighbor-joining goes through the calls it always went through, so a
+ * run without the option says of a failure what it always said (the context's error names the function called). */
+static int join_one(andi_hip_ctx *ctx, const double *D, size_t n, int method, andi_hip_nj_join *J) {
+	return method == ANDI_TREE_NJ ? andi_hip_nj(ctx, D, n, J) : andi_hip_tree(ctx, D, n, method, J);
+}
+
+static int join_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, int method, andi_hip_nj_join *J, int64_t *bad) {
+	return method == ANDI_TREE_NJ ? andi_hip_nj_batch(ctx, D, n, count, J, bad) : andi_hip_tree_batch(ctx, D, n, count, method, J, bad);
+}
+
+static int join_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, int model, int method, uint64_t seed, size_t first,
+						  size_t count, andi_hip_nj_join *J, int64_t *bad) {
+	return method == ANDI_TREE_NJ ? andi_hip_bootstrap_nj(ctx, M, n, model, seed, first, count, J, bad, NULL)
+								  : andi_hip_bootstrap_tree(ctx, M, n, model, method, seed, first, count, J, bad, NULL);
+}
+
+/* --tree: the tree (neighbor-joining, or --tree-method's) of the K-th printed matrix (1 = the point estimate) as one Newick
+ * line, from the averaged distances whatever -vv asks the matrix to print */
 typedef struct {
 	const tree_file *o;
+	int method;        /* ANDI_TREE_* */
 	andi_hip_ctx *ctx; /* one for all trees, on opts.device */
 	int device_for_ctx;
 	int failed;        /* it could not be created: said once */
@@ -552,7 +571,7 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
 				free(D), free(J);
 				return;
 			}
-	if (andi_hip_nj(t->ctx, D, n, J)) {
+	if (join_one(t->ctx, D, n, t->method, J)) {
 		soft_warnx("No tree for matrix %d: %s", k, andi_hip_last_error(t->ctx));
 		free(D), free(J);
 		return;
@@ -584,6 +603,7 @@ typedef struct { /* what a run gives them */
 	int model, truncate, trees_only;
 	uint64_t seed;
 	const rogue_out *rogues;
+	int method; /* ANDI_TREE_*: the builder of the point estimate's tree and of the replicates' */
 } boot_run;
 
 typedef struct {
@@ -633,7 +653,7 @@ static void support_begin(support_state *s, const tree_file *o, const boot_run *
 				s->point_ok = s->trans_ok = s->rogue_ok = 0;
 				break;
 			}
-	if ((s->point_ok || s->trans_ok || s->rogue_ok) && andi_hip_nj(r->ctx, D, n, s->J)) {
+	if ((s->point_ok || s->trans_ok || s->rogue_ok) && join_one(r->ctx, D, n, r->method, s->J)) {
 		if (f) soft_warnx("No support values: %s", andi_hip_last_error(r->ctx));
 		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(r->ctx));
 		if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(r->ctx));
@@ -653,12 +673,12 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 		uint8_t *skip = cf ? s->skipall + first : s->skipall;
 		int failed;
 		if (s->r.trees_only) {
-			failed = andi_hip_bootstrap_nj(ctx, M, n, s->r.model, s->r.seed, first, c, R, s->bad, NULL);
+			failed = join_bootstrap(ctx, M, n, s->r.model, s->r.method, s->r.seed, first, c, R, s->bad);
 		} else {
 			for (size_t k = 0; k < c; k++)
 				if (andi_hip_distances(B + (first - start + k) * n * n, n, s->r.model, s->D + k * n * n))
 					err(errno, "Could not allocate enough memory for the support values.");
-			failed = andi_hip_nj_batch(ctx, s->D, n, c, R, s->bad);
+			failed = join_batch(ctx, s->D, n, c, s->r.method, R, s->bad);
 		}
 		if (failed) {
 			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
@@ -1120,6 +1140,7 @@ int main(int argc, char *argv[]) {
 												 {"rogues", required_argument, NULL, 0},
 												 {"rogue-cutoff", required_argument, NULL, 0},
 												 {"trees-only", no_argument, NULL, 0},
+												 {"tree-method", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1148,7 +1169,7 @@ int main(int argc, char *argv[]) {
 	enum { P_AUTO, P_NEVER, P_ALWAYS } progress = P_AUTO;
 	name_list files = {0}, ref_files = {0}; /* ref_files: --reference, --reference-list, the query-versus-reference mode */
 	int rect = 0, bootstrap_given = 0, trees_only = 0;
-	tree_out tree = {.o = &outs[OUT_TREE]};
+	tree_out tree = {.o = &outs[OUT_TREE], .method = ANDI_TREE_NJ};
 	rogue_out rogues = {.cutoff = 0.3}; /* (booster's default for the same cutoff) */
 	cluster_out clus = {.method = ANDI_LINK_AVERAGE};
 	place_out place = {.method = ANDI_PLACE_FM};
@@ -1172,6 +1193,11 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
 				if (!strcmp(o, "clusters")) clus.clusters_path = optarg;
+				if (!strcmp(o, "tree-method")) {
+					if (!strcasecmp(optarg, "nj")) tree.method = ANDI_TREE_NJ;
+					else if (!strcasecmp(optarg, "bionj")) tree.method = ANDI_TREE_BIONJ;
+					else errx(1, "Expected one of 'nj' or 'bionj' for --tree-method, but '%s' was given.", optarg);
+				}
 				if (!strcmp(o, "linkage")) {
 					if (!strcasecmp(optarg, "single")) clus.method = ANDI_LINK_SINGLE;
 					else if (!strcasecmp(optarg, "complete")) clus.method = ANDI_LINK_COMPLETE;
@@ -1414,7 +1440,7 @@ int main(int argc, char *argv[]) {
 			if (clus.df || clus.cf) cluster_chunk(&clus, B, first, c, all.v, names, n, opts.model, truncate);
 			if (!trees) continue;
 			if (!begun) {
-				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed, &rogues};
+				const boot_run run = {ctx, all.v, names, n, bootstrap, opts.model, truncate, trees_only, seed, &rogues, tree.method};
 				support_begin(&st, outs, &run, M);
 			}
 			begun = 1;

@@ -117,6 +117,8 @@ SYMBOLS = {
                                                       C.c_size_t]),
     "andi_hip_nj": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "andi_hip_nj_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P]),
+    "andi_hip_tree": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
+    "andi_hip_tree_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P, _P]),
     "andi_hip_nj_support": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_size_t, _P, _P]),
     "andi_hip_nj_splits": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, _P, _P, C.POINTER(C.c_size_t), C.POINTER(_P),
                                      C.POINTER(_P)]),
@@ -171,6 +173,8 @@ SYMBOLS = {
     "andi_hip_bootstrap": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_size_t, _P]),
     "andi_hip_bootstrap_range": (C.c_int, [_P, _P, C.c_size_t, C.c_uint64, C.c_size_t, C.c_size_t, _P]),
     "andi_hip_bootstrap_nj": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_uint64, C.c_size_t, C.c_size_t, _P, _P, _P]),
+    "andi_hip_bootstrap_tree": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int, C.c_uint64, C.c_size_t, C.c_size_t, _P, _P,
+                                          _P]),
     "andi_hip_estimate_portable": (C.c_int, [_P, C.c_size_t, C.c_int, _P]),
     "andi_hip_dev_alloc": (C.c_int, [_P, C.c_size_t, C.POINTER(_P)]),
     "andi_hip_dev_free": (None, [_P, _P]),
@@ -962,6 +966,57 @@ def nj_batch(ctx: Context, Ds):
     bad = np.zeros(count, np.int64)
     ctx._check(load().andi_hip_nj_batch(ctx._h, Ds.ctypes.data, n, count, J.ctypes.data, bad.ctypes.data), "nj_batch")
     return J, bad
+
+
+# the tree builders andi_hip_tree takes (ANDI_TREE_*)
+TREE_METHODS = {"nj": 0, "bionj": 1}
+
+
+def _tree_method(method):
+    if method not in TREE_METHODS:
+        raise ValueError("tree method %r: expected nj or bionj" % (method,))
+    return TREE_METHODS[method]
+
+
+def tree(ctx: Context, D, method="nj"):
+    """The tree of the (n, n) distances D by neighbor-joining ("nj") or BIONJ ("bionj") on the device (andi_hip_tree): what
+    nj returns, and with "nj" the same bytes."""
+    method = _tree_method(method)
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    J = np.zeros(1 if n == 2 else max(n - 2, 0), NJ_JOIN)
+    ctx._check(load().andi_hip_tree(ctx._h, D.ctypes.data, n, method, J.ctypes.data), "tree")
+    return J
+
+
+def tree_batch(ctx: Context, Ds, method="nj"):
+    """The trees of the (count, n, n) distances Ds in shared launches (andi_hip_tree_batch): what nj_batch returns, J[k] the
+    records tree(ctx, Ds[k], method) gives, bit for bit."""
+    method = _tree_method(method)
+    Ds = np.ascontiguousarray(Ds, dtype=np.float64)
+    assert Ds.ndim == 3 and Ds.shape[1] == Ds.shape[2]
+    count, n = Ds.shape[0], Ds.shape[1]
+    J = np.zeros((count, 1 if n == 2 else max(n - 2, 0)), NJ_JOIN)
+    bad = np.zeros(count, np.int64)
+    ctx._check(load().andi_hip_tree_batch(ctx._h, Ds.ctypes.data, n, count, method, J.ctypes.data, bad.ctypes.data),
+               "tree_batch")
+    return J, bad
+
+
+def bootstrap_tree(ctx: Context, M, count, model=M_JC, method="nj", seed=0, first=0, distances=False):
+    """bootstrap_nj with the tree builder chosen (andi_hip_bootstrap_tree): the same replicates and distances, joined by
+    `method`; what bootstrap_nj returns."""
+    method = _tree_method(method)
+    M = np.ascontiguousarray(M, dtype=np.uint32)
+    n = M.shape[0]
+    assert M.shape == (n, n, 17)
+    J = np.zeros((count, 1 if n == 2 else max(n - 2, 0)), NJ_JOIN)
+    bad = np.zeros(count, np.int64)
+    D = np.empty((count, n, n), np.float64) if distances else None
+    ctx._check(load().andi_hip_bootstrap_tree(ctx._h, M.ctypes.data, n, model, method, seed, first, count, J.ctypes.data,
+                                              bad.ctypes.data, D.ctypes.data if distances else None), "bootstrap_tree")
+    return (J, bad, D) if distances else (J, bad)
 
 
 def linkage(ctx: Context, D, method="average"):

@@ -26,7 +26,8 @@
  * andi_hip_cluster_stability and andi_hip_format_newick_linkage (additions only); and placement of queries on a tree:
  * andi_hip_place, andi_hip_distances_rect, andi_hip_parse_newick and andi_hip_format_jplace (additions only); and the k-mer
  * sketch screen in front of the query-versus-reference mode: andi_hip_sketch and the calls around it,
- * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only).
+ * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only); and the tree builder by method
+ * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -432,6 +433,45 @@ int andi_hip_nj_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count
  * Synchronous. */
 int andi_hip_bootstrap_nj(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, int model, uint64_t seed, size_t first,
 						  size_t count, andi_hip_nj_join *joins, int64_t *bad, double *D);
+/* The tree builder by method: neighbor-joining as above, or BIONJ (Gascuel, Mol. Biol. Evol. 14:685, 1997), which is
+ * neighbor-joining but for the weight lambda with which a join averages its two nodes' distances to the rest: chosen per
+ * join to minimise the variance of the new distances, not fixed at 1/2. */
+#define ANDI_TREE_NJ 0
+#define ANDI_TREE_BIONJ 1
+/* The tree of the n x n matrix D by `method` (ANDI_TREE_*): arguments, records, errors and limits as andi_hip_nj; a method
+ * outside 0 ... 1 fails with 1 before any HIP call, like the other bad arguments.  With ANDI_TREE_NJ the records are
+ * andi_hip_nj's, bit for bit.  Synchronous.
+ *
+ * BIONJ is bit-exact to this contract (tests/bionj_model.py restates it):
+ *  - andi_hip_nj's, word for word: the input (upper triangle read and mirrored, diagonal +0.0, a non-finite entry fails
+ *    and names the first one); slots, ids and the ascending active list; R_x and Q; the choice of the pair, its tie rule
+ *    and its NaN rule; la, lb and the record; the r = 3 record; n = 2; negative lengths kept; 2 <= n <= 65535;
+ *  - a second matrix V, by the same slots: before the first step V = D, mirrored, diagonal +0.0;
+ *  - a step with r >= 4: the pair (a, b), a the smaller id, and d, la, lb as in andi_hip_nj; then, every operation rounded
+ *    and none fused:
+ *      RV_x = the sequential sum, from +0.0, of V[x][k] over the active slots k in ascending order (x included): R_x's rule;
+ *      vab = V[a][b];
+ *      lambda = 0.5 + (RV_b - RV_a) / ((double)(2*(r-2)) * vab);
+ *      if vab == 0.0 (either sign) or lambda is NaN: lambda = 0.5;  then lambda < 0 -> 0.0 and lambda > 1 -> 1.0;
+ *      mu = 1.0 - lambda;
+ *      for every other active k: D[u][k] = D[k][u] = lambda*(D[a][k] - la) + mu*(D[b][k] - lb),
+ *                                V[u][k] = V[k][u] = (lambda*V[a][k] + mu*V[b][k]) - (lambda*mu)*vab;
+ *      D[u][u] = V[u][u] = +0.0.
+ *    (V[a][a] and V[b][b] are +0.0 and V[a][b] = V[b][a], so RV_b - RV_a is Gascuel's sum over k != a, b of V[b][k] - V[a][k]
+ *    in exact arithmetic; it is stated through row sums because the device sums a row of V by the chain that sums a row of D.)
+ *  Overflow of finite input can make lengths inf or NaN, as in andi_hip_nj; a NaN lambda is 1/2. */
+int andi_hip_tree(andi_hip_ctx *ctx, const double *D, size_t n, int method, andi_hip_nj_join *joins);
+/* andi_hip_nj_batch by method: matrix k's records are bit for bit what andi_hip_tree writes for D + k*n*n with that method;
+ * bad, the grouping ("the results do not depend on the grouping") and the return values are andi_hip_nj_batch's, a method
+ * outside 0 ... 1 one more bad argument.  A BIONJ matrix costs two n x n matrices of doubles on the device, so its groups
+ * are half as large. */
+int andi_hip_tree_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, int method, andi_hip_nj_join *joins,
+						int64_t *bad);
+/* andi_hip_bootstrap_nj by method: the same replicates and distances, joined by `method`; the records are what
+ * andi_hip_tree_batch writes for those matrices with that method, bit for bit.  D, if given, receives the distance
+ * matrices only (never V).  A method outside 0 ... 1 is one more bad argument. */
+int andi_hip_bootstrap_tree(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, int model, int method, uint64_t seed,
+							size_t first, size_t count, andi_hip_nj_join *joins, int64_t *bad, double *D);
 /* Bootstrap support of the branches of `tree` (n - 2 records) among the `count` replicate trees `reps` (count * (n - 2)
  * records, replicate k's from reps + k*(n - 2) on).  Pair record s of a tree, 0 <= s < n - 3, defines the bipartition
  * {L, leaves \ L} with L the leaves below node n + s; an unrooted binary tree has exactly these n - 3 non-trivial
