@@ -1,7 +1,8 @@
 // rep_groups.h — the one host driver of the calls that build a tree per distance matrix, REPLICATES of one n taken a
 // group at a time as their grids' second dimension: andi_hip_nj, andi_hip_nj_batch and andi_hip_bootstrap_nj and their
 // method-taking forms andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (nj.hip),
-// andi_hip_linkage and andi_hip_linkage_batch (linkage.hip).  Private, host code only.  In the order a call uses it:
+// andi_hip_linkage and andi_hip_linkage_batch (linkage.hip) -- and andi_hip_complete_batch (complete.hip), which fills
+// missing distances in front of them and takes alloc_group and for_groups alone.  Private, host code only.  In the order a call uses it:
 //   alloc_group  the group's size (nj_group_size, api_internal.h: GROUP_BYTES of device memory) and its buffers, in the
 //                call's DevScope -- so every exit of a call, an error exit too, waits for the stream before a buffer goes
 //                back; a group that does not fit is halved, down to the one matrix a single call needs too;

@@ -409,6 +409,13 @@ static void usage(int status) {
 		"                       prints the matrices\n"
 		"      --tree-method=M  Build the trees of --tree, --support, --consensus, --transfer and --rogues by 'nj'\n"
 		"                       (neighbor-joining) or 'bionj' (BIONJ, Gascuel 1997); default: nj\n"
+		"      --complete       Before a tree is joined (--tree, --support, --consensus, --transfer, --rogues): estimate every\n"
+		"                       distance that is missing ('nan') from the known distances around it -- the least of\n"
+		"                       max(d(i,k) + d(j,l), d(i,l) + d(j,k)) - d(k,l) over the pairs k, l whose five distances are\n"
+		"                       known (the four-point condition), on the GPU.  The printed matrices are not changed\n"
+		"      --complete-report=FILE  Implies --complete: write one line per missing distance of the first matrix to\n"
+		"                       FILE, tab-separated: the two names, the estimate, the round that found it and the number\n"
+		"                       of quartets it is the least of ('nan', 0, 0: it could not be derived)\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -526,6 +533,32 @@ static void put_newick(const tree_file *o, const newick_src *w, const char **nam
 	free(text);
 }
 
+/* --complete: every matrix that goes into a joined tree has its missing distances estimated from quartets first
+ * (andi_hip_complete), in place; what the run prints is not touched.  --complete-report: the point estimate's missing pairs. */
+typedef struct {
+	int on;
+	const char *report_path;
+	FILE *rf;
+} complete_opts;
+static complete_opts cmpl;
+#define NOT_FINITE (cmpl.on ? " is not finite and could not be derived." : " is not finite.")
+
+/* the one warning of a matrix that received fills; k: the matrix as the run counts them (1 = the point estimate) */
+static void complete_warn(unsigned long k, size_t missing, size_t left) {
+	static int said_1; /* (--tree and --support both complete the point estimate) */
+	if (k == 1 && said_1++) return;
+	if (missing > left)
+		soft_warnx("Matrix %lu: %zu of %zu missing distances were derived from quartets (--complete).", k, missing - left, missing);
+}
+
+/* the K-th matrix D completed in place; 0, or 1 with the context's error set */
+static int complete_one(andi_hip_ctx *ctx, double *D, size_t n, unsigned long k) {
+	size_t missing = 0, left = 0;
+	if (andi_hip_complete(ctx, D, n, 0, D, NULL, 0, &missing, &left)) return 1;
+	complete_warn(k, missing, left);
+	return 0;
+}
+
 /* --tree-method: the builder of every joined tree.  Neighbor-joining goes through the calls it always went through, so a
  * run without the option says of a failure what it always said (the context's error names the function called). */
 static int join_one(andi_hip_ctx *ctx, const double *D, size_t n, int method, andi_hip_nj_join *J) {
@@ -552,6 +585,38 @@ typedef struct {
 	int failed;        /* it could not be created: said once */
 } tree_out;
 
+/* --complete-report: the missing pairs of the point estimate, one line each in row-major order, from a completion of its
+ * own (on the context of --tree, made here if this comes first) */
+static void complete_report(tree_out *t, const andi_hip_model *M, const char **names, size_t n, int model, int truncate) {
+	char msg[512];
+	if (!t->failed && !t->ctx && andi_hip_ctx_create(&t->ctx, t->device_for_ctx, msg, sizeof msg)) {
+		t->failed = 1, t->ctx = NULL;
+		soft_warnx("No trees: %s", msg);
+	}
+	if (t->failed) return;
+	double *D = malloc(n * n * sizeof *D);
+	if (!D || andi_hip_distances(M, n, model, D)) err(errno, "Could not allocate enough memory for the report of derived distances.");
+	size_t cap = 0, missing = 0, left = 0;
+	for (size_t i = 0; i < n; i++)
+		for (size_t j = i + 1; j < n; j++) cap += !isfinite(D[i * n + j]);
+	andi_hip_fill *fills = malloc((cap ? cap : 1) * sizeof *fills);
+	if (!fills) err(errno, "Could not allocate enough memory for the report of derived distances.");
+	if (andi_hip_complete(t->ctx, D, n, 0, D, fills, cap, &missing, &left)) {
+		soft_warnx("No report of derived distances: %s", andi_hip_last_error(t->ctx));
+	} else {
+		fprintf(cmpl.rf, "#first\tsecond\tdistance\tround\tquartets\n");
+		for (size_t x = 0; x < missing && x < cap; x++) {
+			const andi_hip_fill *f = &fills[x];
+			const int w = truncate ? 10 : -1; /* (as the matrix prints a name) */
+			fprintf(cmpl.rf, "%.*s\t%.*s\t", w, names[f->i], w, names[f->j]);
+			if (f->round) fprintf(cmpl.rf, "%.8g\t%u\t%llu\n", f->value, f->round, (unsigned long long)f->quartets);
+			else fprintf(cmpl.rf, "nan\t0\t0\n");
+		}
+		if (ferror(cmpl.rf)) err(1, "%s", cmpl.report_path);
+	}
+	free(D), free(fills);
+}
+
 static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, const char **names, size_t n, int model, int truncate,
 					   int k) {
 	if (t->failed) return;
@@ -564,10 +629,15 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
 	double *D = malloc(n * n * sizeof *D);
 	andi_hip_nj_join *J = malloc(n * sizeof *J);
 	if (!D || !J || andi_hip_distances(M, n, model, D)) err(errno, "Could not allocate enough memory for the tree.");
+	if (cmpl.on && complete_one(t->ctx, D, n, (unsigned long)k)) {
+		soft_warnx("No tree for matrix %d: %s", k, andi_hip_last_error(t->ctx));
+		free(D), free(J);
+		return;
+	}
 	for (size_t i = 0; i < n; i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
-				soft_warnx("No tree for matrix %d: the distance of '%s' and '%s' is not finite.", k, g[i].name, g[j].name);
+				soft_warnx("No tree for matrix %d: the distance of '%s' and '%s'%s", k, g[i].name, g[j].name, NOT_FINITE);
 				free(D), free(J);
 				return;
 			}
@@ -614,6 +684,7 @@ typedef struct {
 	double *D;
 	andi_hip_nj_join *J, *Rall;
 	int64_t *bad;
+	uint64_t *cmissing, *cleft; /* --complete: a chunk's counts of andi_hip_complete_batch */
 	uint8_t *skipall;
 	uint32_t *total, *part, *depth;
 	uint64_t *ttotal, *tpart, *moved, *mpart, pairs;
@@ -636,20 +707,27 @@ static void support_begin(support_state *s, const tree_file *o, const boot_run *
 	double *D = s->D = malloc((trees_only ? 1 : chunk) * n * n * sizeof *D);
 	s->J = malloc(nrec * sizeof *s->J), s->Rall = malloc(kept * nrec * sizeof *s->Rall);
 	s->bad = malloc(chunk * sizeof *s->bad);
+	s->cmissing = calloc(chunk, sizeof *s->cmissing), s->cleft = calloc(chunk, sizeof *s->cleft);
 	s->skipall = malloc(kept);
 	s->total = calloc(nsup, sizeof *s->total), s->part = calloc(nsup, sizeof *s->part), s->depth = calloc(nsup, sizeof *s->depth);
 	s->ttotal = calloc(nsup, sizeof *s->ttotal), s->tpart = calloc(nsup, sizeof *s->tpart);
 	s->moved = calloc(n, sizeof *s->moved), s->mpart = calloc(n, sizeof *s->mpart);
-	if (!D || !s->J || !s->Rall || !s->bad || !s->skipall || !s->total || !s->part || !s->depth || !s->ttotal || !s->tpart ||
+	if (!D || !s->J || !s->Rall || !s->bad || !s->cmissing || !s->cleft || !s->skipall || !s->total || !s->part || !s->depth || !s->ttotal || !s->tpart ||
 		!s->moved || !s->mpart || ((f || tf || rf) && andi_hip_distances(M, n, r->model, D)))
 		err(errno, "Could not allocate enough memory for the support values.");
 	s->point_ok = f != NULL, s->trans_ok = tf != NULL, s->cons_ok = cf != NULL, s->rogue_ok = rf != NULL;
+	if (cmpl.on && (f || tf || rf) && complete_one(r->ctx, D, n, 1)) {
+		if (f) soft_warnx("No support values: %s", andi_hip_last_error(r->ctx));
+		if (tf) soft_warnx("No transfer support: %s", andi_hip_last_error(r->ctx));
+		if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(r->ctx));
+		s->point_ok = s->trans_ok = s->rogue_ok = 0;
+	}
 	for (size_t i = 0; i < n && (s->point_ok || s->trans_ok || s->rogue_ok); i++)
 		for (size_t j = i + 1; j < n; j++)
 			if (!isfinite(D[i * n + j])) {
-				if (f) soft_warnx("No support values: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
-				if (tf) soft_warnx("No transfer support: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
-				if (rf) soft_warnx("No rogue table: the distance of '%s' and '%s' is not finite.", g[i].name, g[j].name);
+				if (f) soft_warnx("No support values: the distance of '%s' and '%s'%s", g[i].name, g[j].name, NOT_FINITE);
+				if (tf) soft_warnx("No transfer support: the distance of '%s' and '%s'%s", g[i].name, g[j].name, NOT_FINITE);
+				if (rf) soft_warnx("No rogue table: the distance of '%s' and '%s'%s", g[i].name, g[j].name, NOT_FINITE);
 				s->point_ok = s->trans_ok = s->rogue_ok = 0;
 				break;
 			}
@@ -678,7 +756,10 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			for (size_t k = 0; k < c; k++)
 				if (andi_hip_distances(B + (first - start + k) * n * n, n, s->r.model, s->D + k * n * n))
 					err(errno, "Could not allocate enough memory for the support values.");
-			failed = join_batch(ctx, s->D, n, c, s->r.method, R, s->bad);
+			failed = cmpl.on && andi_hip_complete_batch(ctx, s->D, n, c, 0, s->D, s->cmissing, s->cleft);
+			for (size_t k = 0; cmpl.on && !failed && k < c; k++)
+				complete_warn(first + (unsigned long)k + 2, (size_t)s->cmissing[k], (size_t)s->cleft[k]);
+			if (!failed) failed = join_batch(ctx, s->D, n, c, s->r.method, R, s->bad);
 		}
 		if (failed) {
 			if (f) soft_warnx("No support values: %s", andi_hip_last_error(ctx));
@@ -693,8 +774,8 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 		for (size_t k = 0; k < c; k++) {
 			skip[k] = s->bad[k] >= 0;
 			if (skip[k])
-				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s' is not finite.", first + (unsigned long)k + 2,
-						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name);
+				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s'%s", first + (unsigned long)k + 2,
+						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name, NOT_FINITE);
 			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec}, s->r.names, n, s->r.truncate);
 			s->counted += !skip[k];
 		}
@@ -782,7 +863,7 @@ static void support_end(support_state *s, int complete) {
 		andi_hip_free(freq), andi_hip_free(sets);
 		free(ids), free(nodes);
 	}
-	free(s->D), free(s->J), free(s->Rall), free(s->bad), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
+	free(s->D), free(s->J), free(s->Rall), free(s->bad), free(s->cmissing), free(s->cleft), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
 		free(s->tpart), free(s->moved), free(s->mpart);
 }
 
@@ -1141,6 +1222,8 @@ int main(int argc, char *argv[]) {
 												 {"rogue-cutoff", required_argument, NULL, 0},
 												 {"trees-only", no_argument, NULL, 0},
 												 {"tree-method", required_argument, NULL, 0},
+												 {"complete", no_argument, NULL, 0},
+												 {"complete-report", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1189,6 +1272,8 @@ int main(int argc, char *argv[]) {
 				for (int k = 0; k < OUT_COUNT; k++)
 					if (!strcmp(o, outs[k].option)) outs[k].path = optarg;
 				if (!strcmp(o, "trees-only")) trees_only = 1;
+				if (!strcmp(o, "complete")) cmpl.on = 1;
+				if (!strcmp(o, "complete-report")) cmpl.on = 1, cmpl.report_path = optarg;
 				if (!strcmp(o, "rogues")) rogues.path = optarg;
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
@@ -1322,6 +1407,8 @@ int main(int argc, char *argv[]) {
 	if (clus.clusters_path && rect) errx(1, "Clusters (--clusters) are" WITH_REFERENCE);
 	if (clus.dendro_path && trees_only) errx(1, "A dendrogram (--dendrogram) is not available together with --trees-only: there are no matrices to cluster.");
 	if (clus.clusters_path && trees_only) errx(1, "Clusters (--clusters) are not available together with --trees-only: there are no matrices to cluster.");
+	if (cmpl.on && trees_only)
+		errx(1, "Missing distances (--complete) are not derived together with --trees-only: the bootstrap matrices stay on the GPU.");
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
 	if (clus.have_threshold && !clus.clusters_path) errx(1, "A threshold (--threshold) needs somewhere to go: give --clusters=FILE.");
 	if (place.path && !rect) errx(1, "Placement (--place) needs references to place on: give --reference=FILE or --reference-list=FILE.");
@@ -1346,6 +1433,7 @@ int main(int argc, char *argv[]) {
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
 	if (rogues.path && !(rogues.f = fopen(rogues.path, "w"))) err(1, "%s", rogues.path);
+	if (cmpl.report_path && !(cmpl.rf = fopen(cmpl.report_path, "w"))) err(1, "%s", cmpl.report_path);
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
 	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
@@ -1390,6 +1478,7 @@ int main(int argc, char *argv[]) {
 
 	const char **names = name_array(all.v, n);
 	print_distances(M, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 1);
+	if (cmpl.rf) complete_report(&tree, M, names, n, opts.model, truncate);
 	if (tree.o->f) write_tree(&tree, M, all.v, names, n, opts.model, truncate, 1);
 	if (clus.df || clus.cf) cluster_point(&clus, M, names, n, opts.model, truncate);
 	if (cli_trace) {
@@ -1457,6 +1546,7 @@ int main(int argc, char *argv[]) {
 	for (int k = 0; k < OUT_COUNT; k++)
 		if (outs[k].f && fclose(outs[k].f)) err(1, "%s", outs[k].path);
 	if (rogues.f && fclose(rogues.f)) err(1, "%s", rogues.path);
+	if (cmpl.rf && fclose(cmpl.rf)) err(1, "%s", cmpl.report_path);
 	free(M);
 	free(in);
 	free(names);

@@ -130,6 +130,9 @@ SYMBOLS = {
     "andi_hip_cluster_medoids": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, _P]),
     "andi_hip_cluster_stability": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.c_size_t, _P]),
     "andi_hip_format_newick_linkage": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
+    "andi_hip_complete": (C.c_int, [_P, _P, C.c_size_t, C.c_uint, _P, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                    C.POINTER(C.c_size_t)]),
+    "andi_hip_complete_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_uint, _P, _P, _P]),
     "andi_hip_place": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
     "andi_hip_distances_rect": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
@@ -1044,6 +1047,42 @@ def linkage_batch(ctx: Context, Ds, method="average"):
     ctx._check(load().andi_hip_linkage_batch(ctx._h, Ds.ctypes.data, n, count, method, Z.ctypes.data,
                                              bad.ctypes.data), "linkage_batch")
     return Z, bad
+
+
+# andi_hip_fill: a missing pair of andi_hip_complete (its value, the round that filled it -- 0: none did -- and its quartets)
+FILL = np.dtype([("i", "<u4"), ("j", "<u4"), ("round", "<u4"), ("pad", "<u4"), ("quartets", "<u8"), ("value", "<f8")])
+
+
+def complete(ctx: Context, D, max_rounds=0):
+    """The missing distances (NaN, +inf, -inf) of the (n, n) matrix D estimated from quartets on the device
+    (andi_hip_complete; only the upper triangle is read): (C, fills) -- C the completed matrix, mirrored, a pair that could
+    not be derived a NaN; fills one record of dtype FILL per missing pair of D in row-major order, round 0 where it stayed
+    missing.  max_rounds = 0: rounds until one fills nothing."""
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    iu = np.triu_indices(n, 1)
+    cap = int((~np.isfinite(D[iu])).sum())
+    Cm = np.empty((n, n), np.float64)
+    fills = np.zeros(cap, FILL)
+    missing, left = C.c_size_t(0), C.c_size_t(0)
+    ctx._check(load().andi_hip_complete(ctx._h, D.ctypes.data, n, int(max_rounds), Cm.ctypes.data,
+                                        fills.ctypes.data if cap else None, cap, C.byref(missing), C.byref(left)), "complete")
+    assert missing.value == cap and left.value == int((fills["round"] == 0).sum())
+    return Cm, fills
+
+
+def complete_batch(ctx: Context, Ds, max_rounds=0):
+    """complete for the (count, n, n) matrices Ds in shared launches (andi_hip_complete_batch): (Cs, missing, left) -- Cs[k]
+    the matrix complete(ctx, Ds[k]) gives, bit for bit; missing[k] and left[k] its missing pairs before and after."""
+    Ds = np.ascontiguousarray(Ds, dtype=np.float64)
+    assert Ds.ndim == 3 and Ds.shape[1] == Ds.shape[2]
+    count, n = Ds.shape[0], Ds.shape[1]
+    Cs = np.empty((count, n, n), np.float64)
+    missing, left = np.zeros(count, np.uint64), np.zeros(count, np.uint64)
+    ctx._check(load().andi_hip_complete_batch(ctx._h, Ds.ctypes.data, n, count, int(max_rounds), Cs.ctypes.data,
+                                              missing.ctypes.data, left.ctypes.data), "complete_batch")
+    return Cs, missing, left
 
 
 def place(ctx: Context, J, D, method="fm", per=False):

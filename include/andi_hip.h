@@ -27,7 +27,8 @@
  * andi_hip_place, andi_hip_distances_rect, andi_hip_parse_newick and andi_hip_format_jplace (additions only); and the k-mer
  * sketch screen in front of the query-versus-reference mode: andi_hip_sketch and the calls around it,
  * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only); and the tree builder by method
- * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only).
+ * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only); and missing
+ * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -626,6 +627,58 @@ int andi_hip_cluster_stability(const uint32_t *labels, size_t nclusters, const u
  * (a height of +inf: a pair without a distance) give 0 and an empty string. */
 size_t andi_hip_format_newick_linkage(const andi_hip_link *links, size_t n, const char *const *names, int truncate_names,
 									  char *out, size_t cap);
+
+/* Missing distances estimated from quartets on the context's device, in front of the tree calls, which refuse a matrix with
+ * a pair that has no distance.  D: an n x n matrix in host memory, row-major.  The estimate of a missing d(i, j) is the
+ * four-point condition's bound d(i,j) <= max(d(i,k) + d(j,l), d(i,l) + d(j,k)) - d(k,l), least over the pairs {k, l}
+ * whose five distances are known: equality holds in every quartet whose topology does not put i and j together.
+ *
+ * The result is bit-exact to this contract (tests/complete_model.py restates it in NumPy):
+ *  - input: only D[i][j] with i < j is read; it is mirrored, the diagonal is +0.0.  A pair is KNOWN iff its entry is
+ *    finite; NaN, +inf and -inf are MISSING.  Negative finite entries are known and kept;
+ *  - rounds t = 1, 2, ... run Jacobi-style: every read of round t sees the matrix as it stood when the round began;
+ *  - for every missing pair i < j the CANDIDATES of the round are the unordered pairs {k, l}, k != l, both outside {i, j},
+ *    with all five of (i,k), (i,l), (j,k), (j,l), (k,l) known at the round's start; each is
+ *    c = max(D[i][k] + D[j][l], D[i][l] + D[j][k]) - D[k][l], every operation rounded to double.  c is symmetric in k and
+ *    l and never a NaN (the operands are finite); it may overflow to +-inf;
+ *  - m = the least candidate.  With at least one candidate and m < +inf the pair is FILLED in round t with
+ *    m <= 0.0 ? +0.0 : m (the estimator's own clamp; it also removes -0.0, so the signs of zero and the order of the
+ *    minimum do not matter).  It is known from round t + 1 on, on equal footing with a measured entry, and never revised;
+ *  - a filled pair records its round and its quartets: the number of candidates in that round;
+ *  - the rounds end after one that fills nothing, or after max_rounds of them (0: no limit; every round but the last
+ *    fills a pair, so there is at most one round per missing pair, and one more);
+ *  - a pair still missing is the quiet NaN 0x7ff8000000000000 (andi_log's) in the output;
+ *  - n < 4: there is never a candidate.
+ * What the estimate is worth, on distances that a tree with branch lengths generates exactly (checked on random trees with
+ * dyadic branch lengths, where every sum is exact: tests/test_complete_host.py): a value of round 1 is never below the true
+ * distance, and it IS the true distance whenever some known quartet separates i from j; with 20-50 % of the pairs of 8-24
+ * leaves missing at random nearly every pair was filled, within three rounds, and about four fills in five were exact.  From round 2
+ * on a value can also be too small: a filled over-estimate may be the d(k,l) that is subtracted.  On noisy data the
+ * minimum is biased low; round and quartets are what lets a user judge a fill.
+ *
+ * C receives the completed n x n matrix (it may be D); *missing the number of missing pairs of the input, *left the
+ * number still missing at the end; fills the first min(cap, *missing) missing pairs in row-major (i < j) order: a filled one
+ * with its value, round and quartets, an unfilled one with round 0, quartets 0 and the quiet NaN.  fills may be NULL when
+ * cap is 0.  A matrix with nothing missing comes back mirrored with *missing == 0, and no quartet kernel is launched.
+ * Pairs left over are no error of this call: the caller decides.  2 <= n <= 65535; bad arguments (a NULL ctx, D, C, missing
+ * or left, a NULL fills with cap > 0, n out of range) fail with 1 before any HIP call and set the context's error; a HIP
+ * error fails with 1 through the context's error.  Synchronous, on the context's stream.  On the device: the matrix (8 n^2
+ * bytes) and 32 bytes per missing pair.  Work per round: (n - 2)(n - 3) / 2 candidates per pair still missing, at most. */
+typedef struct {
+	uint32_t i, j, round, pad;
+	uint64_t quartets;
+	double value;
+} andi_hip_fill; /* 32 bytes; pad is 0 */
+int andi_hip_complete(andi_hip_ctx *ctx, const double *D, size_t n, unsigned max_rounds, double *C, andi_hip_fill *fills,
+					  size_t cap, size_t *missing, size_t *left);
+/* The completion of `count` matrices of one n in shared launches: D is count row-major n x n matrices one after the other,
+ * C receives them completed (it may be D), missing[k] and left[k] matrix k's counts -- bit for bit what the call above
+ * writes for D + k*n*n (the same kernels, the replicate as the grid's second dimension; a matrix of which a round fills
+ * nothing is done, whatever the others still do).  The matrices are taken in groups that fit the device; the results do
+ * not depend on the grouping.  Bad arguments (a NULL pointer, count == 0, n outside 2 ... 65535) fail with 1 before any
+ * HIP call.  Synchronous. */
+int andi_hip_complete_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, unsigned max_rounds, double *C,
+							uint64_t *missing, uint64_t *left);
 
 /* Distance-based placement of queries on a neighbor-joining tree (least-squares placement, as APPLES does it): for every
  * query, the edge of the tree, the point on it and the length of the branch hanging there that fit the query's distances
