@@ -11,6 +11,7 @@ from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_rang
                   nj_transfer_taxa, tree, tree_batch,
                   LINK, cluster_medoids, cluster_stability, linkage, linkage_batch, linkage_cut, newick_linkage,
                   FILL, complete, complete_batch,
+                  DELTA, delta_scores,
                   PLACEMENT, distances_rect, jplace, parse_newick, place,
                   Sketches, screen, screen_select, sketch, sketch_shared,
                   scan_rows, subject_prepare, suffix_array)

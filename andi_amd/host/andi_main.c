@@ -416,6 +416,10 @@ static void usage(int status) {
 		"      --complete-report=FILE  Implies --complete: write one line per missing distance of the first matrix to\n"
 		"                       FILE, tab-separated: the two names, the estimate, the round that found it and the number\n"
 		"                       of quartets it is the least of ('nan', 0, 0: it could not be derived)\n"
+		"      --delta=FILE     Write the tree-likeness score of every genome to FILE, tab-separated: its name, its mean delta\n"
+		"                       over all quartets of genomes that contain it (Holland et al. 2002: 0 where the distances fit\n"
+		"                       a tree, towards 1 where they do not) and the number of those quartets; on the GPU, from the\n"
+		"                       first matrix as it is printed (--complete does not change it)\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -615,6 +619,57 @@ static void complete_report(tree_out *t, const andi_hip_model *M, const char **n
 		if (ferror(cmpl.rf)) err(1, "%s", cmpl.report_path);
 	}
 	free(D), free(fills);
+}
+
+/* --delta: the tree-likeness score of every genome of the point estimate (andi_hip_delta_scores), from the distances as
+ * they are printed -- a pair without a distance takes its quartets out, whatever --complete derives for it (a derived
+ * distance satisfies the four-point condition by construction).  On the context of --tree, made here if this comes first. */
+typedef struct {
+	const char *path;
+	FILE *f;
+} delta_opts;
+static delta_opts dlt;
+
+static void delta_report(tree_out *t, const andi_hip_model *M, const char **names, size_t n, int model, int truncate) {
+	char msg[512];
+	if (n <= 16384 && !t->failed && !t->ctx && andi_hip_ctx_create(&t->ctx, t->device_for_ctx, msg, sizeof msg)) {
+		t->failed = 1, t->ctx = NULL;
+		if (t->o->f) soft_warnx("No trees: %s", msg); /* (write_tree says nothing more) */
+	}
+	const int was = soft_error; /* the scores are an extra: without them the run ends as it would have */
+	if (n > 16384) {
+		soft_warnx("No tree-likeness scores (--delta): they are limited to 16384 sequences (%zu given).", n);
+		soft_error = was;
+		return;
+	}
+	if (t->failed) {
+		soft_warnx("No tree-likeness scores (--delta): there is no GPU context.");
+		soft_error = was;
+		return;
+	}
+	double *D = malloc(n * n * sizeof *D);
+	andi_hip_delta *rec = malloc(n * sizeof *rec);
+	if (!D || !rec || andi_hip_distances(M, n, model, D)) err(errno, "Could not allocate enough memory for the tree-likeness scores.");
+	if (andi_hip_delta_scores(t->ctx, D, n, rec)) {
+		soft_warnx("No tree-likeness scores (--delta): %s", andi_hip_last_error(t->ctx));
+		soft_error = was;
+	} else {
+		unsigned __int128 sum = 0, quartets = 0;
+		const double one = 16777216.0; /* 2^24: a quartet's delta is kept as floor(delta * 2^24) */
+		fprintf(dlt.f, "#name\tdelta\tquartets\n");
+		for (size_t i = 0; i < n; i++) {
+			sum += rec[i].sum, quartets += rec[i].quartets;
+			fprintf(dlt.f, "%.*s\t", truncate ? 10 : -1, names[i]); /* (as the matrix prints a name) */
+			if (rec[i].quartets) fprintf(dlt.f, "%.6f", (double)((long double)rec[i].sum / ((long double)rec[i].quartets * one)));
+			else fprintf(dlt.f, "nan");
+			fprintf(dlt.f, "\t%llu\n", (unsigned long long)rec[i].quartets);
+		}
+		if (quartets) fprintf(dlt.f, "#mean\t%.6f", (double)((long double)sum / ((long double)quartets * one)));
+		else fprintf(dlt.f, "#mean\tnan");
+		fprintf(dlt.f, "\t%llu\n", (unsigned long long)(quartets / 4));
+		if (ferror(dlt.f)) err(1, "%s", dlt.path);
+	}
+	free(D), free(rec);
 }
 
 static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, const char **names, size_t n, int model, int truncate,
@@ -1224,6 +1279,7 @@ int main(int argc, char *argv[]) {
 												 {"tree-method", required_argument, NULL, 0},
 												 {"complete", no_argument, NULL, 0},
 												 {"complete-report", required_argument, NULL, 0},
+												 {"delta", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1274,6 +1330,7 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "trees-only")) trees_only = 1;
 				if (!strcmp(o, "complete")) cmpl.on = 1;
 				if (!strcmp(o, "complete-report")) cmpl.on = 1, cmpl.report_path = optarg;
+				if (!strcmp(o, "delta")) dlt.path = optarg;
 				if (!strcmp(o, "rogues")) rogues.path = optarg;
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
@@ -1407,6 +1464,7 @@ int main(int argc, char *argv[]) {
 	if (clus.clusters_path && rect) errx(1, "Clusters (--clusters) are" WITH_REFERENCE);
 	if (clus.dendro_path && trees_only) errx(1, "A dendrogram (--dendrogram) is not available together with --trees-only: there are no matrices to cluster.");
 	if (clus.clusters_path && trees_only) errx(1, "Clusters (--clusters) are not available together with --trees-only: there are no matrices to cluster.");
+	if (dlt.path && rect) errx(1, "Tree-likeness scores (--delta) are" WITH_REFERENCE);
 	if (cmpl.on && trees_only)
 		errx(1, "Missing distances (--complete) are not derived together with --trees-only: the bootstrap matrices stay on the GPU.");
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
@@ -1434,6 +1492,7 @@ int main(int argc, char *argv[]) {
 		if (outs[k].path && !(outs[k].f = fopen(outs[k].path, "w"))) err(1, "%s", outs[k].path);
 	if (rogues.path && !(rogues.f = fopen(rogues.path, "w"))) err(1, "%s", rogues.path);
 	if (cmpl.report_path && !(cmpl.rf = fopen(cmpl.report_path, "w"))) err(1, "%s", cmpl.report_path);
+	if (dlt.path && !(dlt.f = fopen(dlt.path, "w"))) err(1, "%s", dlt.path);
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
 	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
@@ -1479,6 +1538,7 @@ int main(int argc, char *argv[]) {
 	const char **names = name_array(all.v, n);
 	print_distances(M, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 1);
 	if (cmpl.rf) complete_report(&tree, M, names, n, opts.model, truncate);
+	if (dlt.f) delta_report(&tree, M, names, n, opts.model, truncate);
 	if (tree.o->f) write_tree(&tree, M, all.v, names, n, opts.model, truncate, 1);
 	if (clus.df || clus.cf) cluster_point(&clus, M, names, n, opts.model, truncate);
 	if (cli_trace) {
@@ -1547,6 +1607,7 @@ int main(int argc, char *argv[]) {
 		if (outs[k].f && fclose(outs[k].f)) err(1, "%s", outs[k].path);
 	if (rogues.f && fclose(rogues.f)) err(1, "%s", rogues.path);
 	if (cmpl.rf && fclose(cmpl.rf)) err(1, "%s", cmpl.report_path);
+	if (dlt.f && fclose(dlt.f)) err(1, "%s", dlt.path);
 	free(M);
 	free(in);
 	free(names);

@@ -133,6 +133,7 @@ SYMBOLS = {
     "andi_hip_complete": (C.c_int, [_P, _P, C.c_size_t, C.c_uint, _P, _P, C.c_size_t, C.POINTER(C.c_size_t),
                                     C.POINTER(C.c_size_t)]),
     "andi_hip_complete_batch": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_uint, _P, _P, _P]),
+    "andi_hip_delta_scores": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "andi_hip_place": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
     "andi_hip_distances_rect": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
@@ -1083,6 +1084,23 @@ def complete_batch(ctx: Context, Ds, max_rounds=0):
     ctx._check(load().andi_hip_complete_batch(ctx._h, Ds.ctypes.data, n, count, int(max_rounds), Cs.ctypes.data,
                                               missing.ctypes.data, left.ctypes.data), "complete_batch")
     return Cs, missing, left
+
+
+# andi_hip_delta: a genome's used quartets and the sum of their floor(delta * 2^24)
+DELTA = np.dtype([("sum", "<u8"), ("quartets", "<u8")])
+
+
+def delta_scores(ctx: Context, D):
+    """The tree-likeness scores of the (n, n) matrix D from all its quartets on the device (andi_hip_delta_scores; only the
+    upper triangle is read, a pair that is not finite is missing): an (n,) array of dtype DELTA -- per genome the number of
+    quartets with six known distances that contain it and the sum of their floor(delta * 2^24), delta = (a - b) / (a - c) of
+    the quartet's three sums a >= b >= c.  A genome's mean delta is sum / (quartets * 2^24)."""
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    out = np.zeros(n, DELTA)
+    ctx._check(load().andi_hip_delta_scores(ctx._h, D.ctypes.data, n, out.ctypes.data), "delta_scores")
+    return out
 
 
 def place(ctx: Context, J, D, method="fm", per=False):

@@ -28,7 +28,8 @@
  * sketch screen in front of the query-versus-reference mode: andi_hip_sketch and the calls around it,
  * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only); and the tree builder by method
  * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only); and missing
- * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only).
+ * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only);
+ * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -679,6 +680,39 @@ int andi_hip_complete(andi_hip_ctx *ctx, const double *D, size_t n, unsigned max
  * HIP call.  Synchronous. */
 int andi_hip_complete_batch(andi_hip_ctx *ctx, const double *D, size_t n, size_t count, unsigned max_rounds, double *C,
 							uint64_t *missing, uint64_t *left);
+
+/* Tree-likeness scores from all quartets on the context's device: how far the distances around every genome are from
+ * fitting any tree at all, which everything above (the joined trees, their support, the completion of missing pairs)
+ * takes for granted.  The score is the delta of Holland, Huber, Dress and Moulton (2002; `delta.plot` in ape): 0 for a
+ * quartet that satisfies the four-point condition, towards 1 for one that is a box.  A genome's mean over the quartets it
+ * is in singles out recombinants, chimeric or contaminated assemblies and mislabelled drafts before a tree is built.
+ * D: an n x n matrix in host memory, row-major.
+ *
+ * The result is bit-exact to this contract (tests/delta_model.py restates it in NumPy):
+ *  - input, as andi_hip_complete takes it: only D[i][j] with i < j is read; it is mirrored.  A pair is KNOWN iff its entry
+ *    is finite; NaN, +inf and -inf are MISSING.  Negative finite entries are known;
+ *  - the three sums: for every unordered quartet {x, y, u, v} of distinct genomes whose six distances are known,
+ *    s1 = d(x,y) + d(u,v), s2 = d(x,u) + d(y,v), s3 = d(x,v) + d(y,u), each one rounded double addition.  Each is symmetric
+ *    in its operands and the three are a set, so the quartet's value does not depend on how it is visited;
+ *  - the quartet's delta: a, b, c the largest, the middle and the smallest of the three by value; w = a - c, u = a - b.
+ *    The quartet is USED iff w is finite (which also drops a quartet one of whose sums overflowed).
+ *    delta = w > 0 ? u / w : 0, an IEEE division, no operation contracted into an FMA.  Rounding is monotone, so
+ *    0 <= u <= w and delta lies in [0, 1];
+ *  - the integer: t = (uint64) floor(delta * 2^24); the multiplication is exact, t is 0 ... 2^24;
+ *  - the records: out[x].quartets is the number of used quartets that contain x, out[x].sum the sum of their t.  Both are
+ *    sums of integers, so the result does not depend on any order of summation (the device sums with integer atomics);
+ *  - the mean: a genome's mean delta is sum / (quartets * 2^24); it resolves 6e-8;
+ *  - 2 <= n <= 16384.  At n < 4 every record is {0, 0}.  The upper bound is what keeps sum below 2^64: a genome is in
+ *    C(16383, 3) = 7.33e11 < 2^40 quartets.  The work is C(n, 4), about n^4 / 24, quartets: 3.8e12 at 3085 genomes, and
+ *    the time follows it -- measured on one MI355X, about 5.6e11 quartets a second: 7 s at 3085 genomes, and by that rate
+ *    45 s at 5000, 12 minutes at 10000, an hour and a half at 16384, in one kernel launch.
+ * Bad arguments (a NULL ctx, D or out, n out of range) fail with 1 before any HIP call and set the context's error; a HIP
+ * error fails with 1 through the context's error.  Synchronous, on the context's stream.  On the device: the matrix
+ * (8 n^2 bytes).  There is no batch form: the scores are asked of the point estimate only. */
+typedef struct {
+	uint64_t sum, quartets;
+} andi_hip_delta; /* 16 bytes */
+int andi_hip_delta_scores(andi_hip_ctx *ctx, const double *D, size_t n, andi_hip_delta *out /* n records */);
 
 /* Distance-based placement of queries on a neighbor-joining tree (least-squares placement, as APPLES does it): for every
  * query, the edge of the tree, the point on it and the length of the branch hanging there that fit the query's distances
