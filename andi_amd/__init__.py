@@ -13,5 +13,6 @@ from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_rang
                   FILL, complete, complete_batch,
                   DELTA, delta_scores,
                   PLACEMENT, distances_rect, jplace, parse_newick, place,
+                  ROOT, newick_rooted, root,
                   Sketches, screen, screen_select, sketch, sketch_shared,
                   scan_rows, subject_prepare, suffix_array)

@@ -457,6 +457,116 @@ size_t andi_hip_format_newick_transfer(const andi_hip_nj_join *J, const uint32_t
 	return format_newick(J, NULL, depth, transfer, used, n, names, truncate_names, 0, out, cap);
 }
 
+/* the label of the edge above node v in a rooted text: that of pair record v - n, if there is one */
+static void put_edge_label(sink *o, const char *const *labels, size_t n, size_t v) {
+	if (labels && v >= n && v < 2 * n - 3 && labels[v - n]) put(o, "%s", labels[v - n]);
+}
+
+/* T(v) of andi_hip_format_newick_rooted: the subtree below node v with its label, without its length; the walk of
+ * format_newick.  stack: room for n - 2 frames */
+typedef struct {
+	size_t rec;
+	int next;
+	double len;
+} rooted_frame;
+static void put_subtree(sink *o, const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+						const char *const *labels, size_t v, rooted_frame *stack) {
+	if (v < n) {
+		put_leaf(o, names[v], truncate_names);
+		return;
+	}
+	size_t top = 0;
+	stack[top++] = (rooted_frame){v - n, 0, 0.0};
+	put(o, "(");
+	while (top) {
+		rooted_frame *f = &stack[top - 1];
+		const andi_hip_nj_join *r = &J[f->rec];
+		if (f->next == 2) {
+			const double len = f->len;
+			const size_t rec = f->rec;
+			top--;
+			put(o, ")");
+			put_edge_label(o, labels, n, n + rec);
+			if (top) put(o, ":%.8g", len);
+			continue;
+		}
+		const int k = f->next++;
+		if (k) put(o, ",");
+		const size_t child = (size_t)(k == 0 ? r->a : r->b);
+		const double len = k == 0 ? r->la : r->lb;
+		if (child < n) {
+			put_leaf(o, names[child], truncate_names);
+			put(o, ":%.8g", len);
+		} else {
+			stack[top++] = (rooted_frame){child - n, 0, len};
+			put(o, "(");
+		}
+	}
+}
+
+size_t andi_hip_format_newick_rooted(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+									 int32_t edge, double distal, const char *const *labels, char *out, size_t cap) {
+	sink o = {out, cap, 0};
+	if (out && cap) out[0] = '\0';
+	if (!J || !names || n < 3 || edge < 0 || (size_t)edge >= 2 * n - 3 || !isfinite(distal)) return 0;
+	const size_t pairs = n - 3, E = 2 * n - 3, C = E;
+	size_t *par = malloc(E * sizeof *par);
+	double *len = malloc(E * sizeof *len);
+	rooted_frame *stack = malloc((pairs + 1) * sizeof *stack);
+	size_t *path = malloc((pairs + 2) * sizeof *path);
+	size_t ret = 0;
+	if (!par || !len || !stack || !path) goto done;
+	for (size_t v = 0; v < E; v++) par[v] = (size_t)-1;
+	for (size_t s = 0; s <= pairs; s++) { /* every child a leaf or an earlier record's node, and a child once */
+		const int32_t ch[3] = {J[s].a, J[s].b, J[s].c};
+		const double l[3] = {J[s].la, J[s].lb, J[s].lc};
+		const int kids = s == pairs ? 3 : 2;
+		for (int k = 0; k < kids; k++) {
+			if (ch[k] < 0 || (size_t)ch[k] >= n + s || (size_t)ch[k] >= n + pairs || par[ch[k]] != (size_t)-1) goto done;
+			par[ch[k]] = s == pairs ? C : n + s, len[ch[k]] = l[k];
+		}
+	}
+	/* (2 * pairs + 3 = E children, none twice: every node has its parent) */
+	const size_t v = (size_t)edge;
+	size_t m = 0; /* the nodes from parent(edge) up to the centre */
+	for (size_t q = par[v]; ; q = par[q]) {
+		path[m++] = q;
+		if (q == C) break;
+	}
+	put(&o, "(");
+	put_subtree(&o, J, n, names, truncate_names, labels, v, stack);
+	put(&o, ":%.8g,", distal);
+	for (size_t j = 0; j < m; j++) { /* U(path[j]): its children but the one the path came through, then the level above */
+		const size_t q = path[j], from = j ? path[j - 1] : v;
+		const andi_hip_nj_join *r = &J[q == C ? pairs : q - n];
+		const int kids = q == C ? 3 : 2;
+		put(&o, "(");
+		int first = 1;
+		for (int k = 0; k < kids; k++) {
+			const size_t child = (size_t)(k == 0 ? r->a : k == 1 ? r->b : r->c);
+			if (child == from) continue;
+			if (!first) put(&o, ",");
+			first = 0;
+			put_subtree(&o, J, n, names, truncate_names, labels, child, stack);
+			put(&o, ":%.8g", len[child]);
+		}
+		if (j + 1 < m) put(&o, ",");
+	}
+	for (size_t j = m; j-- > 0;) {
+		const size_t from = j ? path[j - 1] : v;
+		put(&o, ")");
+		put_edge_label(&o, labels, n, from);
+		put(&o, ":%.8g", j ? len[from] : len[v] - distal);
+	}
+	put(&o, ");\n");
+	if (out && cap) out[o.len < cap ? o.len : cap - 1] = '\0';
+	ret = o.len;
+done:
+	free(par), free(len), free(stack), free(path);
+	if (!ret && out && cap) out[0] = '\0';
+	return ret;
+}
+
 /* ------------------------------------------------------------------ */
 /* The majority-rule consensus tree of a bootstrap (include/andi_hip.h) */
 /* ------------------------------------------------------------------ */

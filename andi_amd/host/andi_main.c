@@ -420,6 +420,15 @@ static void usage(int status) {
 		"                       over all quartets of genomes that contain it (Holland et al. 2002: 0 where the distances fit\n"
 		"                       a tree, towards 1 where they do not) and the number of those quartets; on the GPU, from the\n"
 		"                       first matrix as it is printed (--complete does not change it)\n"
+		"      --root=METHOD    Write every tree of --tree, --support and --transfer rooted: by 'mad' (minimal ancestor deviation,\n"
+		"                       Tria et al. 2017: the point whose distances to the leaves disagree least with a clock, over all\n"
+		"                       leaf pairs) or at the 'midpoint' of the longest path; on the GPU, each tree with its own root.\n"
+		"                       Support and TBE labels stay with their branches.  The consensus tree is not rooted, and a\n"
+		"                       rooted file is no --backbone: that goes on requiring an unrooted tree\n"
+		"      --root-report=FILE  With --root: write the root of the first matrix's tree to FILE, tab-separated: the method,\n"
+		"                       the branch (its jplace edge number), the distance from the branch's lower end, the branch's\n"
+		"                       length, the score sqrt(SS / pairs), the root ambiguity index and the number of leaf pairs used\n"
+		"                       ('nan' for score and ambiguity under midpoint)\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -518,12 +527,67 @@ typedef struct {
 	size_t used;
 	const andi_hip_cons_node *nodes;
 	size_t ninner;
+	andi_hip_ctx *ctx; /* --root: the context the tree is rooted on */
+	int point;         /* --root-report: this is the point estimate's tree */
 } newick_src;
+
+/* --root: every line of records J is written rooted (andi_hip_root, andi_hip_format_newick_rooted), with the labels that
+ * belong to its branches moved with them; the consensus tree is not.  --root-report: the point estimate's root. */
+typedef struct {
+	int on, method, reported;
+	const char *report_path;
+	FILE *rf;
+} root_opts;
+static root_opts rootopt;
 
 static size_t format_newick(const newick_src *w, const char **names, size_t n, int truncate, char *text, size_t cap) {
 	if (w->nodes) return andi_hip_format_newick_consensus(w->nodes, n, w->ninner, names, truncate, text, cap);
 	if (w->depth) return andi_hip_format_newick_transfer(w->J, w->depth, w->transfer, w->used, n, names, truncate, text, cap);
 	return andi_hip_format_newick_support(w->J, w->support, n, names, truncate, text, cap);
+}
+
+/* The line of format_newick rooted, or NULL (and a soft warning) if the tree could not be rooted: the labels are the
+ * strings format_newick prints behind the pair records' nodes.  The point estimate's root goes to --root-report, once. */
+static char *rooted_newick(const newick_src *w, const char **names, size_t n, int truncate) {
+	andi_hip_root_result r;
+	if (andi_hip_root(w->ctx, w->J, n, rootopt.method, &r, NULL, NULL)) {
+		soft_warnx("A tree is written without a root: %s", andi_hip_last_error(w->ctx));
+		return NULL;
+	}
+	if (w->point && rootopt.rf && !rootopt.reported++) {
+		double len = 0.0;
+		for (size_t s = 0; s + 2 < n; s++) {
+			if (w->J[s].a == r.edge) len = w->J[s].la;
+			if (w->J[s].b == r.edge) len = w->J[s].lb;
+			if (s + 3 == n && w->J[s].c == r.edge) len = w->J[s].lc;
+		}
+		const int mad = rootopt.method == ANDI_ROOT_MAD;
+		double score = mad ? sqrt(r.ss / (double)r.pairs) : NAN, ambiguity = mad ? sqrt(r.ss / r.ss_second) : NAN;
+		if (isnan(score)) score = NAN; /* (0 / 0 carries a sign that would be printed) */
+		if (isnan(ambiguity)) ambiguity = NAN;
+		fprintf(rootopt.rf, "%s\t%d\t%.8g\t%.8g\t%.8g\t%.8g\t%llu\n", mad ? "mad" : "midpoint", (int)r.edge, r.distal, len, score,
+				ambiguity, (unsigned long long)r.pairs);
+		if (ferror(rootopt.rf)) err(1, "%s", rootopt.report_path);
+	}
+	const size_t nlab = n - 3;
+	char (*buf)[32] = NULL;
+	const char **labels = NULL;
+	if (nlab && (w->support || w->depth)) {
+		buf = xmalloc(nlab * sizeof *buf), labels = xmalloc(nlab * sizeof *labels);
+		for (size_t s = 0; s < nlab; s++) {
+			if (w->support) snprintf(buf[s], sizeof buf[s], "%u", (unsigned)w->support[s]);
+			else snprintf(buf[s], sizeof buf[s], "%.6g", 1.0 - (double)w->transfer[s] / ((double)w->used * (double)(w->depth[s] - 1)));
+			labels[s] = buf[s];
+		}
+	}
+	size_t cap = 96 + n * (labels ? 92 : 44);
+	for (size_t i = 0; i < n; i++) cap += strlen(names[i]) * 2 + 2;
+	char *text = xmalloc(cap);
+	const size_t need = andi_hip_format_newick_rooted(w->J, n, names, truncate, r.edge, r.distal, labels, text, cap);
+	if (need >= cap)
+		free(text), cap = need + 1, text = xmalloc(cap), andi_hip_format_newick_rooted(w->J, n, names, truncate, r.edge, r.distal, labels, text, cap);
+	free(buf), free(labels);
+	return text;
 }
 
 /* one Newick line to the file o */
@@ -533,6 +597,10 @@ static void put_newick(const tree_file *o, const newick_src *w, const char **nam
 	char *text = xmalloc(cap);
 	const size_t need = format_newick(w, names, n, truncate, text, cap);
 	if (need >= cap) free(text), cap = need + 1, text = xmalloc(cap), format_newick(w, names, n, truncate, text, cap);
+	if (rootopt.on && need && w->J && w->ctx && n >= 3) { /* (a text that is refused stays refused; two leaves have no root to find) */
+		char *rooted = rooted_newick(w, names, n, truncate);
+		if (rooted) free(text), text = rooted;
+	}
 	if (fputs(text, o->f) == EOF) err(1, "%s", o->path);
 	free(text);
 }
@@ -701,7 +769,7 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
 		free(D), free(J);
 		return;
 	}
-	put_newick(t->o, &(newick_src){.J = J}, names, n, truncate);
+	put_newick(t->o, &(newick_src){.J = J, .ctx = t->ctx, .point = k == 1}, names, n, truncate);
 	free(D), free(J);
 }
 
@@ -831,7 +899,7 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			if (skip[k])
 				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s'%s", first + (unsigned long)k + 2,
 						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name, NOT_FINITE);
-			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec}, s->r.names, n, s->r.truncate);
+			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec, .ctx = ctx}, s->r.names, n, s->r.truncate);
 			s->counted += !skip[k];
 		}
 		/* (whatever fails below, the replicates' lines of --tree are still written) */
@@ -871,7 +939,7 @@ static void support_end(support_state *s, int complete) {
 	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = s->rogue_ok = 0;
 	if (s->point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total}, names, n, s->r.truncate);
+		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total, .ctx = ctx, .point = 1}, names, n, s->r.truncate);
 	}
 	if (s->trans_ok && counted == 0) {
 		soft_warnx("No transfer support: no bootstrap matrix has a tree.");
@@ -879,7 +947,7 @@ static void support_end(support_state *s, int complete) {
 	}
 	if (s->trans_ok) {
 		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted}, names, n,
+		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted, .ctx = ctx, .point = 1}, names, n,
 				   s->r.truncate);
 	}
 	if (s->rogue_ok && counted == 0) {
@@ -1280,6 +1348,8 @@ int main(int argc, char *argv[]) {
 												 {"complete", no_argument, NULL, 0},
 												 {"complete-report", required_argument, NULL, 0},
 												 {"delta", required_argument, NULL, 0},
+												 {"root", required_argument, NULL, 0},
+												 {"root-report", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1331,6 +1401,13 @@ int main(int argc, char *argv[]) {
 				if (!strcmp(o, "complete")) cmpl.on = 1;
 				if (!strcmp(o, "complete-report")) cmpl.on = 1, cmpl.report_path = optarg;
 				if (!strcmp(o, "delta")) dlt.path = optarg;
+				if (!strcmp(o, "root")) {
+					if (!strcasecmp(optarg, "mad")) rootopt.method = ANDI_ROOT_MAD;
+					else if (!strcasecmp(optarg, "midpoint")) rootopt.method = ANDI_ROOT_MIDPOINT;
+					else errx(1, "Expected one of 'mad' or 'midpoint' for --root, but '%s' was given.", optarg);
+					rootopt.on = 1;
+				}
+				if (!strcmp(o, "root-report")) rootopt.report_path = optarg;
 				if (!strcmp(o, "rogues")) rogues.path = optarg;
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
@@ -1465,6 +1542,7 @@ int main(int argc, char *argv[]) {
 	if (clus.dendro_path && trees_only) errx(1, "A dendrogram (--dendrogram) is not available together with --trees-only: there are no matrices to cluster.");
 	if (clus.clusters_path && trees_only) errx(1, "Clusters (--clusters) are not available together with --trees-only: there are no matrices to cluster.");
 	if (dlt.path && rect) errx(1, "Tree-likeness scores (--delta) are" WITH_REFERENCE);
+	if (rootopt.report_path && !rootopt.on) errx(1, "A root report (--root-report) needs a rooting method: give --root=mad or --root=midpoint.");
 	if (cmpl.on && trees_only)
 		errx(1, "Missing distances (--complete) are not derived together with --trees-only: the bootstrap matrices stay on the GPU.");
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
@@ -1493,6 +1571,10 @@ int main(int argc, char *argv[]) {
 	if (rogues.path && !(rogues.f = fopen(rogues.path, "w"))) err(1, "%s", rogues.path);
 	if (cmpl.report_path && !(cmpl.rf = fopen(cmpl.report_path, "w"))) err(1, "%s", cmpl.report_path);
 	if (dlt.path && !(dlt.f = fopen(dlt.path, "w"))) err(1, "%s", dlt.path);
+	if (rootopt.report_path) {
+		if (!(rootopt.rf = fopen(rootopt.report_path, "w"))) err(1, "%s", rootopt.report_path);
+		fputs("#method\tedge\tdistal\tlength\tscore\tambiguity\tpairs\n", rootopt.rf);
+	}
 	if (clus.dendro_path && !(clus.df = fopen(clus.dendro_path, "w"))) err(1, "%s", clus.dendro_path);
 	if (clus.clusters_path && !(clus.cf = fopen(clus.clusters_path, "w"))) err(1, "%s", clus.clusters_path);
 	if (place.path && !(place.f = fopen(place.path, "w"))) err(1, "%s", place.path);
@@ -1608,6 +1690,7 @@ int main(int argc, char *argv[]) {
 	if (rogues.f && fclose(rogues.f)) err(1, "%s", rogues.path);
 	if (cmpl.rf && fclose(cmpl.rf)) err(1, "%s", cmpl.report_path);
 	if (dlt.f && fclose(dlt.f)) err(1, "%s", dlt.path);
+	if (rootopt.rf && fclose(rootopt.rf)) err(1, "%s", rootopt.report_path);
 	free(M);
 	free(in);
 	free(names);

@@ -136,6 +136,9 @@ SYMBOLS = {
     "andi_hip_delta_scores": (C.c_int, [_P, _P, C.c_size_t, _P]),
     "andi_hip_place": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t, C.c_int, _P, _P, _P, _P]),
     "andi_hip_distances_rect": (C.c_int, [_P, _P, C.c_size_t, C.c_size_t, C.c_int, _P]),
+    "andi_hip_root": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P]),
+    "andi_hip_format_newick_rooted": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, C.c_int32, C.c_double,
+                                                   C.POINTER(C.c_char_p), _P, C.c_size_t]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
                                             C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
@@ -1119,6 +1122,55 @@ def place(ctx: Context, J, D, method="fm", per=False):
     ctx._check(load().andi_hip_place(ctx._h, J.ctypes.data, n, D.ctypes.data, nq, m, out.ctypes.data,
                                      *[r.ctypes.data if per else None for r in rows]), "place")
     return (out, *rows) if per else out
+
+
+# andi_hip_root_result: the root of a tree (the edge and the distance from its child end), MAD's sum of squared deviations
+# there, the used leaf pairs, the least sum among the other edges, and the used pair of the greatest path length
+ROOT = np.dtype([("edge", "<i4"), ("pad", "<u4"), ("distal", "<f8"), ("ss", "<f8"), ("pairs", "<u8"), ("ss_second", "<f8"),
+                 ("far_b", "<i4"), ("far_c", "<i4")])
+ROOT_METHODS = {"mad": 0, "midpoint": 1}
+
+
+def root(ctx: Context, J, method="mad", per=False):
+    """The root of the tree J (n - 2 records of nj, tree or parse_newick) on the device (andi_hip_root): a record of dtype
+    ROOT -- the edge, the distance `distal` from its child end, and under "mad" the sum ss of squared deviations there, the
+    number of used leaf pairs and the least sum among the other edges (the score is sqrt(ss / pairs), the root ambiguity
+    index sqrt(ss / ss_second)); under "midpoint" ss and ss_second are 0.  With per=True (mad only) also the (2n - 3,)
+    float64 arrays x and ss of every edge."""
+    if str(method).lower() not in ROOT_METHODS:
+        raise ValueError("method must be one of %s" % sorted(ROOT_METHODS))
+    m = ROOT_METHODS[str(method).lower()]
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    out = np.zeros(1, ROOT)
+    rows = [np.zeros(2 * n - 3, np.float64) for _ in range(2)] if per else [None] * 2
+    ctx._check(load().andi_hip_root(ctx._h, J.ctypes.data, n, m, out.ctypes.data,
+                                    *[r.ctypes.data if per else None for r in rows]), "root")
+    return (out[0], *rows) if per else out[0]
+
+
+def newick_rooted(joins, names, edge, distal, labels=None, truncate_names=False):
+    """The Newick line of nj's records rooted on `edge`, `distal` from its child end (andi_hip_format_newick_rooted);
+    labels: None, or n - 3 strings (or None) that belong to the edges above the pair records' nodes and move with them; ""
+    where the library refuses (malformed records, an edge out of range)."""
+    J = np.ascontiguousarray(joins, dtype=NJ_JOIN)
+    n = len(names)
+    cn = _names(names)
+    cl, extra = None, 0
+    if labels is not None:
+        assert len(labels) >= max(n - 3, 0)
+        enc = [None if x is None else str(x).encode() for x in labels[:max(n - 3, 0)]]
+        cl = (C.c_char_p * max(len(enc), 1))(*enc)
+        extra = 2 * sum(len(x) + 1 for x in enc if x is not None)
+    cap = 96 + 40 * n + sum(len(x) for x in names) + extra
+    for _ in range(2):  # (the call returns the bytes it needs)
+        out = C.create_string_buffer(cap)
+        need = load().andi_hip_format_newick_rooted(J.ctypes.data, n, cn, int(truncate_names), int(edge), float(distal), cl,
+                                                    C.cast(out, _P), cap)
+        if need < cap:
+            break
+        cap = need + 1
+    return out.value.decode()
 
 
 def nj_support(ctx: Context, J, reps, skip=None):

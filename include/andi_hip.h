@@ -29,7 +29,8 @@
  * andi_hip_sketch_shared, andi_hip_screen_select and andi_hip_screen (additions only); and the tree builder by method
  * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only); and missing
  * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only);
- * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only).
+ * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only); and the root of
+ * a tree without an outgroup: andi_hip_root and andi_hip_format_newick_rooted (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -788,6 +789,80 @@ int andi_hip_parse_newick(const char *text, const char *const *names, size_t n, 
 size_t andi_hip_format_jplace(const andi_hip_nj_join *tree, size_t n, const char *const *ref_names, int truncate_names,
 							  const andi_hip_placement *placements, size_t nq, const char *const *query_names, int method,
 							  char *out, size_t cap);
+
+/* The root of a neighbor-joining tree without an outgroup: minimal ancestor deviation (MAD; Tria, Landan and Dagan,
+ * Nat. Ecol. Evol. 2017) or the midpoint of the longest path.  tree: the n - 2 records of andi_hip_nj / andi_hip_tree /
+ * andi_hip_parse_newick for n leaves (validated on the host by andi_hip_place's rule); method: ANDI_ROOT_MAD or
+ * ANDI_ROOT_MIDPOINT; out: one record; per_x, per_ss: NULL, or 2n - 3 doubles each, x and SS of every edge (MAD only).
+ * 3 <= n <= 65535.  Bad arguments (a NULL ctx, tree or out, n out of range, a method outside 0 ... 1), a branch length that
+ * is not finite and records that are not andi_hip_nj's fail with 1 before any HIP call, through the context's error, and
+ * write nothing.  Synchronous, on the context's stream.
+ *
+ * The result is bit-exact to this contract (tests/root_model.py restates it); every operation is an IEEE double operation
+ * rounded on its own (no a*b+c contracted into an FMA), every sum sequential in the order given:
+ *  - the tree: leaf i has id i, pair record s < n - 3 makes node n + s, the final record the centre C = 2n - 3.  parent(v)
+ *    and len(v) come from the record that has v as a child (la, lb or lc).  There are 2n - 3 edges; edge v, 0 <= v < 2n - 3,
+ *    joins v to parent(v) (its jplace edge number as well).  Negative lengths are kept as they are;
+ *  - path lengths h(v, i) from node v to leaf i: h(i, i) = +0.0; upwards from i to C, h(parent(v), i) = h(v, i) + len(v);
+ *    for every other node c, in descending id order, h(c, i) = h(parent(c), i) + len(c).  below(v, i) iff v lies on the
+ *    path from i to C;
+ *  - the near-end distance t_v(i) = below(v, i) ? h(v, i) : h(parent(v), i), from the end of edge v on leaf i's side;
+ *  - the patristic distance of the leaves b < c: p(b, c) = t_b(c) + len(b) = h(parent(b), c) + len(b), edge b being leaf b's
+ *    own (the chain that ends at the LOWER leaf's branch; it is h(b, c)).  The pair is USED iff p is finite and p > 0:
+ *    identical genomes and negative branches can give p <= 0, and such a pair counts for nothing, on every edge alike.
+ *    pairs is the number of used pairs;
+ *  - per edge v, with L = len(v) and Lc = L > 0 ? L : +0.0, pass 1 over the used pairs that STRADDLE the edge, those with
+ *    below(v, b) != below(v, c): a is the one of b, c below v; N += (p - 2*t_v(a)) / (p*p), W += 1.0 / (p*p).  Then
+ *    x = W == 0.0 ? +0.0 : clamp(N / (2*W)), clamp(a) = a > 0 ? (a < Lc ? a : Lc) : +0.0 (a NaN gives +0.0).  x is the
+ *    distance of the root from the child end v of the edge (jplace's distal end, as in andi_hip_placement);
+ *  - pass 2 over all used pairs, SS += r*r: for a straddling pair r = (2*d) / p - 1.0 with d the distance from b, the
+ *    lower-numbered leaf, to the root: d = below(v, b) ? t_v(b) + x : t_v(b) + (L - x); for a pair on one side
+ *    r = (t_v(b) - t_v(c)) / p (their deepest common ancestor under a root on edge v is the point of their path nearest
+ *    to the edge, and 2*d(b, anc)/p - 1 reduces to this);
+ *  - the order of the sums, in both passes: for a fixed (v, b) the inner sum over c > b ascending, from +0.0 (in pass 1 a
+ *    pair that does not straddle adds nothing); then the inner sums are added over b ascending, from +0.0;
+ *  - the choice: the edge with the least SS by value, ties to the smaller v, a NaN after every number.  The record is
+ *    {v, 0, x, SS, pairs, ss_second, far_b, far_c}, ss_second the least SS among the other edges by the same order.  With
+ *    no used pair every SS and x is +0.0 and edge 0 is chosen.  The score sqrt(ss / pairs) and the root ambiguity index
+ *    sqrt(ss / ss_second) are left to the caller;
+ *  - far_b < far_c is the used pair of the greatest p, ties to the first in (b, c) order; -1, -1 without a used pair.  Both
+ *    methods fill it;
+ *  - ANDI_ROOT_MIDPOINT: the root is the point at p*0.5 from far_b on the path to far_c.  The walk: rem = p*0.5; over the
+ *    edges v of the path in order from far_b -- first upwards (towards C) to the node where the paths of far_b and far_c to
+ *    C meet, then downwards to far_c --: if rem < len(v) the edge holds the root, at distal = rem on the way up and
+ *    distal = len(v) - rem on the way down; otherwise rem = rem - len(v).  So a point that falls on a node belongs to the
+ *    NEXT edge of the path, at that node's end of it, and an edge of length <= 0 never holds the root; if no edge takes it
+ *    (rounding, negative lengths) it is far_c's edge at distal +0.0.  ss and ss_second are +0.0, per_x and per_ss are
+ *    untouched; without a used pair the record is {0, 0, +0.0, +0.0, 0, +0.0, -1, -1}.
+ * On the device: andi_hip_place's table of the (2n - 3) x n path lengths, 8 bytes each; when it does not fit the call fails
+ * through the context's error, which names the bytes.  Under MAD the leaves b are taken in groups that fit (16 (2n - 3)
+ * bytes a leaf); the results do not depend on the grouping.  Work: (2n - 3) * n(n - 1)/2 pair visits, twice -- measured on
+ * one MI355X, 66 ms at 3085 leaves with the copies, 4.5 ms for the midpoint. */
+enum { ANDI_ROOT_MAD = 0, ANDI_ROOT_MIDPOINT = 1 };
+typedef struct {
+	int32_t edge;
+	uint32_t pad;
+	double distal, ss;
+	uint64_t pairs;
+	double ss_second;
+	int32_t far_b, far_c;
+} andi_hip_root_result; /* 48 bytes */
+int andi_hip_root(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, int method, andi_hip_root_result *out,
+				  double *per_x, double *per_ss);
+/* andi_hip_format_newick's text of the records J rooted on `edge` (0 <= edge < 2n - 3, n >= 3), `distal` from the edge's
+ * child end: "(" T(child) ":" L(distal) "," U ":" L(len(edge) - distal) ");\n", L is %.8g, len(edge) - distal one rounded
+ * subtraction.  T(v) is the subtree below v as andi_hip_format_newick prints it.  U is the rest of the tree seen from
+ * parent(edge) = q: "(" then the other children of q in record order, as T(.) with their lengths, then, unless q is the
+ * centre, "," U(q) ":" L(len(q)), the same construction one level up, then ")".  The old centre becomes an ordinary inner
+ * node with two children (its three without the one the path to the root passes through).
+ * labels: NULL, or n - 3 strings (an entry may be NULL: no label), one per pair record s; a label belongs to the EDGE
+ * n + s and stands behind the ")" of whichever end of that edge is the lower one in the rooted tree: node n + s itself, or,
+ * on the path from the centre to the root, its former parent (the group U(n + s)); if the root edge is an inner edge both
+ * root children that are inner nodes carry its label.  The strings are printed as they are.
+ * Not recursive.  Return value, cap and malformed records as andi_hip_format_newick; an edge out of range, n < 3 and a
+ * distal that is not finite give 0 and an empty string too.  No GPU is touched. */
+size_t andi_hip_format_newick_rooted(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
+									 int32_t edge, double distal, const char *const *labels, char *out, size_t cap);
 
 /* ------------------------------------------------------------------ */
 /* The k-mer sketch screen: which references are worth an exact run    */
