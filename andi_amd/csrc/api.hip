@@ -394,6 +394,8 @@ void andi_hip_ctx_destroy(andi_hip_ctx *ctx) {
 	(void)hipSetDevice(ctx->device);
 	if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
 	resolve_events(ctx);
+	for (hipEvent_t ev : ctx->idle_events) (void)hipEventDestroy(ev);
+	ctx->idle_events.clear();
 	if (ctx->scratch) (void)andi_arena::dev_free(ctx->scratch);
 	if (ctx->desc_dev) (void)andi_arena::dev_free(ctx->desc_dev);
 	if (ctx->desc_host) host_pool::pinned_put(ctx->desc_host, ctx->desc_bytes);
@@ -812,6 +814,40 @@ extern "C" int andi_hip_test_coop_items(andi_hip_ctx *ctx, uint32_t *items, size
 	if (items && l.items && ni) HIP_TRY(ctx, hipMemcpy(items, l.items, ni * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	if (pair_class && l.pair_class && np) HIP_TRY(ctx, hipMemcpy(pair_class, l.pair_class, np, hipMemcpyDeviceToHost));
 	if (pair_cost && l.pair_cost && np) HIP_TRY(ctx, hipMemcpy(pair_cost, l.pair_cost, np, hipMemcpyDeviceToHost));
+	return 0;
+}
+// What the context's last routed scan call enqueued around pass A (scan_call.hip: launch_routed), per layout -- 0 the lane scan's, 1 the
+// wavefront kernel's, 2 the pairs handed back: out[k] = 1 if layout k's pass A was enqueued, out[3 + k] = its rounds of stitching again (both set where the launches are made);
+// out[6] = 1 if the call went ahead of the pending index builds (scan_call.hip: upload_descriptors), out[7] = 1 if a raised flag made it run again.
+// count_b (may be NULL): the 16 words of the wavefront kernel's restitch_count as pass B left them (scan.h: [0 .. 2] stretches stitched again
+// per round, [3] true chains that left their segment on their own, [8] the first stage's list).  All zero where the last call was not routed.
+extern "C" int andi_hip_test_call_edges(andi_hip_ctx *ctx, uint32_t *out, uint32_t *count_b) {
+	if (!ctx || !out) return 1;
+	const auto &l = ctx->last_edges;
+	for (int k = 0; k < 3; ++k) out[k] = l.pass_a[k], out[3 + k] = l.rounds[k];
+	out[6] = l.went_ahead, out[7] = l.ran_again;
+	if (!count_b) return 0;
+	for (int k = 0; k < 16; ++k) count_b[k] = 0;
+	if (!l.count_b) return 0;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	HIP_TRY(ctx, hipMemcpy(count_b, l.count_b, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	return 0;
+}
+// The lane layout of the context's last routed scan call as it lies in the call's scratch after the call (scan.h): pair_waves (pairs words),
+// pair_wave0 (pairs + 1 words; only where the lanes' segment lengths are per pair), sub_order (nsub words) and the layout's sixteen counters
+// as the host's first look saw them.  info = { pairs, subjects, 1 if pair_wave0 is there, 1 if the host looked }.  Any pointer may be NULL.
+extern "C" int andi_hip_test_pair_layout(andi_hip_ctx *ctx, uint32_t *pair_waves, uint32_t *pair_wave0, uint32_t *sub_order, uint32_t *counts, uint32_t *info) {
+	if (!ctx) return 1;
+	const auto &l = ctx->last_items;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	if (info) info[0] = l.pairs, info[1] = l.nsub, info[2] = l.pair_wave0 ? 1u : 0u, info[3] = l.looked;
+	if (pair_waves && l.pair_waves && l.pairs) HIP_TRY(ctx, hipMemcpy(pair_waves, l.pair_waves, l.pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (pair_wave0 && l.pair_wave0 && l.pairs) HIP_TRY(ctx, hipMemcpy(pair_wave0, l.pair_wave0, ((size_t)l.pairs + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (sub_order && l.sub_order && l.nsub) HIP_TRY(ctx, hipMemcpy(sub_order, l.sub_order, l.nsub * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (counts)
+		for (int k = 0; k < 16; ++k) counts[k] = l.counts[k];
 	return 0;
 }
 // The per-slot records of the context's last scan call that used ONE segment length (not routed, no per-pair lengths), as they lie in lane

@@ -59,7 +59,9 @@ struct andi_hip_ctx {
 	uint32_t *h_quad_waves = nullptr; // pinned: the length of k_lane_quad's list of a scan call
 	hipStream_t coop_stream = nullptr; // routed scan calls: pass A by wavefronts runs beside the lane scan's kernels
 	hipEvent_t coop_fork = nullptr, coop_join = nullptr, l2_fork = nullptr, l2_join = nullptr;
-	uint32_t *h_any_left = nullptr;    // pinned: [0] the wavefront kernel handed some pair back, [1 + k] the layout's counter restitch_count[k] (ANDI_LANE_WAVES: wavefronts of the lane layout, ...)
+	// pinned, 64 words: [0] the wavefront kernel handed some pair back, [1 + k] the layout's counter restitch_count[k] (ANDI_LANE_WAVES: wavefronts of
+	// the lane layout, ...) at the first look, [ANDI_LOOK_B + k] restitch_count[k] of the wavefront kernel's layout at the look behind its pass A
+	uint32_t *h_any_left = nullptr;
 	void *pool_scratch = nullptr;      // pass A by wavefronts with pooled walks (coop_pool.h): a scratch per resident wavefront
 	size_t pool_bytes = 0;
 	uint32_t pool_waves = 0;
@@ -73,9 +75,14 @@ struct andi_hip_ctx {
 		const uint32_t *items = nullptr;
 		const uint8_t *pair_class = nullptr, *pair_cost = nullptr;
 		uint32_t n_items = 0, pairs = 0, total_segs = 0;
+		// (andi_hip_test_pair_layout) the lane layout's arrays in the call's scratch -- pair_wave0 only where the lanes' segment lengths are per
+		// pair --, its subjects, and its sixteen counters as the host's first look saw them (looked: the call did look)
+		const uint32_t *pair_waves = nullptr, *pair_wave0 = nullptr, *sub_order = nullptr;
+		uint32_t nsub = 0, looked = 0, counts[16] = {};
 	} last_items;
 	unsigned long long *d_route = nullptr; // routed scan calls: query nucleotides whose pass A ran by wavefronts / by lanes, pairs handed back (read with the timings)
 	std::vector<EventPair> pending;
+	std::vector<hipEvent_t> idle_events; // the timers' events between uses (Timed, resolve_events): created once, destroyed with the context
 	andi_hip_timings acc{};
 #ifdef ANDI_TEST_HOOKS
 	// (the suite's library only: every translation unit that sees this struct is compiled a second time for it, Makefile: HOOKOBJ)
@@ -88,8 +95,16 @@ struct andi_hip_ctx {
 		const ColdMark *marks = nullptr;
 		uint32_t nsub = 0, total_segs = 0, seg = 0;
 	} last_slots;
+	// the last routed scan call, per layout (0 a: the lane scan's, 1 b: the wavefront kernel's, 2 a2: the pairs handed back): whether its pass A
+	// was enqueued and how many rounds of stitching again were, and where pass B of layout b counted -- what the suite's hook andi_hip_test_call_edges reads
+	struct {
+		uint32_t pass_a[3] = {0, 0, 0}, rounds[3] = {0, 0, 0};
+		uint32_t went_ahead = 0, ran_again = 0; // the call did not wait for the pending builds (upload_descriptors); a raised flag made it run again
+		const uint32_t *count_b = nullptr; // layout b's restitch_count, in the call's scratch
+	} last_edges;
 #endif
 };
+#define ANDI_LOOK_B 32 /* andi_hip_ctx.h_any_left: where the second look's sixteen words go */
 
 struct andi_hip_esa {
 	uint8_t *S = nullptr;
@@ -225,8 +240,8 @@ void resolve_events(andi_hip_ctx *ctx) {
 				ctx->acc.stitch_launches++;
 			}
 		}
-		(void)hipEventDestroy(ev.a);
-		(void)hipEventDestroy(ev.b);
+		ctx->idle_events.push_back(ev.a); // (for the next timer: creating and destroying two events per timer, six to eight per scan call, was
+		ctx->idle_events.push_back(ev.b); // time of the host thread the device waits for behind every look of a routed call)
 	}
 	ctx->pending.clear();
 }
@@ -235,14 +250,25 @@ struct Timed {
 	andi_hip_ctx *ctx;
 	EventPair ev;
 	bool ok;
+	static bool take(andi_hip_ctx *c, hipEvent_t *e) { // an idle event of the context's, or a new one
+		if (c->idle_events.empty()) return hipEventCreate(e) == hipSuccess;
+		*e = c->idle_events.back();
+		c->idle_events.pop_back();
+		return true;
+	}
+	void give_back() {
+		ctx->idle_events.push_back(ev.a);
+		ctx->idle_events.push_back(ev.b);
+	}
 	Timed(andi_hip_ctx *c, int kind) : ctx(c), ok(false) {
 		ev.kind = kind;
-		if (hipEventCreate(&ev.a) != hipSuccess) return;
-		if (hipEventCreate(&ev.b) != hipSuccess) {
-			(void)hipEventDestroy(ev.a);
+		if (!take(c, &ev.a)) return;
+		if (!take(c, &ev.b)) {
+			c->idle_events.push_back(ev.a);
 			return;
 		}
 		ok = hipEventRecord(ev.a, c->stream) == hipSuccess;
+		if (!ok) give_back();
 	}
 	void stop() {
 		if (!ok) return;
@@ -251,10 +277,8 @@ struct Timed {
 		ok = false;
 		if (ctx->pending.size() > 256) resolve_events(ctx);
 	}
-	~Timed() { // an error exit before stop(): the events go with the timer
-		if (!ok) return;
-		(void)hipEventDestroy(ev.a);
-		(void)hipEventDestroy(ev.b);
+	~Timed() { // an error exit before stop(): the events go back unused
+		if (ok) give_back();
 	}
 	Timed(const Timed &) = delete;
 	Timed &operator=(const Timed &) = delete;

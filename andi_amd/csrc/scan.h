@@ -168,7 +168,8 @@ hipError_t andi_launch_pack_symbols(const uint8_t *src, size_t bytes, uint8_t *N
 // the bit-sliced form of 4-bit symbols (EsaDev.P): `symbols` of them from N0 (rounded up to blocks of 32) into planes
 hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *planes, uint32_t *codes, hipStream_t st);
 // adaptive mode: sample every pair's match lengths, choose its segment length (and, in a routed call, its pass A), lay out the slots
-hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st);
+// (more: sixteen further words to clear with the layout's own counters, or null -- a routed call's second restitch_count)
+hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st, uint32_t *more = nullptr);
 // routed calls: the second lane layout (a2: the pairs pass A by wavefronts handed back); who took what, for the timings
 hipError_t andi_launch_pair_leftover(const ScanArgs &a2, hipStream_t st);
 hipError_t andi_launch_route_count(const ScanArgs &a, hipStream_t st);
@@ -181,7 +182,18 @@ hipError_t andi_launch_coop_cold(const ScanArgs &a, hipStream_t st);
 int andi_coop_wants_pool(const ScanArgs &a); // a launch of pass A by wavefronts that k_pool_cold would take if the context had its scratch
 int andi_coop_will_pool(const ScanArgs &a); // that launch is k_pool_cold's (mode P, coop_pool.h), not k_coop_cold's
 size_t andi_pool_scratch_bytes(int device, uint32_t *waves); // the pooled kernels' scratch (4096 bytes for the ticket in front); 0: those kernels are off (ANDI_POOL=0)
-hipError_t andi_launch_lane_stitch(const ScanArgs &a, hipStream_t st);
+// Pass B's launches in parts, for a caller that looks at the first stage's counters before it decides on the rest (scan_call.hip:
+// launch_routed): the clearing of restitch_count's 16 words, the first stage with its list, the rounds that stitch again
+// INVARIANT a caller of ANDI_STITCH_STAGE0 without ANDI_STITCH_CLEAR vouches for (launch_routed does, for the wavefront kernel's layout): all
+// sixteen words of that layout's restitch_count are zero since the layout's clearing (k_layout_clear) except ANDI_ROUTE_ANY_LEFT, the one
+// word pass A by wavefronts writes there (coop_dev.h) and no stage of pass B reads or counts in.  Whoever lets a kernel between the layout
+// and pass B count in another of those words must give that call its clearing back.
+#define ANDI_STITCH_CLEAR 1u
+#define ANDI_STITCH_STAGE0 2u
+#define ANDI_STITCH_ROUNDS 4u
+#define ANDI_STITCH_ALL 7u
+// (rounds, where not null: the rounds of stitching again this call launched are added to it)
+hipError_t andi_launch_lane_stitch(const ScanArgs &a, hipStream_t st, unsigned parts = ANDI_STITCH_ALL, uint32_t *rounds = nullptr);
 hipError_t andi_launch_lane_quad_small(const ScanArgs &a, uint32_t count, hipStream_t st); // k_lane_quad, one wavefront per block (scan_lane.hip compiled a second time)
 // Pass B again for the segments that were entered in a state their predecessor's true chain did not leave in (a true
 // chain that runs on lucky anchors through a repeat in which cold chains find nothing unique): per round, k_stitch_heads
@@ -245,7 +257,7 @@ static_assert(ANDI_RESTITCH_ROUNDS < 8, "restitch_count[]: rounds 0 .. ROUNDS at
 #define ANDI_STITCH_TOGETHER 40 /* steps of pass B's phase 2 in which the cold chain is replayed beside the true one */
 #endif
 hipError_t andi_launch_scan_cold(const ScanArgs &a, hipStream_t st);
-hipError_t andi_launch_scan_stitch(const ScanArgs &a, hipStream_t st);
+hipError_t andi_launch_scan_stitch(const ScanArgs &a, hipStream_t st, unsigned parts = ANDI_STITCH_ALL, uint32_t *rounds = nullptr); // (the reference's walk goes with the rounds)
 hipError_t andi_launch_scan_reduce(const ScanArgs &a, hipStream_t st);
 hipError_t andi_launch_match_positions(const EsaDev &E, const uint8_t *q, uint32_t qlen,
 									   uint32_t first, uint32_t count, int cached,

@@ -597,9 +597,9 @@ hipError_t andi_launch_scan_cold(const ScanArgs &a, hipStream_t st) {
 	return a.exact_equal ? launch_reference<true>(a, st, false) : launch_reference<false>(a, st, false);
 }
 
-hipError_t andi_launch_scan_stitch(const ScanArgs &a, hipStream_t st) {
-	hipError_t e = andi_launch_lane_stitch(a, st);
-	if (e != hipSuccess || !a.any_reference) return e;
+hipError_t andi_launch_scan_stitch(const ScanArgs &a, hipStream_t st, unsigned parts, uint32_t *rounds) {
+	hipError_t e = andi_launch_lane_stitch(a, st, parts, rounds);
+	if (e != hipSuccess || !a.any_reference || !(parts & ANDI_STITCH_ROUNDS)) return e;
 	return a.exact_equal ? launch_reference<true>(a, st, true) : launch_reference<false>(a, st, true);
 }
 

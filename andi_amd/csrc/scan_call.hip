@@ -263,8 +263,12 @@ int carve_scratch(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size_t slot
 
 // the subjects' descriptors, [EsaDev x nsub][int64 x nsub] (pinned host -> device, guarded by desc_done): every subject's
 // walk as its index build's flags say.  Counts the pairs, their query nucleotides and the subjects on the reference's walk.
+// ahead: the caller is going to look at the device before pass A anyway (launch_routed) and checks the flags then -- where every subject has its
+// probe table and builds are still in flight, the descriptors are written for the probe walk WITHOUT waiting for them (*ahead stays set;
+// cleared where the wait was taken after all): the host enqueued the call's first kernels only once the builders had ended, 25 us of
+// idle device per call (profiles/r14_call_edges.md).
 int upload_descriptors(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const int64_t *self, size_t nsub, const andi_hip_queries *q,
-					   bool force_reference, int &any_reference, uint64_t &pairs, uint64_t &nt) {
+					   bool force_reference, int &any_reference, uint64_t &pairs, uint64_t &nt, bool *ahead) {
 	const size_t desc_need = nsub * (sizeof(EsaDev) + sizeof(int64_t));
 	if (ctx->desc_bytes < desc_need) {
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -285,7 +289,9 @@ int upload_descriptors(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 	// the index builds must have finished: their flags decide which walk is exact.  (Only the builds this context
 	// has queued since its last scan are waited for -- not whatever else is on the stream; subjects built by another
 	// context are the caller's to have synchronised, as before.)
-	if (ctx->builds_pending) {
+	*ahead = *ahead && ctx->builds_pending && !force_reference;
+	for (size_t s = 0; s < nsub && *ahead; ++s) *ahead = subjects[s] && subjects[s]->index_built;
+	if (ctx->builds_pending && !*ahead) {
 		HIP_TRY(ctx, hipEventSynchronize(ctx->built));
 		ctx->builds_pending = false;
 	}
@@ -294,6 +300,14 @@ int upload_descriptors(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 		if (!e || (!e->index_built && !e->ref_built)) {
 			ctx->err = "andi_hip_scan_rows: subject index not built";
 			return 1;
+		}
+		if (*ahead) { // (the flags are not final yet: taken to be clear, looked at behind the first look)
+			h_esa[s] = esa_view(e, ANDI_MODE_PROBE);
+			h_self[s] = self ? self[s] : -1;
+			const bool has_self = h_self[s] >= 0 && (size_t)h_self[s] < q->nq;
+			pairs += q->nq - (has_self ? 1 : 0);
+			nt += q->total_nt - (has_self ? q->len[(size_t)h_self[s]] : 0);
+			continue;
 		}
 		int mode = ANDI_MODE_PROBE;
 		if (!e->index_built || e->h_flags[0] != 0 || force_reference) {
@@ -411,8 +425,10 @@ hipError_t launch_direct(andi_hip_ctx *ctx, ScanArgs &a, const char *&what) {
 // The call's pairs are routed (scan.h): the wavefront kernel's layout b (at b_off of the scratch) beside the lane scan's a.
 // The pairs are sampled and routed; pass A by wavefronts (on a stream of its own) runs beside the lane scan's kernels; the
 // pairs it handed back -- rare: the host looks -- get a second lane layout a2; passes B and C once per layout.
+// ahead (upload_descriptors): the subjects' flags were taken to be clear; *again is set, with nothing but the layout's kernels run and the
+// streams drained, where the first look finds one of them raised: the caller runs the call again, waiting for the builds first.
 hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size_t b_off, const andi_hip_queries *q,
-						 size_t slots, size_t slots2, const char *&what) {
+						 size_t slots, size_t slots2, andi_hip_esa *const *subjects, bool ahead, bool *again, const char *&what) {
 	const size_t nsub = a.nsub, pairs_all = nsub * q->nq;
 	ScanArgs b = a;
 	b.adaptive = 0, b.coop = 1, b.route = ANDI_LAYOUT_COOP;
@@ -424,10 +440,11 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	b.items_order = listed ? P.items_order : (uint32_t)ANDI_ITEMS_GRID;
 	b.layout_count = a.restitch_count;
 	hipError_t e;
+	const size_t timers_before = ctx->pending.size();
+	uint32_t pass_a[3] = {0, 0, 0}, rounds[3] = {0, 0, 0}; // what is launched per layout (a, b, a2), set where it is launched (the suite's hook reads them)
 	{
 		Timed t(ctx, 2);
-		e = hipMemsetAsync(b.restitch_count, 0, 16 * sizeof(uint32_t), ctx->stream);
-		if (e == hipSuccess) e = andi_launch_pair_layout(a, ctx->stream);
+		e = andi_launch_pair_layout(a, ctx->stream, b.restitch_count); // (b's counters cleared with a's: pass B's first stage counts on that, below)
 		if (e == hipSuccess && listed) e = andi_launch_coop_items(b, ctx->stream);
 		t.stop();
 		if (e != hipSuccess) return what = "scan layout", e;
@@ -444,6 +461,19 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	e = hipSuccess;
 	if (look) e = hipMemcpyAsync(ctx->h_any_left + 1, a.restitch_count, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
 	if (look && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (ahead && e == hipSuccess) { // (the look's wait implies the builds have ended: they are earlier work of the same stream)
+		ctx->builds_pending = false;
+		for (size_t s = 0; s < nsub; ++s)
+			if (subjects[s]->h_flags[0] != 0 || subjects[s]->h_flags[1] != 0) *again = true;
+		if (*again) { // (only the call's stream has work, and the look waited for it)
+			// the discarded layout's timer does not count: stitch_ms and stitch_launches are the rerun's alone
+			while (ctx->pending.size() > timers_before) {
+				ctx->idle_events.push_back(ctx->pending.back().a), ctx->idle_events.push_back(ctx->pending.back().b);
+				ctx->pending.pop_back();
+			}
+			return hipSuccess;
+		}
+	}
 	const bool lanes_first = look && e == hipSuccess && (uint64_t)ctx->h_any_left[1 + ANDI_LANE_WAVES] * 20 < ctx->h_any_left[1 + ANDI_ALL_WAVES];
 	// which wavefront kernel: the pooled one where the pairs that suit it hold at least half of the segments (scan.h)
 	b.pool_use = look && e == hipSuccess && 2 * (uint64_t)ctx->h_any_left[1 + ANDI_POOL_SEGS] >= ctx->h_any_left[1 + ANDI_COOP_SEGS] && ctx->h_any_left[1 + ANDI_COOP_SEGS] != 0;
@@ -453,20 +483,44 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 	if (andi_coop_will_pool(b)) b.coop_items = nullptr;
 	ctx->last_items.items = b.coop_items, ctx->last_items.pair_class = b.pair_class, ctx->last_items.pair_cost = b.pair_cost;
 	ctx->last_items.n_items = b.n_items, ctx->last_items.pairs = (uint32_t)pairs_all, ctx->last_items.total_segs = b.total_segs;
-	if (e == hipSuccess) e = hipEventRecord(ctx->coop_fork, ctx->stream);
-	if (e == hipSuccess) e = hipStreamWaitEvent(ctx->coop_stream, ctx->coop_fork, 0);
-	if (e == hipSuccess && lanes_first) e = andi_launch_scan_cold(a, ctx->stream);
-	if (e == hipSuccess) e = andi_launch_coop_cold(b, ctx->coop_stream);
+	ctx->last_items.pair_waves = a.pair_waves, ctx->last_items.pair_wave0 = a.adaptive ? a.pair_wave0 : nullptr, ctx->last_items.sub_order = a.sub_order;
+	ctx->last_items.nsub = a.nsub, ctx->last_items.looked = look ? 1u : 0u;
+	for (int k = 0; k < 16; ++k) ctx->last_items.counts[k] = ctx->h_any_left[1 + k];
+	// A lane layout without a pair (known from the first look; a call that does not look is taken to have some) launches nothing: its pass A
+	// is a memset of 8 bytes per slot, a look of its own on the side stream and kernels whose wavefronts all return -- 0.1 ms of the bench
+	// step in front of the wavefront kernel (profiles/r14_call_edges.md) --, and its passes B and C have nothing to do.  The wavefront
+	// kernel and its passes then stay on the call's stream: with nothing beside them a stream of their own is two crossings for nothing.
+	const bool any_lanes = ctx->h_any_left[1 + ANDI_LANE_WAVES] != 0;
+	const hipStream_t bs = any_lanes ? ctx->coop_stream : ctx->stream;
+	if (e == hipSuccess && any_lanes) e = hipEventRecord(ctx->coop_fork, ctx->stream);
+	if (e == hipSuccess && any_lanes) e = hipStreamWaitEvent(ctx->coop_stream, ctx->coop_fork, 0);
+	if (e == hipSuccess && lanes_first && any_lanes) e = andi_launch_scan_cold(a, ctx->stream), pass_a[0] = 1;
+	if (e == hipSuccess) e = andi_launch_coop_cold(b, bs), pass_a[1] = 1;
 	if (andi_coop_will_pool(b)) ctx->acc.pool_calls++;
-	if (e == hipSuccess) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
-	if (e == hipSuccess && !lanes_first) e = andi_launch_scan_cold(a, ctx->stream);
-	if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
-	if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_any_left, b.restitch_count + ANDI_ROUTE_ANY_LEFT, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-	if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+	if (e == hipSuccess && any_lanes) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
+	if (e == hipSuccess && !lanes_first && any_lanes) e = andi_launch_scan_cold(a, ctx->stream), pass_a[0] = 1;
+	if (e == hipSuccess && any_lanes) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
 	if (e != hipSuccess) return what = "scan pass A", e;
-	const bool any_left = ctx->h_any_left[0] != 0;
-	const bool any_lanes = ctx->h_any_left[1 + ANDI_LANE_WAVES] != 0; // (no pair in the lane layout: its passes B and C have nothing to do)
+	t.stop(); // (pass A's kernels, as before; the host's wait for the look below is no longer inside)
+	// Passes B and C once per layout, side by side (each is a chain of small launches).  The host must see whether a pair was handed back --
+	// one word of layout b --, but nothing of b's pass B depends on that: its first stage goes right behind the wavefront kernel, and the
+	// host looks behind THAT, at three words in one copy -- pairs handed back, chains of the first stage that left their segment on their
+	// own, the first stage's list.  Where no chain did, the rounds that stitch again would all return at once (k_stitch_heads): they are
+	// not launched.  (b's counters are clear but for the first of those words since the layout's clearing: the stage counts in them as
+	// they are.)  The lane layout's passes need nothing from the look and are enqueued in front of it.
+	Timed t2(ctx, 2);
+	e = andi_launch_scan_stitch(b, bs, ANDI_STITCH_STAGE0);
+	if (e == hipSuccess) e = hipMemcpyAsync(ctx->h_any_left + ANDI_LOOK_B, b.restitch_count, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, bs);
+	if (e == hipSuccess) e = hipEventRecord(ctx->l2_fork, ctx->stream); // (pass A of both layouts done: where the chain of the pairs handed back starts)
+	if (e == hipSuccess && any_lanes) e = andi_launch_scan_stitch(a, ctx->stream, ANDI_STITCH_ALL, &rounds[0]);
+	if (e == hipSuccess && any_lanes) e = andi_launch_scan_reduce(a, ctx->stream);
+	if (e == hipSuccess) e = hipStreamSynchronize(bs);
+	if (e != hipSuccess) return what = "scan passes B/C", e;
+	const bool any_left = (ctx->h_any_left[0] = ctx->h_any_left[ANDI_LOOK_B + ANDI_ROUTE_ANY_LEFT]) != 0;
+	const bool rounds_b = ctx->h_any_left[ANDI_LOOK_B + ANDI_RESTITCH_ROUNDS] != 0;
 	ScanArgs a2 = a;
+	// (scratch2 may be regrown here although the lane layout's passes B and C are still in flight on the call's stream and only bs has been
+	// waited for: no kernel of layouts a and b touches scratch2, and the previous call's use of it lies before this call's work on every stream, bs included)
 	if (any_left) { // the pairs handed back: a lane layout of their own (as large as the first at most)
 		const size_t need2 = carve_layout(a2, nullptr, 0, slots, pairs_all, false, 0) + 256;
 		if (ctx->scratch2_bytes < need2) {
@@ -480,29 +534,27 @@ hipError_t launch_routed(andi_hip_ctx *ctx, const ScanPlan &P, ScanArgs &a, size
 		a2.route = ANDI_LAYOUT_LANES2;
 		a2.side_stream = nullptr; // (its own kernels one after the other: it runs on the side stream itself, below)
 	}
-	t.stop();
-	// Passes B and C once per layout, side by side (each is a chain of small launches); the pairs handed back take
-	// their pass A at the head of their chain.
-	Timed t2(ctx, 2);
-	e = hipEventRecord(ctx->l2_fork, ctx->stream);
-	if (e == hipSuccess) e = hipStreamWaitEvent(ctx->coop_stream, ctx->l2_fork, 0);
-	if (e == hipSuccess) e = andi_launch_scan_stitch(b, ctx->coop_stream);
-	if (e == hipSuccess) e = andi_launch_scan_reduce(b, ctx->coop_stream);
-	if (e == hipSuccess) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
-	if (e == hipSuccess && any_left) {
+	if (rounds_b) e = andi_launch_scan_stitch(b, bs, ANDI_STITCH_ROUNDS, &rounds[1]);
+	if (e == hipSuccess) e = andi_launch_scan_reduce(b, bs);
+	if (e == hipSuccess && any_lanes) e = hipEventRecord(ctx->coop_join, ctx->coop_stream);
+	if (e == hipSuccess && any_left) { // (they take their pass A at the head of their chain, behind both layouts' pass A)
 		e = hipStreamWaitEvent(ctx->side_stream, ctx->l2_fork, 0);
 		if (e == hipSuccess) e = andi_launch_pair_leftover(a2, ctx->side_stream);
-		if (e == hipSuccess) e = andi_launch_scan_cold(a2, ctx->side_stream);
-		if (e == hipSuccess) e = andi_launch_scan_stitch(a2, ctx->side_stream);
+		if (e == hipSuccess) e = andi_launch_scan_cold(a2, ctx->side_stream), pass_a[2] = 1;
+		if (e == hipSuccess) e = andi_launch_scan_stitch(a2, ctx->side_stream, ANDI_STITCH_ALL, &rounds[2]);
 		if (e == hipSuccess) e = andi_launch_scan_reduce(a2, ctx->side_stream);
 		if (e == hipSuccess) e = hipEventRecord(ctx->l2_join, ctx->side_stream);
 	}
-	if (e == hipSuccess && any_lanes) e = andi_launch_scan_stitch(a, ctx->stream);
-	if (e == hipSuccess && any_lanes) e = andi_launch_scan_reduce(a, ctx->stream);
-	if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
+	if (e == hipSuccess && any_lanes) e = hipStreamWaitEvent(ctx->stream, ctx->coop_join, 0);
 	if (e == hipSuccess && any_left) e = hipStreamWaitEvent(ctx->stream, ctx->l2_join, 0);
 	if (e == hipSuccess) e = andi_launch_route_count(a, ctx->stream);
 	t2.stop();
+#ifdef ANDI_TEST_HOOKS
+	for (int k = 0; k < 3; ++k) ctx->last_edges.pass_a[k] = pass_a[k], ctx->last_edges.rounds[k] = rounds[k];
+	ctx->last_edges.count_b = b.restitch_count;
+#else
+	(void)pass_a, (void)rounds;
+#endif
 	if (e != hipSuccess) return what = "scan passes B/C", e;
 	ctx->acc.coop_calls++;
 	ctx->acc.routed_calls++;
@@ -536,33 +588,42 @@ int andi_hip_scan_rows(andi_hip_ctx *ctx, andi_hip_esa *const *subjects, const i
 	ctx->last_items = {}; // (what the test hook reads points into this call's scratch: nothing of an earlier call's outlives it)
 #ifdef ANDI_TEST_HOOKS
 	ctx->last_slots = {}; // (likewise: before the scratch may be regrown, and for a call that is routed or takes per-pair lengths)
+	ctx->last_edges = {};
 #endif
-	ScanPlan P = plan_call(subjects, nsub, q, model, segment);
-	if (ensure_segmentation(ctx, q, P.segment)) return 1;
-	int any_reference = 0;
-	uint64_t pairs = 0, nt = 0;
-	if (upload_descriptors(ctx, subjects, self, nsub, q, P.force_reference, any_reference, pairs, nt)) return 1;
-	const int64_t *h_self = (const int64_t *)((const EsaDev *)ctx->desc_host + nsub);
-	plan_layout(ctx, P, h_self, nsub, q, any_reference, nt);
-	if (P.routed && ensure_segmentation(ctx, q, P.coop_seg, true)) return 1;
-	const size_t slots = P.adaptive ? (size_t)64 * P.max_waves : nsub * (size_t)q->total_segs;
-	const size_t slots2 = P.routed ? nsub * (size_t)q->c_total_segs : 0; // (the wavefront kernel's layout, beside the lane scan's)
-	ScanArgs a = scan_args(ctx, P, nsub, q, M_dev, any_reference);
-	size_t b_off = 0;
-	if (carve_scratch(ctx, P, a, slots, slots2, nsub, nsub * q->nq, &b_off)) return 1;
+	for (bool may_go_ahead = true;; may_go_ahead = false) {
+		ScanPlan P = plan_call(subjects, nsub, q, model, segment);
+		if (ensure_segmentation(ctx, q, P.segment)) return 1;
+		int any_reference = 0;
+		uint64_t pairs = 0, nt = 0;
+		bool ahead = may_go_ahead && P.routed && !P.route_all_few; // (the calls whose host looks at the layout: launch_routed)
+		if (upload_descriptors(ctx, subjects, self, nsub, q, P.force_reference, any_reference, pairs, nt, &ahead)) return 1;
+		const int64_t *h_self = (const int64_t *)((const EsaDev *)ctx->desc_host + nsub);
+		plan_layout(ctx, P, h_self, nsub, q, any_reference, nt);
+		if (P.routed && ensure_segmentation(ctx, q, P.coop_seg, true)) return 1;
+		const size_t slots = P.adaptive ? (size_t)64 * P.max_waves : nsub * (size_t)q->total_segs;
+		const size_t slots2 = P.routed ? nsub * (size_t)q->c_total_segs : 0; // (the wavefront kernel's layout, beside the lane scan's)
+		ScanArgs a = scan_args(ctx, P, nsub, q, M_dev, any_reference);
+		size_t b_off = 0;
+		if (carve_scratch(ctx, P, a, slots, slots2, nsub, nsub * q->nq, &b_off)) return 1;
 
-	// every error exit from here on first waits for the streams the launches fork work onto: their kernels read the scratch
-	// the next call may regrow, and the context's teardown waits for ctx->stream only
-	const char *what = nullptr;
-	const hipError_t e = P.routed ? launch_routed(ctx, P, a, b_off, q, slots, slots2, what) : launch_direct(ctx, a, what);
-	if (e != hipSuccess) {
-		(void)hipStreamSynchronize(ctx->coop_stream);
-		(void)hipStreamSynchronize(ctx->side_stream);
-		(void)hipStreamSynchronize(ctx->stream);
-		return fail(ctx, what, e);
+		// every error exit from here on first waits for the streams the launches fork work onto: their kernels read the scratch
+		// the next call may regrow, and the context's teardown waits for ctx->stream only
+		const char *what = nullptr;
+		bool again = false;
+		const hipError_t e = P.routed ? launch_routed(ctx, P, a, b_off, q, slots, slots2, subjects, ahead, &again, what) : launch_direct(ctx, a, what);
+		if (e != hipSuccess) {
+			(void)hipStreamSynchronize(ctx->coop_stream);
+			(void)hipStreamSynchronize(ctx->side_stream);
+			(void)hipStreamSynchronize(ctx->stream);
+			return fail(ctx, what, e);
+		}
+#ifdef ANDI_TEST_HOOKS
+		ctx->last_edges.went_ahead |= ahead ? 1u : 0u, ctx->last_edges.ran_again |= again ? 1u : 0u;
+#endif
+		if (again) continue; // (a flag was raised: the same call the way it runs behind finished builds -- the reference's walk, or its error)
+		(P.adaptive ? ctx->acc.adaptive_calls : ctx->acc.uniform_calls)++;
+		ctx->acc.scan_pairs += pairs;
+		ctx->acc.scan_query_nt += nt;
+		return 0;
 	}
-	(P.adaptive ? ctx->acc.adaptive_calls : ctx->acc.uniform_calls)++;
-	ctx->acc.scan_pairs += pairs;
-	ctx->acc.scan_query_nt += nt;
-	return 0;
 }

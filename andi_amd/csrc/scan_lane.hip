@@ -28,9 +28,9 @@ namespace {
 // are made seg_factor times that (as a power-of-two multiple of seg0, at most 8 seg0).
 // Short segments keep the lanes of a wavefront close together in memory and the work
 // items small; long ones keep the stitching of low-divergence pairs cheap.
-// (A block of several wavefronts per pair: every one of them takes the samples of the mean -- the same, so that all know
-// what the pair is a candidate for -- and its share of the further samples of a routed call: the kernel's time is the
-// chain of dependent probes of one wavefront, 185 us with one wavefront per pair, 100 us with eight.)
+// (A block of several wavefronts per pair: the first takes the samples of the mean, the others share the further samples of a
+// routed call beside it -- the kernel's time is the chain of dependent probes of one wavefront, 185 us with one wavefront
+// per pair, 100 us with eight that each took the mean and then a round; since round 14 the longer of the two chains.)
 [[maybe_unused]] constexpr uint32_t EST_WAVES = 4; // (calls of up to 4096 pairs)
 constexpr uint32_t EST_WAVES_FEW = 8; // (calls of up to 1024 pairs: a round of further samples per wavefront)
 // (Calls of more pairs than that, `many`: the device is full with one wavefront per pair; four pairs share a block.  What
@@ -65,6 +65,43 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 	// mostly sampling otherwise)
 	const uint32_t nl_shift = !a.route || c.qlen >= 32768u ? 6u : c.qlen >= 16384u ? 5u : 4u, nl = 1u << nl_shift;
 	const uint32_t p = (uint32_t)(((uint64_t)(2 * lane + 1) * c.qlen) >> (nl_shift + 1));
+	// What of "would the pair suit pass A by wavefronts" (coop_cand, below) does not depend on the samples of the mean -- and the further
+	// samples of such a pair, which need that verdict and none of the mean's numbers: rounds first, first + step, ... of them.
+	uint32_t break_dist = ~0u;
+	if (a.qsep && a.self[sub] >= 0) {
+		const uint32_t ends = a.qsep[qidx] + a.qsep[(uint32_t)a.self[sub]];
+		if (ends) break_dist = c.qlen / ends;
+	}
+	const bool pre_cand = a.route && c.qlen >= (a.route_seg < ANDI_ROUTE_MIN_QLEN ? a.route_seg : ANDI_ROUTE_MIN_QLEN) && break_dist >= 20480u;
+	const uint32_t T = c.thr + 3; // (beyond what chance matches reach: a 13-mer occurs in a 10 Mbp text one time in seven)
+	uint32_t nrounds = est_waves > 1 ? 8u : 4u;
+	while (nrounds > 1 && c.qlen < nrounds * (64u * 2048u)) nrounds >>= 1;
+	auto further_samples = [&](uint32_t first_round, uint32_t step, uint32_t &shorts, uint32_t &runs) {
+		for (uint32_t k = first_round; k < nrounds; k += step) {
+			const uint32_t pk = (uint32_t)(((uint64_t)(2 * nrounds * lane + 2 * k + 1) * c.qlen) / (2u * nl * nrounds));
+			bool all_short = lane < nl;
+			for (uint32_t j = 0; j < 5 && all_short; ++j) {
+				const uint32_t pj = pk + 128 * j;
+				LWin wk;
+				wk.q0 = EMPTY, wk.dg = NO_DIAG;
+				all_short = pj + T < c.qlen && lane_probe(c, pj, wk, T + 1).len < T;
+				if (j == 0 && all_short) ++shorts;
+			}
+			if (all_short) ++runs;
+		}
+#pragma unroll
+		for (int d = 32; d; d >>= 1) shorts += (uint32_t)__shfl_xor((int)shorts, d), runs += (uint32_t)__shfl_xor((int)runs, d);
+	};
+	// A block of several wavefronts: the FIRST takes the mean, the others take the rounds of further samples beside it, before the verdict
+	// is known -- their counts are used only if the pair turns out a candidate.  (Until round 14 every wavefront repeated the mean and took
+	// its rounds behind it: the kernel's time was the sum of two chains of dependent loads that do not depend on each other.)
+	if (!many && wave != 0) {
+		uint32_t shorts = 0, runs = 0;
+		if (pre_cand) further_samples(wave - 1, est_waves - 1, shorts, runs);
+		if (pre_cand && lane == 0) atomicAdd(&s_shorts, shorts), atomicAdd(&s_runs, runs);
+		__syncthreads(); // (the first wavefront's, below)
+		return;
+	}
 	LWin w;
 	w.q0 = EMPTY, w.dg = NO_DIAG;
 	// a pair whose mean is seg0 * 8 / factor gets the longest segments anyway: samples are cut at twice
@@ -97,12 +134,8 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 	// k_coop_cold's second session of round 6: with that kernel a sixth faster the C4 shape of 40-contig genomes -- an end every 26 000
 	// positions -- takes 41.3 ms by wavefronts against 50.9 by lanes, the bench set of 100-contig genomes -- 24 500 -- 10.6 either way, the C4
 	// shape of 100-contig genomes -- 10 500 -- 71 against 59: profiles/r07_coop/join_threshold.txt.)
-	uint32_t break_dist = ~0u;
-	if (a.qsep && a.self[sub] >= 0) {
-		const uint32_t ends = a.qsep[qidx] + a.qsep[(uint32_t)a.self[sub]];
-		if (ends) break_dist = c.qlen / ends;
-	}
-	const bool coop_cand = a.route && (sum >> 6) < 512u && c.qlen >= (a.route_seg < ANDI_ROUTE_MIN_QLEN ? a.route_seg : ANDI_ROUTE_MIN_QLEN) && break_dist >= 20480u; // (matches of 512 symbols and more on average: k_lane_quad's, always)
+	const bool coop_cand = pre_cand && (sum >> 6) < 512u; // (matches of 512 symbols and more on average: k_lane_quad's, always)
+	if (!many) __syncthreads(); // (the other wavefronts' counts are in)
 	if (coop_cand) { // (wave-uniform)
 		// Unrelated stretches are contiguous: where a sample sees less than a threshold's worth of matching symbols, four
 		// more are taken, 128 symbols apart.  Five short ones in a row come about by chance at the fifth power of the rate of
@@ -111,34 +144,14 @@ __global__ __launch_bounds__(64 * EST_WAVES_FEW) void k_pair_estimate(ScanArgs a
 		// sequence from none at six standard deviations whatever the divergence.  (The excess of short samples over what
 		// the mean match length explains, the test of k_lane_quad's candidates below, is too weak here: it missed one
 		// structured pair in six and suspected one clean pair in nine; three in a row miss the pairs 5 % and more apart.)
-		const uint32_t T = c.thr + 3; // (beyond what chance matches reach: a 13-mer occurs in a 10 Mbp text one time in seven)
 		// (calls of thousands of pairs: 256 samples -- one wavefront per pair there, and the chain of its dependent probes is
 		// what the kernel takes: 0.77 -> 0.4 ms for the C4 shape's 24 680 pairs; 10 % of unrelated sequence still stand out
 		// by four standard deviations)
 		// (short queries: a sample per 2048 symbols at most -- the follow-ups of one span 640)
-		uint32_t nrounds = est_waves > 1 ? 8u : 4u;
-		while (nrounds > 1 && c.qlen < nrounds * (64u * 2048u)) nrounds >>= 1;
 		const uint32_t nsamples = nl * nrounds;
 		uint32_t shorts = 0, runs = 0;
-		for (uint32_t k = wave; k < nrounds; k += est_waves) {
-			const uint32_t pk = (uint32_t)(((uint64_t)(2 * nrounds * lane + 2 * k + 1) * c.qlen) / (2u * nl * nrounds));
-			bool all_short = lane < nl;
-			for (uint32_t j = 0; j < 5 && all_short; ++j) {
-				const uint32_t pj = pk + 128 * j;
-				LWin wk;
-				wk.q0 = EMPTY, wk.dg = NO_DIAG;
-				all_short = pj + T < c.qlen && lane_probe(c, pj, wk, T + 1).len < T;
-				if (j == 0 && all_short) ++shorts;
-			}
-			if (all_short) ++runs;
-		}
-#pragma unroll
-		for (int d = 32; d; d >>= 1) shorts += (uint32_t)__shfl_xor((int)shorts, d), runs += (uint32_t)__shfl_xor((int)runs, d);
-		if (!many) {
-			if (lane == 0) atomicAdd(&s_shorts, shorts), atomicAdd(&s_runs, runs);
-			__syncthreads(); // (coop_cand is the same in all wavefronts of the block: they took the same samples)
-			shorts = s_shorts, runs = s_runs;
-		}
+		if (many) further_samples(0, 1, shorts, runs); // (one wavefront per pair: the rounds behind the mean)
+		else shorts = s_shorts, runs = s_runs;
 		// The rate f0 of short samples OUTSIDE unrelated stretches: from the short samples that did not turn into a run --
 		// f0 - f0^5 of the samples in homologous sequence, hardly any inside a stretch without homology (Newton on the lower
 		// branch; pairs beyond 6 % or so have no solution there and are taken for suspicious: the lane scan's anyway).
@@ -272,6 +285,16 @@ __global__ __launch_bounds__(1024) void k_pair_offsets(ScanArgs a) {
 	}
 }
 
+// What the layout counts in, cleared by one launch (three memsets took 20 us behind one another, each a launch with a gap in front of it):
+// the 16 words of restitch_count -- k_lane_quad's list is empty, no wavefronts counted --, the 16 of a second layout's (more: the wavefront
+// kernel's in a routed call, or null) and the subjects' summed costs
+__global__ __launch_bounds__(256) void k_layout_clear(ScanArgs a, uint32_t *more) {
+	const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+	if (t < 16) a.restitch_count[t] = 0;
+	if (more && t >= 16 && t < 32) more[t - 16] = 0;
+	if (a.sub_cost && t < a.nsub) a.sub_cost[t] = 0.f;
+}
+
 // routed calls: the wavefronts of all pairs, of those the lane scan would like (not marked for the wavefront kernel, or
 // soft), and of those it gets whatever the others do -- what k_pair_route decides by.  (A sum per block: a million pairs
 // adding to three words one by one took 30 ms.)
@@ -306,22 +329,27 @@ __global__ __launch_bounds__(1024) void k_pair_totals(ScanArgs a) {
 }
 
 // routed calls: which pairs take pass A by wavefronts (they get no wavefronts in the lane layout)
-__device__ __forceinline__ uint32_t route_pair(const ScanArgs &a, uint32_t pair, uint32_t &pool_segs, uint32_t &coop_segs) {
+// (w: the layout's sums of wavefronts -- k_pair_totals' and k_pair_estimate's ANDI_STRUCT_WAVES -- as k_pair_route reads them from
+// restitch_count and k_pair_layout_small has them in LDS)
+struct RouteWaves {
+	uint32_t all, sparse, hard, island, strct;
+};
+__device__ __forceinline__ uint32_t route_pair(const ScanArgs &a, uint32_t pair, const RouteWaves &w, uint32_t &pool_segs, uint32_t &coop_segs) {
 	uint32_t cls = a.pair_class[pair];
-	const bool lanes_few = 10 * a.restitch_count[ANDI_SPARSE_WAVES] <= a.restitch_count[ANDI_ALL_WAVES]; // (the lane scan's and those it would like)
+	const bool lanes_few = 10 * w.sparse <= w.all; // (the lane scan's and those it would like)
 	// (small calls: the soft pairs are the wavefront kernel's as well -- 3 x 1 Mbp 10 % apart, BASELINE's configs[0]: pass A
 	// 0.34 ms by wavefronts, 2.0 ms by lanes, whose chains take a segment's few hundred steps one after the other)
 	if ((cls & ANDI_ROUTE_COOP) && (cls & ANDI_ROUTE_SOFT) && !lanes_few && !a.route_all_few) cls &= ~ANDI_ROUTE_COOP;
 	// (small calls: the pairs the sampling could not judge stay with the lane scan where a twentieth of the call shows
 	// unrelated stretches -- structured genomes: 12 x 1 Mbp took 5.4 ms with such pairs tried by wavefronts and handed
 	// back, 3.9 ms by lanes)
-	if ((cls & ANDI_ROUTE_GUESS) && 20 * a.restitch_count[ANDI_ISLAND_WAVES] > a.restitch_count[ANDI_ALL_WAVES]) cls &= ~ANDI_ROUTE_COOP;
+	if ((cls & ANDI_ROUTE_GUESS) && 20 * w.island > w.all) cls &= ~ANDI_ROUTE_COOP;
 	// A call of structured genomes -- a third of its wavefronts belong to pairs with unrelated stretches (and not merely far apart) --
 	// gives the suspected pairs segments twice as long: what such pairs cost is pass B, where every segment boundary inside a stretch
 	// without homology is a replay of hundreds of steps by one lane, and pass A loses nothing (the structured set's passes B/C 6.8 ->
 	// 4.4 ms, its step 19.0 -> 16.6).  All of them or none: with the segment lengths mixed pass A was the slower for it (10.1 against
 	// 9.4 ms), and clean pairs 4-10 % apart -- suspected too -- lose 5-10 % with long segments where they are most of a call.
-	if ((cls & (ANDI_ROUTE_LEFT | ANDI_ROUTE_GUESS)) && !(cls & ANDI_ROUTE_COOP) && (cls & 3u) < a.max_class && 3 * a.restitch_count[ANDI_STRUCT_WAVES] >= a.restitch_count[ANDI_ALL_WAVES]) {
+	if ((cls & (ANDI_ROUTE_LEFT | ANDI_ROUTE_GUESS)) && !(cls & ANDI_ROUTE_COOP) && (cls & 3u) < a.max_class && 3 * w.strct >= w.all) {
 		++cls;
 		const uint32_t seg = a.seg0 << (cls & 3u);
 		a.pair_waves[pair] = ((a.qlen[pair % a.nq] + seg - 1) / seg + 63) / 64;
@@ -331,7 +359,7 @@ __device__ __forceinline__ uint32_t route_pair(const ScanArgs &a, uint32_t pair,
 	// Small calls (route_all_few): pass A by wavefronts takes a fraction of a millisecond, and a lane's chain over one
 	// segment as long as it ever does -- six pairs of 9900 left to the lane scan (100 x 30 kbp) made pass A 1.1 ms instead
 	// of 0.6.  Where the lane scan's pairs are that few, the wavefront kernel takes them all (and hands back what it must).
-	if (a.route_all_few && 20 * a.restitch_count[ANDI_HARD_WAVES] <= a.restitch_count[ANDI_ALL_WAVES] && a.self[pair / a.nq] != (int64_t)(pair % a.nq))
+	if (a.route_all_few && 20 * w.hard <= w.all && a.self[pair / a.nq] != (int64_t)(pair % a.nq))
 		cls |= ANDI_ROUTE_COOP;
 	if (cls & ANDI_ROUTE_COOP) { // (which of the wavefront kernels: scan.h)
 		const uint32_t segs = (a.qlen[pair % a.nq] + a.route_seg - 1) / a.route_seg;
@@ -345,7 +373,9 @@ __device__ __forceinline__ uint32_t route_pair(const ScanArgs &a, uint32_t pair,
 __global__ __launch_bounds__(256) void k_pair_route(ScanArgs a) {
 	const uint32_t P = a.nsub * a.nq, pair = blockIdx.x * 256 + threadIdx.x;
 	uint32_t mine = 0, pool_segs = 0, coop_segs = 0; // wavefronts the pair keeps in the lane layout; the wavefront kernel's segments
-	if (pair < P) mine = route_pair(a, pair, pool_segs, coop_segs);
+	const RouteWaves w = {a.restitch_count[ANDI_ALL_WAVES], a.restitch_count[ANDI_SPARSE_WAVES], a.restitch_count[ANDI_HARD_WAVES],
+						  a.restitch_count[ANDI_ISLAND_WAVES], a.restitch_count[ANDI_STRUCT_WAVES]};
+	if (pair < P) mine = route_pair(a, pair, w, pool_segs, coop_segs);
 #pragma unroll
 	for (int d = 32; d; d >>= 1)
 		mine += (uint32_t)__shfl_xor((int)mine, d), pool_segs += (uint32_t)__shfl_xor((int)pool_segs, d), coop_segs += (uint32_t)__shfl_xor((int)coop_segs, d);
@@ -366,6 +396,81 @@ __global__ __launch_bounds__(1024) void k_sub_order(ScanArgs a) {
 			rank += (o > c || (o == c && t < s)) ? 1u : 0u;
 		}
 		a.sub_order[rank] = s;
+	}
+}
+
+// Routed calls of at most 1024 pairs: what k_pair_totals, k_pair_route, k_sub_order and pair_offsets' three kernels do, by ONE block with
+// a pair per thread -- six launches of the 5 us a launch with these arguments takes at the least, one behind the other, for a few hundred
+// pairs (profiles/r14_call_edges.md).  Every array and counter ends up as those kernels leave it: the sums go through LDS and are added to
+// the (cleared) counters once, the pairs' own words are read and written by the pair's thread alone.
+__global__ __launch_bounds__(1024) void k_pair_layout_small(ScanArgs a) {
+	__shared__ uint32_t s_part[1024];
+	__shared__ uint32_t s_sum[8];
+	const uint32_t P = a.nsub * a.nq, pair = threadIdx.x;
+	if (threadIdx.x < 8) s_sum[threadIdx.x] = 0;
+	__syncthreads();
+	{ // k_pair_totals
+		uint32_t all = 0, sparse = 0, hard = 0, isl = 0;
+		if (pair < P) {
+			const uint32_t cls = a.pair_class[pair];
+			all = a.pair_waves[pair];
+			hard = (cls & ANDI_ROUTE_COOP) ? 0u : all;
+			sparse = (cls & ANDI_ROUTE_SOFT) ? all : hard;
+			isl = (cls & ANDI_ROUTE_LEFT) ? all : 0u;
+		}
+#pragma unroll
+		for (int d = 32; d; d >>= 1) {
+			all += (uint32_t)__shfl_xor((int)all, d);
+			sparse += (uint32_t)__shfl_xor((int)sparse, d);
+			hard += (uint32_t)__shfl_xor((int)hard, d);
+			isl += (uint32_t)__shfl_xor((int)isl, d);
+		}
+		if ((threadIdx.x & 63u) == 0) atomicAdd(&s_sum[0], all), atomicAdd(&s_sum[1], sparse), atomicAdd(&s_sum[2], hard), atomicAdd(&s_sum[3], isl);
+	}
+	__syncthreads();
+	const RouteWaves w = {s_sum[0], s_sum[1], s_sum[2], s_sum[3], a.restitch_count[ANDI_STRUCT_WAVES]};
+	if (threadIdx.x == 0) {
+		if (w.all) atomicAdd(&a.restitch_count[ANDI_ALL_WAVES], w.all);
+		if (w.sparse) atomicAdd(&a.restitch_count[ANDI_SPARSE_WAVES], w.sparse);
+		if (w.hard) atomicAdd(&a.restitch_count[ANDI_HARD_WAVES], w.hard);
+		if (w.island) atomicAdd(&a.restitch_count[ANDI_ISLAND_WAVES], w.island);
+	}
+	{ // k_pair_route
+		uint32_t mine = 0, pool_segs = 0, coop_segs = 0;
+		if (pair < P) mine = route_pair(a, pair, w, pool_segs, coop_segs);
+#pragma unroll
+		for (int d = 32; d; d >>= 1)
+			mine += (uint32_t)__shfl_xor((int)mine, d), pool_segs += (uint32_t)__shfl_xor((int)pool_segs, d), coop_segs += (uint32_t)__shfl_xor((int)coop_segs, d);
+		if ((threadIdx.x & 63u) == 0) atomicAdd(&s_sum[4], mine), atomicAdd(&s_sum[5], coop_segs), atomicAdd(&s_sum[6], pool_segs);
+	}
+	if (a.sub_order && threadIdx.x < a.nsub) { // k_sub_order (at most 1024 subjects here)
+		const uint32_t s = threadIdx.x;
+		const float c = a.sub_cost[s];
+		uint32_t rank = 0;
+		for (uint32_t t = 0; t < a.nsub; ++t) {
+			const float o = a.sub_cost[t];
+			rank += (o > c || (o == c && t < s)) ? 1u : 0u;
+		}
+		a.sub_order[rank] = s;
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		if (s_sum[4]) atomicAdd(&a.restitch_count[ANDI_LANE_WAVES], s_sum[4]);
+		if (s_sum[5]) atomicAdd(&a.restitch_count[ANDI_COOP_SEGS], s_sum[5]), atomicAdd(&a.restitch_count[ANDI_POOL_SEGS], s_sum[6]);
+	}
+	if (!a.adaptive) return; // (one segment length for the lanes: the marks only)
+	// pair_offsets: one block's scan is the whole of it
+	const uint32_t v = pair < P ? a.pair_waves[pair] : 0u; // (as route_pair, this thread, left it)
+	const uint32_t incl = block_scan_1024(v, s_part);
+	if (threadIdx.x == 1023) a.pair_bsum[0] = 0, a.pair_wave0[P] = incl; // (the one block's offset; wavefronts in use)
+	if (pair < P) {
+		const uint32_t w0 = incl - v;
+		a.pair_wave0[pair] = w0;
+		if ((a.pair_class[pair] & 0x80u) && v) { // its wavefronts go on k_lane_quad's list
+			uint32_t *list = (uint32_t *)a.defer_list;
+			const uint32_t base = atomicAdd(&a.restitch_count[ANDI_QUAD_WAVES], v);
+			for (uint32_t k = 0; k < v; ++k) list[base + k] = w0 + k;
+		}
 	}
 }
 
@@ -1418,13 +1523,18 @@ static hipError_t pair_offsets(const ScanArgs &a, hipStream_t st) {
 	return hipSuccess;
 }
 
-hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st) {
+hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st, uint32_t *more) {
 	const uint32_t P = a.nsub * a.nq;
-	(void)hipMemsetAsync(a.restitch_count, 0, 16 * sizeof(uint32_t), st); // k_lane_quad's list is empty, no wavefronts counted
-	if (a.sub_cost) (void)hipMemsetAsync(a.sub_cost, 0, a.nsub * sizeof(float), st);
+	k_layout_clear<<<((a.sub_cost && a.nsub > 32 ? a.nsub : 32u) + 255) / 256, 256, 0, st>>>(a, more);
+	CHECK_LAUNCH();
 	if (P <= 4096) k_pair_estimate<<<P, P <= 1024 ? 64 * EST_WAVES_FEW : 64 * EST_WAVES, 0, st>>>(a, false);
 	else k_pair_estimate<<<(P + 3) / 4, 256, 0, st>>>(a, true);
 	CHECK_LAUNCH();
+	if (a.route && P <= 1024) { // (routing, the subjects' order and the offsets in one launch)
+		k_pair_layout_small<<<1, 1024, 0, st>>>(a);
+		CHECK_LAUNCH();
+		return hipSuccess;
+	}
 	if (a.route) {
 		k_pair_totals<<<(P + 1023) / 1024, 1024, 0, st>>>(a);
 		CHECK_LAUNCH();
@@ -1490,12 +1600,13 @@ hipError_t andi_launch_lane_cold(const ScanArgs &a, hipStream_t st) {
 	return e;
 }
 
-hipError_t andi_launch_lane_stitch(const ScanArgs &a0, hipStream_t st) {
+hipError_t andi_launch_lane_stitch(const ScanArgs &a0, hipStream_t st, unsigned parts, uint32_t *rounds) {
 	hipStream_t st_ = st;
 	(void)st_;
 	dim3 grid = lane_grid(a0);
 	ScanArgs a = a0;
-	hipError_t e = hipMemsetAsync(a.restitch_count, 0, 16 * sizeof(uint32_t), st);
+	// (a caller that leaves the clearing out vouches for the words the stages count in: scan_call.hip, launch_routed)
+	hipError_t e = (parts & ANDI_STITCH_CLEAR) ? hipMemsetAsync(a.restitch_count, 0, 16 * sizeof(uint32_t), st) : hipSuccess;
 	if (e != hipSuccess) return e;
 	// every stage: the launch over all segments, then the segments it put on the list (a grid for half of all
 	// segments at most: blocks beyond the list's length return at once; the list cannot be longer than the
@@ -1519,12 +1630,12 @@ hipError_t andi_launch_lane_stitch(const ScanArgs &a0, hipStream_t st) {
 		while ((size_t)L * 8192 < slots) L *= 2;
 		if (L < 64) a.stitch_lanes = L, grid0 = dim3((a.total_segs + WAVES_PER_BLOCK * L - 1) / (WAVES_PER_BLOCK * L), a.nsub);
 	}
-	if (a.exact_equal)
+	if ((parts & ANDI_STITCH_STAGE0) && a.exact_equal)
 		stage(k_lane_stitch<true, 0>, k_lane_stitch<true, 1>, grid0, 8);
-	else
+	else if (parts & ANDI_STITCH_STAGE0)
 		stage(k_lane_stitch<false, 0>, k_lane_stitch<false, 1>, grid0, 8);
 #ifdef ANDI_LANE_STATS
-	if (andi_knob(KNOB_LANE_STATS)) { // pass B's first stage: how its segments were settled, and the chain steps that took
+	if ((parts & ANDI_STITCH_STAGE0) && andi_knob(KNOB_LANE_STATS)) { // pass B's first stage: how its segments were settled, and the chain steps that took
 		static const char *names[8] = {"entered behind the cold chain's first anchor", "met behind its first anchor", "met at a mark",
 									   "met in phase 2", "position-synced", "left on their own", "steps of those that left on their own", "steps of the others"};
 		unsigned long long h[24];
@@ -1536,16 +1647,17 @@ hipError_t andi_launch_lane_stitch(const ScanArgs &a0, hipStream_t st) {
 		(void)hipMemcpyToSymbol(HIP_SYMBOL(g_lane_stats), h, sizeof h);
 	}
 #endif
-	const bool again = !andi_knob(KNOB_NO_RESTITCH);
+	const bool again = (parts & ANDI_STITCH_ROUNDS) && !andi_knob(KNOB_NO_RESTITCH);
 	for (uint32_t r = 0; again && r < ANDI_RESTITCH_ROUNDS; ++r) {
 		a.restitch_round = r;
 		if (a.exact_equal)
 			stage(k_stitch_heads, k_lane_stitch<true, 2>, grid, 13 + r);
 		else
 			stage(k_stitch_heads, k_lane_stitch<false, 2>, grid, 13 + r);
+		if (rounds) ++*rounds;
 	}
 #ifdef ANDI_LANE_STATS
-	if (andi_knob(KNOB_LANE_STATS)) { // replays by length (steps: 0, 1, 2-3, 4-7, ...) per kind of launch
+	if ((parts & ANDI_STITCH_ROUNDS) && andi_knob(KNOB_LANE_STATS)) { // replays by length (steps: 0, 1, 2-3, 4-7, ...) per kind of launch
 		static const char *kinds[4] = {"first stage", "first stage, listed", "-", "stretches stitched again (segments)"};
 		unsigned long long h[4][16], st[4];
 		unsigned int mx[4];

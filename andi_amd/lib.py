@@ -195,6 +195,8 @@ HOOK_SYMBOLS = {
     "andi_hip_test_download_text": (C.c_int, [_P, _P, _P, _P, C.c_size_t, _P, C.c_size_t]),
     "andi_hip_test_pack_text": (C.c_int, [_P, _P, C.c_int]),
     "andi_hip_test_coop_items": (C.c_int, [_P, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "andi_hip_test_call_edges": (C.c_int, [_P, _P, _P]),
+    "andi_hip_test_pair_layout": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "andi_hip_test_query_codes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
     "andi_hip_test_stitch_slots": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
 }
@@ -612,6 +614,28 @@ class Context:
         items, cls, cost = np.zeros(int(info[0]), np.uint32), np.zeros(int(info[1]), np.uint8), np.zeros(int(info[1]), np.uint8)
         self._check(hook(self._h, items.ctypes.data, len(items), cls.ctypes.data, cost.ctypes.data, len(cls), info.ctypes.data), "test_coop_items")
         return (items if info[3] else None), cls, cost, int(info[2])
+
+    def call_edges(self):
+        """(a test hook) what the last routed scan call enqueued around pass A, per layout ("lanes", "coop", "back": the lane scan's, the
+        wavefront kernel's, the pairs handed back): {layout: (pass A enqueued, rounds of stitching again enqueued)}, and the 16 counters of the
+        wavefront kernel's layout as its pass B left them (scan.h: restitch_count -- [0 .. 2] stretches stitched again per round, [3] chains
+        that left their segment on their own)"""
+        out, count_b = np.zeros(8, np.uint32), np.zeros(16, np.uint32)
+        self._check(_hook("andi_hip_test_call_edges")(self._h, out.ctypes.data, count_b.ctypes.data), "test_call_edges")
+        edges = {name: (bool(out[k]), int(out[3 + k])) for k, name in enumerate(("lanes", "coop", "back"))}
+        edges["ahead"], edges["again"] = bool(out[6]), bool(out[7])  # went ahead of the pending builds; ran again on a raised flag
+        return edges, count_b
+
+    def pair_layout(self):
+        """(a test hook) the lane layout of the last routed scan call: dict of pair_waves, pair_wave0 (None where the lanes have one segment
+        length), sub_order, and the layout's sixteen counters at the host's first look (None where the host did not look)"""
+        hook = _hook("andi_hip_test_pair_layout")
+        info = np.zeros(4, np.uint32)
+        self._check(hook(self._h, None, None, None, None, info.ctypes.data), "test_pair_layout")
+        pairs, nsub = int(info[0]), int(info[1])
+        waves, wave0, order, counts = np.zeros(pairs, np.uint32), np.zeros(pairs + 1, np.uint32), np.zeros(nsub, np.uint32), np.zeros(16, np.uint32)
+        self._check(hook(self._h, waves.ctypes.data, wave0.ctypes.data, order.ctypes.data, counts.ctypes.data, info.ctypes.data), "test_pair_layout")
+        return {"pair_waves": waves, "pair_wave0": wave0 if info[2] else None, "sub_order": order, "counts": counts if info[3] else None}
 
     def stitch_slots(self):
         """(a test hook) the per-slot records of the last scan call that used one segment length (not routed, no per-pair lengths),
