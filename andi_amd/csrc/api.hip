@@ -898,6 +898,147 @@ extern "C" int andi_hip_test_query_codes(andi_hip_ctx *ctx, const andi_hip_queri
 	if (words) HIP_TRY(ctx, hipMemcpy(out, q->codes + 2 * (q->off[qidx] / 32), words * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return 0;
 }
+// The layout kernels of a routed scan call (scan_lane.hip) ALONE, on arrays of the caller's: no subject, no query text, no k_pair_estimate.
+// par = { nsub, nq, restitch_count[ANDI_STRUCT_WAVES], seg0, max_class, route_seg, route_all_few, adaptive, items_order, 1: with sub_order,
+// 1: with a list, allow_small (andi_launch_pair_routing) }; qlen[nq], self[nsub]; pair_class, pair_waves, pair_cost (with a list) of all
+// nsub * nq pairs and sub_cost[nsub] (with sub_order) as k_pair_estimate would leave them; left (may be NULL): a byte per pair, nonzero for
+// the pairs that get ANDI_ROUTE_LEFT behind the routing -- as pass A by wavefronts hands pairs back.  The wavefront layout's segmentation
+// (qseg_start, total_segs) is made from qlen and route_seg as the queries' cached one is (scan_call.hip: ensure_segmentation).
+// Launched as launch_routed does (scan_call.hip): the routing, the list (layout_count: the lane layout's counters), a download -- stage 1:
+// class1, waves1, wave01 (pairs + 1 words, adaptive only), order (with sub_order), counts1[16], quad (k_lane_quad's list, counts1[ANDI_QUAD_WAVES]
+// words of it), items (counts1[ANDI_COOP_SEGS] entries) --; then, with `left`, those marks and andi_launch_pair_leftover on a second layout
+// with its own pair_waves, pair_wave0, pair_bsum, counters and list; andi_launch_route_count; a download -- stage 2: class2, and with `left`
+// waves2, wave02 (adaptive only) and the second layout's counts2[16]; route_nt[3].  info = { 1: the routing was k_pair_layout_small's one
+// block, 2: several kernels; launches of the list's sort (0: no list, 1, 3); total_segs; words the quad list was allocated }.  Any output may
+// be NULL.  Bad arguments: returns 1 with nothing launched.
+extern "C" int andi_hip_test_layout_kernels(andi_hip_ctx *ctx, const uint32_t *par, const uint32_t *qlen, const int64_t *self, const uint8_t *pair_class,
+											const uint32_t *pair_waves, const uint8_t *pair_cost, const float *sub_cost, const uint8_t *left,
+											uint8_t *class1, uint32_t *waves1, uint32_t *wave01, uint32_t *order, uint32_t *counts1, uint32_t *quad,
+											uint32_t *items, uint8_t *class2, uint32_t *waves2, uint32_t *wave02, uint32_t *counts2,
+											unsigned long long *route_nt, uint32_t *info) {
+	if (!ctx) return 1;
+	if (!par || !qlen || !self || !pair_class || !pair_waves) {
+		ctx->err = "andi_hip_test_layout_kernels: par, qlen, self, pair_class and pair_waves are required";
+		return 1;
+	}
+	const uint32_t nsub = par[0], nq = par[1], strct = par[2], seg0 = par[3], max_class = par[4], route_seg = par[5];
+	const uint32_t all_few = par[6], adaptive = par[7], items_order = par[8];
+	const bool with_order = par[9] != 0, with_list = par[10] != 0, allow_small = par[11] != 0;
+	const uint64_t P64 = (uint64_t)nsub * nq;
+	const size_t LIMIT = (size_t)1 << 27; // (words of any one array: a hook of the suite's, not a call of gigabytes)
+	if (!nsub || !nq || P64 > UINT32_MAX || P64 > LIMIT) {
+		ctx->err = "andi_hip_test_layout_kernels: no pairs, or nsub * nq beyond what the kernels' 32-bit pair index (and this hook) takes";
+		return 1;
+	}
+	if (!seg0 || seg0 > (1u << 28) || max_class > 3 || !route_seg || adaptive > 1 || all_few > 1) {
+		ctx->err = "andi_hip_test_layout_kernels: seg0 in 1 .. 2^28, max_class <= 3, route_seg >= 1, adaptive and route_all_few 0 or 1";
+		return 1;
+	}
+	if ((with_order && !sub_cost) || (with_list && !pair_cost) || (with_list && items_order != ANDI_ITEMS_HEAVY && items_order != ANDI_ITEMS_LIGHT)) {
+		ctx->err = "andi_hip_test_layout_kernels: sub_order needs sub_cost, a list needs pair_cost and an order of ANDI_ITEMS_HEAVY or ANDI_ITEMS_LIGHT";
+		return 1;
+	}
+	const size_t P = (size_t)P64;
+	// the wavefront layout's segmentation, and what the lists can hold at the most: every pair's wavefronts as given, and at the
+	// shortest segment length (a bumped or handed-back pair's are counted anew from its class)
+	std::vector<uint32_t> start(nq + 1);
+	uint64_t total = 0, waves_q = 0, waves_in = 0;
+	for (size_t i = 0; i < nq; ++i) {
+		start[i] = (uint32_t)total;
+		total += (qlen[i] + (uint64_t)route_seg - 1) / route_seg;
+		waves_q += ((qlen[i] + (uint64_t)seg0 - 1) / seg0 + 63) / 64;
+		if (total >= UINT32_MAX) break;
+	}
+	start[nq] = (uint32_t)total;
+	for (size_t i = 0; i < P; ++i) waves_in += pair_waves[i];
+	const uint64_t quad_cap = waves_in + waves_q * nsub; // (a pair keeps the wavefronts it came with or gets at most those of class 0)
+	if (total >= UINT32_MAX || total * nsub > UINT32_MAX || (with_list && total * nsub > LIMIT) || quad_cap > LIMIT) {
+		ctx->err = "andi_hip_test_layout_kernels: more segments or wavefronts than 32 bits (and this hook) take";
+		return 1;
+	}
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const hipStream_t st = ctx->stream;
+	DevScope dev(st);
+	uint32_t *d_qlen = nullptr, *d_start = nullptr, *d_waves = nullptr, *d_wave0 = nullptr, *d_bsum = nullptr, *d_count = nullptr, *d_order = nullptr;
+	uint32_t *d_hist = nullptr, *d_items = nullptr, *d_waves2 = nullptr, *d_wave02 = nullptr, *d_bsum2 = nullptr, *d_count2 = nullptr;
+	unsigned long long *d_quad = nullptr, *d_quad2 = nullptr, *d_nt = nullptr; // (a list of words in pass B's list of 64-bit entries: scan.h)
+	int64_t *d_self = nullptr;
+	uint8_t *d_class = nullptr, *d_cost = nullptr;
+	float *d_subcost = nullptr;
+	const size_t nblocks = (P + 1023) / 1024, n_items = (size_t)(total * nsub), quad_words = (size_t)quad_cap;
+	dev.alloc(&d_qlen, nq), dev.alloc(&d_start, (size_t)nq + 1), dev.alloc(&d_self, nsub), dev.alloc(&d_class, P), dev.alloc(&d_waves, P);
+	dev.alloc(&d_count, 16), dev.alloc(&d_nt, 3);
+	if (adaptive) dev.alloc(&d_wave0, P + 1), dev.alloc(&d_bsum, P / 1024 + 2), dev.alloc(&d_quad, quad_words / 2 + 1);
+	if (with_order) dev.alloc(&d_subcost, nsub), dev.alloc(&d_order, nsub);
+	if (with_list) dev.alloc(&d_cost, P), dev.alloc(&d_hist, ANDI_COST_CLASSES * nblocks), dev.alloc(&d_items, n_items + 1);
+	if (left) {
+		dev.alloc(&d_waves2, P), dev.alloc(&d_count2, 16);
+		if (adaptive) dev.alloc(&d_wave02, P + 1), dev.alloc(&d_bsum2, P / 1024 + 2), dev.alloc(&d_quad2, quad_words / 2 + 1);
+	}
+	HIP_TRY(ctx, dev.err);
+	uint32_t h_count[16] = {};
+	h_count[ANDI_STRUCT_WAVES] = strct;
+	HIP_TRY(ctx, hipMemcpyAsync(d_qlen, qlen, nq * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_start, start.data(), ((size_t)nq + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_self, self, nsub * sizeof(int64_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_class, pair_class, P, hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_waves, pair_waves, P * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemcpyAsync(d_count, h_count, sizeof h_count, hipMemcpyHostToDevice, st));
+	HIP_TRY(ctx, hipMemsetAsync(d_nt, 0, 3 * sizeof(unsigned long long), st));
+	if (with_order) HIP_TRY(ctx, hipMemcpyAsync(d_subcost, sub_cost, nsub * sizeof(float), hipMemcpyHostToDevice, st));
+	if (with_list) HIP_TRY(ctx, hipMemcpyAsync(d_cost, pair_cost, P, hipMemcpyHostToDevice, st));
+	if (left) HIP_TRY(ctx, hipMemsetAsync(d_count2, 0, 16 * sizeof(uint32_t), st));
+	HIP_TRY(ctx, hipStreamSynchronize(st)); // (h_count and start are this frame's)
+	ScanArgs a{};
+	a.self = d_self, a.nsub = nsub, a.qlen = d_qlen, a.nq = nq;
+	a.qseg_start = d_start, a.total_segs = (uint32_t)total, a.seg = route_seg;
+	a.restitch_count = d_count, a.defer_count = d_count + 8, a.defer_list = d_quad;
+	a.adaptive = (int)adaptive, a.seg0 = seg0, a.max_class = max_class;
+	a.pair_class = d_class, a.pair_waves = d_waves, a.pair_wave0 = d_wave0, a.pair_bsum = d_bsum;
+	a.pair_cost = d_cost, a.item_hist = d_hist, a.items_order = ANDI_ITEMS_GRID;
+	a.sub_cost = d_subcost, a.sub_order = d_order;
+	a.route = ANDI_LAYOUT_LANES, a.route_seg = route_seg, a.route_all_few = all_few, a.route_nt = d_nt;
+	ScanArgs b = a; // the wavefront kernel's layout (launch_routed)
+	b.adaptive = 0, b.coop = 1, b.route = ANDI_LAYOUT_COOP;
+	b.coop_items = d_items, b.items_order = with_list ? items_order : (uint32_t)ANDI_ITEMS_GRID, b.layout_count = d_count;
+	const bool small = P <= 1024 && allow_small;
+	if (info) info[0] = small ? 1u : 2u, info[1] = with_list ? (nblocks == 1 ? 1u : 3u) : 0u, info[2] = (uint32_t)total, info[3] = (uint32_t)quad_words;
+	HIP_TRY(ctx, andi_launch_pair_routing(a, st, allow_small));
+	if (with_list) HIP_TRY(ctx, andi_launch_coop_items(b, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	std::vector<uint8_t> cls(P);
+	HIP_TRY(ctx, hipMemcpy(h_count, d_count, sizeof h_count, hipMemcpyDeviceToHost));
+	HIP_TRY(ctx, hipMemcpy(cls.data(), d_class, P, hipMemcpyDeviceToHost));
+	if (h_count[ANDI_QUAD_WAVES] > quad_words || h_count[ANDI_COOP_SEGS] > n_items) {
+		ctx->err = "andi_hip_test_layout_kernels: a list's counter is beyond what the list holds";
+		return 1;
+	}
+	if (counts1) memcpy(counts1, h_count, sizeof h_count);
+	if (class1) memcpy(class1, cls.data(), P);
+	if (waves1) HIP_TRY(ctx, hipMemcpy(waves1, d_waves, P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (wave01 && adaptive) HIP_TRY(ctx, hipMemcpy(wave01, d_wave0, (P + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (order && with_order) HIP_TRY(ctx, hipMemcpy(order, d_order, nsub * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (quad && adaptive && h_count[ANDI_QUAD_WAVES]) HIP_TRY(ctx, hipMemcpy(quad, d_quad, h_count[ANDI_QUAD_WAVES] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (items && with_list && h_count[ANDI_COOP_SEGS]) HIP_TRY(ctx, hipMemcpy(items, d_items, h_count[ANDI_COOP_SEGS] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (left) {
+		for (size_t i = 0; i < P; ++i)
+			if (left[i]) cls[i] |= ANDI_ROUTE_LEFT;
+		HIP_TRY(ctx, hipMemcpyAsync(d_class, cls.data(), P, hipMemcpyHostToDevice, st));
+		ScanArgs a2 = a; // the pairs handed back: a lane layout of their own
+		a2.route = ANDI_LAYOUT_LANES2;
+		a2.pair_waves = d_waves2, a2.pair_wave0 = d_wave02, a2.pair_bsum = d_bsum2;
+		a2.restitch_count = d_count2, a2.defer_count = d_count2 + 8, a2.defer_list = d_quad2;
+		HIP_TRY(ctx, andi_launch_pair_leftover(a2, st));
+	}
+	HIP_TRY(ctx, andi_launch_route_count(a, st));
+	HIP_TRY(ctx, hipStreamSynchronize(st));
+	if (class2) HIP_TRY(ctx, hipMemcpy(class2, d_class, P, hipMemcpyDeviceToHost));
+	if (waves2 && left) HIP_TRY(ctx, hipMemcpy(waves2, d_waves2, P * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (wave02 && left && adaptive) HIP_TRY(ctx, hipMemcpy(wave02, d_wave02, (P + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (counts2 && left) HIP_TRY(ctx, hipMemcpy(counts2, d_count2, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	if (route_nt) HIP_TRY(ctx, hipMemcpy(route_nt, d_nt, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	return 0;
+}
 #endif
 
 int andi_hip_esa_single_form(const andi_hip_esa *e) { return e && e->index_built ? e->deep_ext : 0; }

@@ -170,6 +170,10 @@ hipError_t andi_launch_pack_planes(const uint8_t *N0, size_t symbols, uint32_t *
 // adaptive mode: sample every pair's match lengths, choose its segment length (and, in a routed call, its pass A), lay out the slots
 // (more: sixteen further words to clear with the layout's own counters, or null -- a routed call's second restitch_count)
 hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st, uint32_t *more = nullptr);
+// ... its part behind the sampling, on pair_class, pair_waves, pair_cost, sub_cost and restitch_count[ANDI_STRUCT_WAVES] as k_pair_estimate
+// leaves them: the routing, the subjects' order, the offsets -- one block for a routed call of at most 1024 pairs (allow_small = false:
+// the kernels of the larger calls all the same; only the suite's hook passes it)
+hipError_t andi_launch_pair_routing(const ScanArgs &a, hipStream_t st, bool allow_small = true);
 // routed calls: the second lane layout (a2: the pairs pass A by wavefronts handed back); who took what, for the timings
 hipError_t andi_launch_pair_leftover(const ScanArgs &a2, hipStream_t st);
 hipError_t andi_launch_route_count(const ScanArgs &a, hipStream_t st);

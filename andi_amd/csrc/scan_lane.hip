@@ -1530,7 +1530,14 @@ hipError_t andi_launch_pair_layout(const ScanArgs &a, hipStream_t st, uint32_t *
 	if (P <= 4096) k_pair_estimate<<<P, P <= 1024 ? 64 * EST_WAVES_FEW : 64 * EST_WAVES, 0, st>>>(a, false);
 	else k_pair_estimate<<<(P + 3) / 4, 256, 0, st>>>(a, true);
 	CHECK_LAUNCH();
-	if (a.route && P <= 1024) { // (routing, the subjects' order and the offsets in one launch)
+	return andi_launch_pair_routing(a, st);
+}
+
+// ... and everything behind the sampling: the routing, the subjects' order, the offsets (allow_small = false: the kernels of the
+// larger calls whatever the number of pairs -- the suite's hook andi_hip_test_layout_kernels, api.hip, compares the two paths)
+hipError_t andi_launch_pair_routing(const ScanArgs &a, hipStream_t st, bool allow_small) {
+	const uint32_t P = a.nsub * a.nq;
+	if (a.route && P <= 1024 && allow_small) { // (routing, the subjects' order and the offsets in one launch)
 		k_pair_layout_small<<<1, 1024, 0, st>>>(a);
 		CHECK_LAUNCH();
 		return hipSuccess;

@@ -199,6 +199,7 @@ HOOK_SYMBOLS = {
     "andi_hip_test_pair_layout": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "andi_hip_test_query_codes": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_size_t]),
     "andi_hip_test_stitch_slots": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "andi_hip_test_layout_kernels": (C.c_int, [_P] * 22),
 }
 
 _lib = None
@@ -636,6 +637,48 @@ class Context:
         waves, wave0, order, counts = np.zeros(pairs, np.uint32), np.zeros(pairs + 1, np.uint32), np.zeros(nsub, np.uint32), np.zeros(16, np.uint32)
         self._check(hook(self._h, waves.ctypes.data, wave0.ctypes.data, order.ctypes.data, counts.ctypes.data, info.ctypes.data), "test_pair_layout")
         return {"pair_waves": waves, "pair_wave0": wave0 if info[2] else None, "sub_order": order, "counts": counts if info[3] else None}
+
+    def layout_kernels(self, nsub, nq, qlen, self_q, pair_class, pair_waves, pair_cost=None, sub_cost=None, *, struct_waves=0, seg0=64, max_class=3,
+                       route_seg=2048, route_all_few=0, adaptive=1, items_order=1, sub_order=True, listed=True, allow_small=True, left=None):
+        """(a test hook) the layout kernels of a routed scan call alone, on the caller's arrays (api.hip: andi_hip_test_layout_kernels; no
+        subject, no query text, no sampling): pair_class, pair_waves, pair_cost of all nsub * nq pairs and sub_cost as k_pair_estimate would
+        leave them, struct_waves its restitch_count[ANDI_STRUCT_WAVES]; left: a mask of the pairs marked ANDI_ROUTE_LEFT behind the routing
+        (None: no second layout).  Returns a dict: stage 1 -- pair_class, pair_waves, pair_wave0 (None unless adaptive), sub_order (None
+        without one), counts, quad (k_lane_quad's list), items (None without a list) --, stage 2 -- pair_class2, route_nt and, with `left`,
+        pair_waves2, pair_wave02 (adaptive), counts2 --, and path (1: one block, 2: several kernels), sort_launches, total_segs."""
+        hook = _hook("andi_hip_test_layout_kernels")
+        P, LIMIT = int(nsub) * int(nq), 1 << 27
+        u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32)
+        qlen, self_q = u32(qlen), np.ascontiguousarray(self_q, dtype=np.int64)
+        pair_class, pair_waves = np.ascontiguousarray(pair_class, dtype=np.uint8), u32(pair_waves)
+        pair_cost = None if pair_cost is None else np.ascontiguousarray(pair_cost, dtype=np.uint8)
+        sub_cost = None if sub_cost is None else np.ascontiguousarray(sub_cost, dtype=np.float32)
+        left = None if left is None else np.ascontiguousarray(np.asarray(left) != 0, dtype=np.uint8)
+        sane = 0 < P <= LIMIT  # (beyond: the library refuses before it reads an array)
+        if sane:
+            for arr, n in ((qlen, nq), (self_q, nsub), (pair_class, P), (pair_waves, P), (pair_cost, P), (sub_cost, nsub), (left, P)):
+                if arr is not None and arr.shape != (n,):
+                    raise ValueError("layout_kernels: an array of %s where %d entries are due" % (arr.shape, n))
+        par = np.array([nsub, nq, struct_waves, seg0, max_class, route_seg, route_all_few, adaptive, items_order, int(bool(sub_order)), int(bool(listed)),
+                        int(bool(allow_small))], dtype=np.uint32)
+        total = int(((qlen.astype(np.int64) + route_seg - 1) // route_seg).sum()) if sane and route_seg > 0 else 0
+        quad_cap = int(pair_waves.sum(dtype=np.int64)) + int(nsub) * int((((qlen.astype(np.int64) + seg0 - 1) // seg0 + 63) // 64).sum()) if sane and seg0 > 0 else 0
+        z = lambda n, t=np.uint32: np.zeros(n, t) if sane and n <= LIMIT else None
+        out = {"pair_class": z(P, np.uint8), "pair_waves": z(P), "pair_wave0": z(P + 1) if adaptive else None, "sub_order": z(nsub) if sub_order else None,
+               "counts": np.zeros(16, np.uint32), "quad": z(quad_cap), "items": z(int(nsub) * total) if listed else None, "pair_class2": z(P, np.uint8),
+               "pair_waves2": z(P) if left is not None else None, "pair_wave02": z(P + 1) if left is not None and adaptive else None,
+               "counts2": np.zeros(16, np.uint32) if left is not None else None, "route_nt": np.zeros(3, np.uint64)}
+        info = np.zeros(4, np.uint32)
+        p = lambda a: None if a is None else a.ctypes.data
+        self._check(hook(self._h, p(par), p(qlen), p(self_q), p(pair_class), p(pair_waves), p(pair_cost), p(sub_cost), p(left),
+                         *[p(out[k]) for k in ("pair_class", "pair_waves", "pair_wave0", "sub_order", "counts", "quad", "items", "pair_class2",
+                                               "pair_waves2", "pair_wave02", "counts2", "route_nt")], p(info)), "test_layout_kernels")
+        if out["quad"] is not None:
+            out["quad"] = out["quad"][: int(out["counts"][13])]  # (scan.h: ANDI_QUAD_WAVES)
+        if out["items"] is not None:
+            out["items"] = out["items"][: int(out["counts"][7])]  # (ANDI_COOP_SEGS)
+        out.update(path=int(info[0]), sort_launches=int(info[1]), total_segs=int(info[2]))
+        return out
 
     def stitch_slots(self):
         """(a test hook) the per-slot records of the last scan call that used one segment length (not routed, no per-pair lengths),

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import andi_amd
+import layout_model
 from andi_amd import synth
 from conftest import knobs, rand_dna
 from oracle import orc
@@ -74,6 +75,8 @@ def test_star_set_same_counts_under_every_order(star, model):
         assert (items is None) == (order == "G"), order
         if items is not None:
             assert (np.sort(items) == _expected_items(cls, [len(s) for s in star], 2048, 6)).all(), order
+            exact = layout_model.coop_items(6, 6, [len(s) for s in star], 2048, cls, cost, layout_model.ITEMS_LIGHT if order == "R" else layout_model.ITEMS_HEAVY)
+            assert len(items) == len(exact) and (items == exact).all(), order  # (entry by entry: the stable order scan.h promises)
             c = cost[_pairs_of(items.astype(np.int64), [len(s) for s in star], 2048, 6)[0]].astype(int)
             if order is None:
                 assert (np.diff(c) <= 0).all() and c[0] > c[-1]
@@ -124,9 +127,12 @@ def test_ragged_set_of_4830_pairs_and_its_list(ragged, seg):
     pairs, _ = _pairs_of(items.astype(np.int64), lens, seg, 70)
     assert (pairs // 70 != pairs % 70).all()
     assert not (cls.reshape(70, 70).diagonal() & ROUTE_COOP).any()
-    # classes do not rise along the list (the order inside a class is left open)
+    # classes do not rise along the list; inside a class the pairs stand in slot order, a pair's segments in theirs (scan.h: a stable sort) --
+    # entry by entry what tests/layout_model.py makes of the call's final pair_class and pair_cost
     c = cost[pairs].astype(int)
     assert (np.diff(c) <= 0).all() and c[0] > c[-1]
+    exact = layout_model.coop_items(70, 70, lens, seg, cls, cost)
+    assert len(items) == len(exact) and (items == exact).all(), np.nonzero(items != exact)[0][:8].tolist()
     short = np.asarray(lens) < seg
     if seg == 8192:
         assert short.any() and not short.all() and not short[pairs % 70].any()
