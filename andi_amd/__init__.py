@@ -14,5 +14,6 @@ from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_rang
                   DELTA, delta_scores,
                   PLACEMENT, distances_rect, jplace, parse_newick, place,
                   ROOT, newick_rooted, root,
+                  FIT, fit, relength,
                   Sketches, screen, screen_select, sketch, sketch_shared,
                   scan_rows, subject_prepare, suffix_array)

@@ -567,6 +567,33 @@ done:
 	return ret;
 }
 
+/* andi_hip_fit's lengths put into the records (include/andi_hip.h) */
+int andi_hip_relength(const andi_hip_nj_join *J, size_t n, const double *len, andi_hip_nj_join *out) {
+	if (!J || !len || !out || n < 3) return 1;
+	const size_t pairs = n - 3;
+	uint8_t *seen = calloc(n + pairs, 1);
+	if (!seen) return 1;
+	for (size_t s = 0; s <= pairs; s++) { /* every child a leaf or an earlier record's node, and a child once */
+		const int32_t ch[3] = {J[s].a, J[s].b, J[s].c};
+		const int kids = s == pairs ? 3 : 2;
+		for (int k = 0; k < kids; k++) {
+			if (ch[k] < 0 || (size_t)ch[k] >= n + s || (size_t)ch[k] >= n + pairs || seen[ch[k]]) {
+				free(seen);
+				return 1;
+			}
+			seen[ch[k]] = 1;
+		}
+	}
+	free(seen);
+	for (size_t s = 0; s <= pairs; s++) {
+		andi_hip_nj_join r = J[s];
+		r.la = len[r.a], r.lb = len[r.b];
+		if (s == pairs) r.lc = len[r.c];
+		out[s] = r;
+	}
+	return 0;
+}
+
 /* ------------------------------------------------------------------ */
 /* The majority-rule consensus tree of a bootstrap (include/andi_hip.h) */
 /* ------------------------------------------------------------------ */

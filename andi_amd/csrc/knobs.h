@@ -11,7 +11,7 @@
 
 #define ANDI_KNOB_LIST_SHIPPED(X) X(ARENA_KEEP) X(ARENA_MB) X(COOP) X(E2E_TRACE) X(FORCE_REFERENCE) X(GATHER) X(POOL)
 #define ANDI_KNOB_LIST_HOOKS(X)                                                                                            \
-	X(COOP_GIVEUP) X(COOP_ORDER) X(COOP_SEG) X(COOP_STATS) X(DEEP_K) X(FORCE_ADAPTIVE) X(KNOCK) X(LANE_STATS) X(NJ_GROUP) X(NO_RESTITCH)       \
+	X(COOP_GIVEUP) X(COOP_ORDER) X(COOP_SEG) X(COOP_STATS) X(DEEP_K) X(FIT_GROUP) X(FORCE_ADAPTIVE) X(KNOCK) X(LANE_STATS) X(NJ_GROUP) X(NO_RESTITCH)       \
 	X(NO_SIDE_STREAM) X(PLACE_GROUP) X(POOL_FIRST) X(POOL_MATCH) X(QUAD_BLOCKS4) X(QUERIES_BYTES) X(QUERIES_PACKED) X(QUAD_MATCH) X(QUAD_UNLISTED) \
 	X(RECT_BATCH) X(ROOT_GROUP) X(ROUTE_SMALL) X(ROUTE_TINY) X(SEG0) X(SEG_FACTOR) X(SKETCH_BATCH) X(SKETCH_LDS) X(SPLIT_HASH_BITS) X(UNIFORM_SEGMENTS) X(UPLOAD_MIN_MB)
 #define ANDI_KNOB_LIST(X) ANDI_KNOB_LIST_SHIPPED(X) ANDI_KNOB_LIST_HOOKS(X)

@@ -429,6 +429,14 @@ static void usage(int status) {
 		"                       the branch (its jplace edge number), the distance from the branch's lower end, the branch's\n"
 		"                       length, the score sqrt(SS / pairs), the root ambiguity index and the number of leaf pairs used\n"
 		"                       ('nan' for score and ambiguity under midpoint)\n"
+		"      --lengths=KIND   The branch lengths of every tree of --tree, --support and --transfer: 'joined' (as the joining\n"
+		"                       gives them; the default) or 'ols': refit to the tree's own matrix by ordinary least squares on\n"
+		"                       the GPU (as FastME's OLS lengths; negative lengths are kept), before --root roots the tree.\n"
+		"                       The consensus tree, placements and clusters are not touched; not together with --trees-only\n"
+		"      --fit=FILE       Write how well the first matrix's tree explains its distances to FILE, tab-separated: the\n"
+		"                       residual sum of squares and R^2 under least-squares and under the joined lengths, the trees'\n"
+		"                       lengths and negative branches, the worst-fitted pair; then every genome's share of the two\n"
+		"                       sums of squares.  Works without --tree; after --complete, if given\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -527,9 +535,30 @@ typedef struct {
 	size_t used;
 	const andi_hip_cons_node *nodes;
 	size_t ninner;
-	andi_hip_ctx *ctx; /* --root: the context the tree is rooted on */
+	andi_hip_ctx *ctx; /* --root, --lengths: the context the tree is rooted and refit on */
 	int point;         /* --root-report: this is the point estimate's tree */
+	const double *D;   /* --lengths=ols: the n x n matrix J was joined from (NULL: the lengths stay) */
 } newick_src;
+
+/* --lengths=ols: every line of records J that comes with its matrix is written with the least-squares lengths of that
+ * matrix (andi_hip_fit, andi_hip_relength), before it is rooted; the consensus tree has no records and is not. */
+static int lengths_ols;
+
+/* The records of w with the refit lengths, or NULL (and a soft warning) if the fit failed. */
+static andi_hip_nj_join *refit_records(const newick_src *w, size_t n) {
+	double *len = xmalloc((2 * n - 3) * sizeof *len);
+	andi_hip_nj_join *out = xmalloc((n - 2) * sizeof *out);
+	andi_hip_fit_result r;
+	if (andi_hip_fit(w->ctx, w->J, n, w->D, ANDI_FIT_OLS, len, &r, NULL, NULL)) {
+		soft_warnx("A tree is written with its joined lengths: %s", andi_hip_last_error(w->ctx));
+		free(out), out = NULL;
+	} else if (andi_hip_relength(w->J, n, len, out)) {
+		soft_warnx("A tree is written with its joined lengths: its records are malformed.");
+		free(out), out = NULL;
+	}
+	free(len);
+	return out;
+}
 
 /* --root: every line of records J is written rooted (andi_hip_root, andi_hip_format_newick_rooted), with the labels that
  * belong to its branches moved with them; the consensus tree is not.  --root-report: the point estimate's root. */
@@ -591,7 +620,11 @@ static char *rooted_newick(const newick_src *w, const char **names, size_t n, in
 }
 
 /* one Newick line to the file o */
-static void put_newick(const tree_file *o, const newick_src *w, const char **names, size_t n, int truncate) {
+static void put_newick(const tree_file *o, const newick_src *given, const char **names, size_t n, int truncate) {
+	newick_src src = *given;
+	const newick_src *w = &src;
+	andi_hip_nj_join *refit = NULL;
+	if (lengths_ols && src.J && src.D && src.ctx && n >= 3 && (refit = refit_records(given, n))) src.J = refit;
 	size_t cap = 64 + n * (w->nodes ? 80 : w->depth ? 60 : 52);
 	for (size_t i = 0; i < n; i++) cap += strlen(names[i]);
 	char *text = xmalloc(cap);
@@ -602,7 +635,7 @@ static void put_newick(const tree_file *o, const newick_src *w, const char **nam
 		if (rooted) free(text), text = rooted;
 	}
 	if (fputs(text, o->f) == EOF) err(1, "%s", o->path);
-	free(text);
+	free(text), free(refit);
 }
 
 /* --complete: every matrix that goes into a joined tree has its missing distances estimated from quartets first
@@ -740,6 +773,73 @@ static void delta_report(tree_out *t, const andi_hip_model *M, const char **name
 	free(D), free(rec);
 }
 
+/* --fit: how well the point estimate's tree explains its matrix (andi_hip_fit), from a tree of its own (--tree-method's),
+ * joined from the matrix as --complete leaves it.  On the context of --tree, made here if this comes first. */
+typedef struct {
+	const char *path;
+	FILE *f;
+} fit_opts;
+static fit_opts fitopt;
+
+static void put_g(FILE *f, double x, char end) {
+	if (isnan(x)) fprintf(f, "nan%c", end); /* (a NaN carries a sign that would be printed) */
+	else fprintf(f, "%.8g%c", x, end);
+}
+
+static void fit_report(tree_out *t, const andi_hip_model *M, const genome *g, const char **names, size_t n, int model, int truncate) {
+	char msg[512];
+	if (!t->failed && !t->ctx && andi_hip_ctx_create(&t->ctx, t->device_for_ctx, msg, sizeof msg)) {
+		t->failed = 1, t->ctx = NULL;
+		soft_warnx("No trees: %s", msg);
+	}
+	if (t->failed) return;
+	double *D = malloc(n * n * sizeof *D), *len = malloc((2 * n) * sizeof *len), *ss = malloc(2 * n * sizeof *ss);
+	andi_hip_nj_join *J = malloc(n * sizeof *J);
+	if (!D || !len || !ss || !J || andi_hip_distances(M, n, model, D)) err(errno, "Could not allocate enough memory for the fit report.");
+	andi_hip_fit_result r;
+	int ok = 1;
+	if (cmpl.on && complete_one(t->ctx, D, n, 1)) {
+		soft_warnx("No fit report: %s", andi_hip_last_error(t->ctx));
+		ok = 0;
+	}
+	for (size_t i = 0; i < n && ok; i++)
+		for (size_t j = i + 1; j < n; j++)
+			if (!isfinite(D[i * n + j])) {
+				soft_warnx("No fit report: the distance of '%s' and '%s'%s", g[i].name, g[j].name, NOT_FINITE);
+				ok = 0;
+				break;
+			}
+	if (ok && n < 3) {
+		soft_warnx("No fit report: a tree of two sequences has one branch and nothing to fit.");
+		ok = 0;
+	}
+	if (ok && (join_one(t->ctx, D, n, t->method, J) || andi_hip_fit(t->ctx, J, n, D, ANDI_FIT_OLS, len, &r, ss, ss + n))) {
+		soft_warnx("No fit report: %s", andi_hip_last_error(t->ctx));
+		ok = 0;
+	}
+	if (ok) {
+		const int w = truncate ? 10 : -1; /* (as the matrix prints a name) */
+		FILE *f = fitopt.f;
+		fputs("#method\tpairs\trss\trss_joined\ttss\tr2\tr2_joined\tlength\tlength_joined\tnegative\tnegative_joined\tworst_first\t"
+			  "worst_second\tworst_residual\n", f);
+		fprintf(f, "ols\t%llu\t", (unsigned long long)r.pairs);
+		put_g(f, r.rss, '\t'), put_g(f, r.rss_joined, '\t'), put_g(f, r.tss, '\t');
+		put_g(f, r.tss == 0 ? NAN : 1.0 - r.rss / r.tss, '\t'), put_g(f, r.tss == 0 ? NAN : 1.0 - r.rss_joined / r.tss, '\t');
+		put_g(f, r.length, '\t'), put_g(f, r.length_joined, '\t');
+		fprintf(f, "%u\t%u\t", (unsigned)r.negative, (unsigned)r.negative_joined);
+		if (r.worst_b >= 0) fprintf(f, "%.*s\t%.*s\t", w, names[r.worst_b], w, names[r.worst_c]);
+		else fputs("-\t-\t", f);
+		put_g(f, r.worst, '\n');
+		fputs("#name\tss\tss_joined\n", f);
+		for (size_t i = 0; i < n; i++) {
+			fprintf(f, "%.*s\t", w, names[i]);
+			put_g(f, ss[i], '\t'), put_g(f, ss[n + i], '\n');
+		}
+		if (ferror(f)) err(1, "%s", fitopt.path);
+	}
+	free(D), free(len), free(ss), free(J);
+}
+
 static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, const char **names, size_t n, int model, int truncate,
 					   int k) {
 	if (t->failed) return;
@@ -769,7 +869,7 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
 		free(D), free(J);
 		return;
 	}
-	put_newick(t->o, &(newick_src){.J = J, .ctx = t->ctx, .point = k == 1}, names, n, truncate);
+	put_newick(t->o, &(newick_src){.J = J, .ctx = t->ctx, .point = k == 1, .D = D}, names, n, truncate);
 	free(D), free(J);
 }
 
@@ -804,7 +904,7 @@ typedef struct {
 	const tree_file *o; /* outs */
 	size_t nrec, nsup, cap; /* cap: the replicates of one andi_hip_nj_batch / andi_hip_bootstrap_nj call, at most */
 	unsigned long counted;
-	double *D;
+	double *D, *Dpoint; /* Dpoint: --lengths=ols: the point estimate's matrix, kept beside its tree */
 	andi_hip_nj_join *J, *Rall;
 	int64_t *bad;
 	uint64_t *cmissing, *cleft; /* --complete: a chunk's counts of andi_hip_complete_batch */
@@ -860,6 +960,10 @@ static void support_begin(support_state *s, const tree_file *o, const boot_run *
 		if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(r->ctx));
 		s->point_ok = s->trans_ok = s->rogue_ok = 0;
 	}
+	if (lengths_ols && !trees_only && (s->point_ok || s->trans_ok)) { /* (the chunks' matrices take D's place) */
+		if (!(s->Dpoint = malloc(n * n * sizeof *D))) err(errno, "Could not allocate enough memory for the support values.");
+		memcpy(s->Dpoint, D, n * n * sizeof *D);
+	}
 }
 
 /* replicates start ... start + count - 1: their matrices B (count * n * n models), or NULL under --trees-only */
@@ -899,7 +1003,7 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			if (skip[k])
 				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s'%s", first + (unsigned long)k + 2,
 						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name, NOT_FINITE);
-			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec, .ctx = ctx}, s->r.names, n, s->r.truncate);
+			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec, .ctx = ctx, .D = s->r.trees_only ? NULL : s->D + k * n * n}, s->r.names, n, s->r.truncate);
 			s->counted += !skip[k];
 		}
 		/* (whatever fails below, the replicates' lines of --tree are still written) */
@@ -939,7 +1043,7 @@ static void support_end(support_state *s, int complete) {
 	if (!complete) s->point_ok = s->trans_ok = s->cons_ok = s->rogue_ok = 0;
 	if (s->point_ok) {
 		if (counted < replicates) soft_warnx("Support values from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total, .ctx = ctx, .point = 1}, names, n, s->r.truncate);
+		put_newick(&s->o[OUT_SUPPORT], &(newick_src){.J = s->J, .support = s->total, .ctx = ctx, .point = 1, .D = s->Dpoint}, names, n, s->r.truncate);
 	}
 	if (s->trans_ok && counted == 0) {
 		soft_warnx("No transfer support: no bootstrap matrix has a tree.");
@@ -947,7 +1051,7 @@ static void support_end(support_state *s, int complete) {
 	}
 	if (s->trans_ok) {
 		if (counted < replicates) soft_warnx("Transfer support from %lu of %lu bootstrap matrices.", counted, replicates);
-		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted, .ctx = ctx, .point = 1}, names, n,
+		put_newick(&s->o[OUT_TRANSFER], &(newick_src){.J = s->J, .depth = s->depth, .transfer = s->ttotal, .used = counted, .ctx = ctx, .point = 1, .D = s->Dpoint}, names, n,
 				   s->r.truncate);
 	}
 	if (s->rogue_ok && counted == 0) {
@@ -986,7 +1090,7 @@ static void support_end(support_state *s, int complete) {
 		andi_hip_free(freq), andi_hip_free(sets);
 		free(ids), free(nodes);
 	}
-	free(s->D), free(s->J), free(s->Rall), free(s->bad), free(s->cmissing), free(s->cleft), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
+	free(s->D), free(s->Dpoint), free(s->J), free(s->Rall), free(s->bad), free(s->cmissing), free(s->cleft), free(s->skipall), free(s->total), free(s->part), free(s->depth), free(s->ttotal),
 		free(s->tpart), free(s->moved), free(s->mpart);
 }
 
@@ -1350,6 +1454,8 @@ int main(int argc, char *argv[]) {
 												 {"delta", required_argument, NULL, 0},
 												 {"root", required_argument, NULL, 0},
 												 {"root-report", required_argument, NULL, 0},
+												 {"lengths", required_argument, NULL, 0},
+												 {"fit", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1408,6 +1514,12 @@ int main(int argc, char *argv[]) {
 					rootopt.on = 1;
 				}
 				if (!strcmp(o, "root-report")) rootopt.report_path = optarg;
+				if (!strcmp(o, "lengths")) {
+					if (!strcasecmp(optarg, "joined")) lengths_ols = 0;
+					else if (!strcasecmp(optarg, "ols")) lengths_ols = 1;
+					else errx(1, "Expected one of 'joined' or 'ols' for --lengths, but '%s' was given.", optarg);
+				}
+				if (!strcmp(o, "fit")) fitopt.path = optarg;
 				if (!strcmp(o, "rogues")) rogues.path = optarg;
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
@@ -1545,6 +1657,9 @@ int main(int argc, char *argv[]) {
 	if (rootopt.report_path && !rootopt.on) errx(1, "A root report (--root-report) needs a rooting method: give --root=mad or --root=midpoint.");
 	if (cmpl.on && trees_only)
 		errx(1, "Missing distances (--complete) are not derived together with --trees-only: the bootstrap matrices stay on the GPU.");
+	if (lengths_ols && trees_only)
+		errx(1, "Branch lengths (--lengths=ols) are not refit together with --trees-only: the bootstrap matrices stay on the GPU.");
+	if (fitopt.path && rect) errx(1, "A fit report (--fit) is" WITH_REFERENCE);
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
 	if (clus.have_threshold && !clus.clusters_path) errx(1, "A threshold (--threshold) needs somewhere to go: give --clusters=FILE.");
 	if (place.path && !rect) errx(1, "Placement (--place) needs references to place on: give --reference=FILE or --reference-list=FILE.");
@@ -1571,6 +1686,7 @@ int main(int argc, char *argv[]) {
 	if (rogues.path && !(rogues.f = fopen(rogues.path, "w"))) err(1, "%s", rogues.path);
 	if (cmpl.report_path && !(cmpl.rf = fopen(cmpl.report_path, "w"))) err(1, "%s", cmpl.report_path);
 	if (dlt.path && !(dlt.f = fopen(dlt.path, "w"))) err(1, "%s", dlt.path);
+	if (fitopt.path && !(fitopt.f = fopen(fitopt.path, "w"))) err(1, "%s", fitopt.path);
 	if (rootopt.report_path) {
 		if (!(rootopt.rf = fopen(rootopt.report_path, "w"))) err(1, "%s", rootopt.report_path);
 		fputs("#method\tedge\tdistal\tlength\tscore\tambiguity\tpairs\n", rootopt.rf);
@@ -1621,6 +1737,7 @@ int main(int argc, char *argv[]) {
 	print_distances(M, NULL, names, n, NULL, 0, opts.model, verbose >= 2, truncate, 1);
 	if (cmpl.rf) complete_report(&tree, M, names, n, opts.model, truncate);
 	if (dlt.f) delta_report(&tree, M, names, n, opts.model, truncate);
+	if (fitopt.f) fit_report(&tree, M, all.v, names, n, opts.model, truncate);
 	if (tree.o->f) write_tree(&tree, M, all.v, names, n, opts.model, truncate, 1);
 	if (clus.df || clus.cf) cluster_point(&clus, M, names, n, opts.model, truncate);
 	if (cli_trace) {
@@ -1690,6 +1807,7 @@ int main(int argc, char *argv[]) {
 	if (rogues.f && fclose(rogues.f)) err(1, "%s", rogues.path);
 	if (cmpl.rf && fclose(cmpl.rf)) err(1, "%s", cmpl.report_path);
 	if (dlt.f && fclose(dlt.f)) err(1, "%s", dlt.path);
+	if (fitopt.f && fclose(fitopt.f)) err(1, "%s", fitopt.path);
 	if (rootopt.rf && fclose(rootopt.rf)) err(1, "%s", rootopt.report_path);
 	free(M);
 	free(in);

@@ -139,6 +139,8 @@ SYMBOLS = {
     "andi_hip_root": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P, _P, _P]),
     "andi_hip_format_newick_rooted": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, C.c_int32, C.c_double,
                                                    C.POINTER(C.c_char_p), _P, C.c_size_t]),
+    "andi_hip_fit": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P, _P, _P, _P]),
+    "andi_hip_relength": (C.c_int, [_P, C.c_size_t, _P, _P]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
                                             C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
@@ -1238,6 +1240,49 @@ def newick_rooted(joins, names, edge, distal, labels=None, truncate_names=False)
             break
         cap = need + 1
     return out.value.decode()
+
+
+# andi_hip_fit_result: how well a tree explains its matrix -- the residual sums of squares under the refit lengths and
+# under the records' own, the total sum of squares, the trees' lengths and negative branches, the worst-fitted pair
+FIT = np.dtype([("rss", "<f8"), ("rss_joined", "<f8"), ("tss", "<f8"), ("length", "<f8"), ("length_joined", "<f8"),
+                ("worst", "<f8"), ("pairs", "<u8"), ("negative", "<u4"), ("negative_joined", "<u4"), ("worst_b", "<i4"),
+                ("worst_c", "<i4")])
+FIT_METHODS = ("ols",)
+
+
+def fit(ctx: Context, J, D, method="ols", per=False):
+    """The branch lengths of the tree J (n - 2 records of nj, tree or parse_newick) refit to the (n, n) matrix D by least
+    squares on the device (andi_hip_fit): (len, record) -- the (2n - 3,) float64 lengths by edge and a record of dtype
+    FIT (R^2 is 1 - rss / tss) --, and with per=True also the (n,) float64 arrays leaf_ss and leaf_ss_joined, every
+    genome's share of rss and of rss_joined.  relength puts the lengths into the records."""
+    if str(method).lower() not in FIT_METHODS:
+        raise ValueError("method must be one of %s" % sorted(FIT_METHODS))
+    m = FIT_METHODS.index(str(method).lower())
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.shape != (n, n):
+        raise ValueError("D must be (n, n) for the n - 2 records of J")
+    length = np.zeros(2 * n - 3, np.float64)
+    out = np.zeros(1, FIT)
+    rows = [np.zeros(n, np.float64) for _ in range(2)] if per else [None] * 2
+    ctx._check(load().andi_hip_fit(ctx._h, J.ctypes.data, n, D.ctypes.data, m, length.ctypes.data, out.ctypes.data,
+                                   *[r.ctypes.data if per else None for r in rows]), "fit")
+    return (length, out[0], *rows) if per else (length, out[0])
+
+
+def relength(J, length):
+    """The records J with their branch lengths replaced by length[child], the (2n - 3,) lengths by edge
+    (andi_hip_relength); raises ValueError where the library refuses (malformed records)."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    length = np.ascontiguousarray(length, dtype=np.float64)
+    if length.shape != (2 * n - 3,):
+        raise ValueError("length must hold 2n - 3 values")
+    out = np.zeros(len(J), NJ_JOIN)
+    if load().andi_hip_relength(J.ctypes.data, n, length.ctypes.data, out.ctypes.data):
+        raise ValueError("andi_hip_relength: the records are not those of andi_hip_nj")
+    return out
 
 
 def nj_support(ctx: Context, J, reps, skip=None):

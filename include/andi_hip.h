@@ -30,7 +30,8 @@
  * (neighbor-joining or BIONJ): andi_hip_tree, andi_hip_tree_batch and andi_hip_bootstrap_tree (additions only); and missing
  * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only);
  * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only); and the root of
- * a tree without an outgroup: andi_hip_root and andi_hip_format_newick_rooted (additions only).
+ * a tree without an outgroup: andi_hip_root and andi_hip_format_newick_rooted (additions only); and a tree's branch
+ * lengths refit to its matrix by least squares: andi_hip_fit and andi_hip_relength (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -863,6 +864,67 @@ int andi_hip_root(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, int
  * distal that is not finite give 0 and an empty string too.  No GPU is touched. */
 size_t andi_hip_format_newick_rooted(const andi_hip_nj_join *J, size_t n, const char *const *names, int truncate_names,
 									 int32_t edge, double distal, const char *const *labels, char *out, size_t cap);
+
+/* The branch lengths of a fixed tree refit to a distance matrix by ordinary least squares (as FastME's OLS lengths and the
+ * unconstrained form of phangorn's nnls.tree; the closed form per edge of Rzhetsky and Nei 1993 and of Desper and Gascuel
+ * 2002, eq. 3), and how well the tree explains the matrix under the refit lengths and under the records' own.  The
+ * lengths the joining gives come from reduced matrices; these are the best fit to the distances themselves, what
+ * least-squares placement (andi_hip_place) and MAD (andi_hip_root) read path lengths as.
+ * tree: the n - 2 records of andi_hip_nj / andi_hip_tree / andi_hip_parse_newick for n leaves (validated on the host by
+ * andi_hip_place's rule); D: the n x n host matrix -- as in andi_hip_nj only the upper triangle is read, the lower is
+ * mirrored and the diagonal ignored; method: ANDI_FIT_OLS; len: 2n - 3 doubles, the refit length of every edge; out: one
+ * record; leaf_ss, leaf_ss_joined: NULL, or n doubles each.  3 <= n <= 65535.  Bad arguments (a NULL ctx, tree, D, len or
+ * out, n out of range, a method other than 0), a branch length of the records that is not finite, records that are not
+ * andi_hip_nj's and a D[i][j], i < j, that is not finite (the message names the first in row-major order, as
+ * andi_hip_nj's does) fail with 1 before any HIP call, through the context's error, and write nothing.  Synchronous, on
+ * the context's stream.  andi_hip_relength puts the lengths into the records.
+ *
+ * The result is bit-exact to this contract (tests/fit_model.py restates it); every operation is an IEEE double operation
+ * rounded on its own (no a*b+c contracted into an FMA), every sum sequential from +0.0 in the order given:
+ *  - the tree, the edges, parent(v), len(v), below(v, i) and the path lengths h(v, i): andi_hip_place's.  Edge v,
+ *    0 <= v < 2n - 3, joins v to parent(v); C = 2n - 3 is the centre;
+ *  - the classes of the leaves around edge v, with q = parent(v): class 0 is the leaves below the first child of v's pair
+ *    record, class 1 those below its second child; for a leaf edge (v < n) class 0 is {v} and class 1 is empty.  If
+ *    q != C, class 2 is the leaves below the other child of q (v's sibling) and class 3 every leaf not below q; if q == C,
+ *    classes 2 and 3 are the leaves below the other two children of the final record, in record order;
+ *  - the sums: for fixed (v, b) and each class k != class(v, b), s_k(v, b) is the sum of D[b][c] over c > b ascending with
+ *    class(v, c) == k.  For x < y, S_xy(v) is the sum over b ascending of s_y(v, b) where class(v, b) == x and of
+ *    s_x(v, b) where class(v, b) == y; any other b adds nothing;
+ *  - the means: n_k the sizes of the classes, m_xy = S_xy / (double)(n_x * n_y), the product in 64-bit integers;
+ *  - the lengths: of a leaf edge len = ((m_02 + m_03) - m_23) * 0.5; of an inner edge, with
+ *    g = (double)(n_1*n_2 + n_0*n_3) / (double)((n_0 + n_1)*(n_2 + n_3)),
+ *    len = ((g*(m_02 + m_13) + (1.0 - g)*(m_12 + m_03)) - (m_01 + m_23)) * 0.5.  Negative results are kept; sums of finite
+ *    input that overflow may give +-inf or NaN, which are returned as they are;
+ *  - the fit, once under the refit lengths (rss, leaf_ss, length, negative, worst) and once under the records' own
+ *    (rss_joined, leaf_ss_joined, length_joined, negative_joined): the path lengths h by andi_hip_place's rule under that
+ *    length vector; for b < c, p(b, c) = h(parent(b), c) + len(b) (andi_hip_root's chain; every pair counts) and
+ *    r = D[b][c] - p.  rss is the sum over b ascending of the sum over c > b ascending of r*r; leaf_ss[i] the sum over
+ *    j != i ascending of r*r of the pair {i, j}; length the sum of len(v) over v ascending; negative the number of v with
+ *    len(v) < 0;
+ *  - tss: mean = (the sum over b ascending of the sum over c > b ascending of D[b][c]) / (double)pairs, pairs =
+ *    n(n - 1)/2; tss is the sum of (D[b][c] - mean)^2 in the same nested order.  R^2 = 1 - rss / tss is left to the caller;
+ *  - worst_b < worst_c: the pair of the greatest |r| under the refit lengths, ties to the first in (b, c) order, a NaN
+ *    below every number; worst is its r.  If every residual is a NaN: -1, -1 and worst a NaN.
+ * On the device: the matrix and the residuals (8 n^2 bytes each), andi_hip_place's table of the (2n - 3) x n path lengths
+ * (when it does not fit the call fails through the context's error, which names the bytes), and the leaves b in groups
+ * that fit 1 GiB (32 (2n - 3) bytes a leaf); the results do not depend on the grouping.  Work: (2n - 3) * n(n - 1)/2 pair
+ * visits, once, without a division. */
+enum { ANDI_FIT_OLS = 0 };
+typedef struct {
+	double rss, rss_joined;       /* residual sums of squares: refit lengths, the records' own lengths */
+	double tss;                   /* sum of (D - mean)^2 */
+	double length, length_joined; /* sum of all branch lengths */
+	double worst;                 /* the residual D - p of the pair below */
+	uint64_t pairs;               /* n(n-1)/2 */
+	uint32_t negative, negative_joined; /* edges with len < 0 */
+	int32_t worst_b, worst_c;     /* pair of the greatest |residual| under the refit lengths */
+} andi_hip_fit_result; /* 72 bytes */
+int andi_hip_fit(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, int method, double *len /* 2n-3 */,
+				 andi_hip_fit_result *out, double *leaf_ss /* NULL or n */, double *leaf_ss_joined /* NULL or n */);
+/* The records J with their lengths replaced: la, lb (and lc of the final record) of every record become len[child], len
+ * the 2n - 3 lengths by edge (andi_hip_fit's); everything else is copied, and out may be J itself.  Returns 1, and writes
+ * nothing, on a NULL pointer, n < 3 or records that are not andi_hip_nj's (andi_hip_place's rule).  No GPU is touched. */
+int andi_hip_relength(const andi_hip_nj_join *J, size_t n, const double *len, andi_hip_nj_join *out);
 
 /* ------------------------------------------------------------------ */
 /* The k-mer sketch screen: which references are worth an exact run    */
