@@ -437,6 +437,17 @@ static void usage(int status) {
 		"                       residual sum of squares and R^2 under least-squares and under the joined lengths, the trees'\n"
 		"                       lengths and negative branches, the worst-fitted pair; then every genome's share of the two\n"
 		"                       sums of squares.  Works without --tree; after --complete, if given\n"
+		"      --refine=METHOD  Refine every joined tree of --tree, --support, --consensus, --transfer and --rogues against its own\n"
+		"                       matrix right after the join: 'none' (the default) or 'bnni', balanced nearest-neighbor\n"
+		"                       interchanges on the GPU until none shortens the tree (as FastME's BNNI); the tree then carries\n"
+		"                       its balanced (BME) lengths, which --lengths, --root and --fit start from; not together with\n"
+		"                       --trees-only\n"
+		"      --refine-tol=X   With --refine: an interchange is made only if it shortens the tree by more than X, in the units\n"
+		"                       of the printed matrix; default: 1e-9\n"
+		"      --refine-report=FILE  With --refine: write the refinement of the first matrix's tree to FILE, tab-separated: the\n"
+		"                       method, the interchanges made, whether the search converged, the tree's length before and\n"
+		"                       after, the joined tree's inner branches that the refined tree lacks; then every interchange:\n"
+		"                       its gain and the first genome of each of the two subtrees it swapped\n"
 		"      --linkage=METHOD Cluster with 'single', 'complete' or 'average' linkage; default: average (UPGMA)\n"
 		"      --dendrogram=FILE  Write the linkage tree of each printed matrix to FILE (Newick, rooted, one line per\n"
 		"                       matrix); a pair without a distance counts as farther apart than any other\n"
@@ -680,6 +691,89 @@ static int join_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, 
 								  : andi_hip_bootstrap_tree(ctx, M, n, model, method, seed, first, count, J, bad, NULL);
 }
 
+/* --refine=bnni: every joined tree is refined against the matrix it was joined from (andi_hip_refine) right after the join,
+ * so every file of trees sees the refined records, with their balanced lengths.  --refine-report: the point estimate's. */
+typedef struct {
+	int on, reported;
+	double tol;
+	const char *tol_arg, *report_path;
+	FILE *rf;
+} refine_opts;
+static refine_opts refopt = {.tol = 1e-9};
+
+static size_t set_words; /* (for cmp_sets) */
+static int cmp_sets(const void *a, const void *b) {
+	const uint64_t *x = a, *y = b;
+	for (size_t w = 0; w < set_words; w++)
+		if (x[w] != y[w]) return x[w] < y[w] ? -1 : 1;
+	return 0;
+}
+
+/* the leaf sets of the n - 3 pair records, each on its side without leaf 0, sorted */
+static uint64_t *sorted_sets(const andi_hip_nj_join *J, size_t n) {
+	const size_t W = (n + 63) / 64, nsets = n - 3;
+	uint64_t *sets = xmalloc((nsets ? nsets : 1) * W * sizeof *sets);
+	memset(sets, 0, (nsets ? nsets : 1) * W * sizeof *sets);
+	for (size_t s = 0; s < nsets; s++) {
+		const int32_t ch[2] = {J[s].a, J[s].b};
+		for (int k = 0; k < 2; k++) {
+			if ((size_t)ch[k] < n) sets[s * W + (size_t)ch[k] / 64] |= (uint64_t)1 << (ch[k] % 64);
+			else
+				for (size_t w = 0; w < W; w++) sets[s * W + w] |= sets[((size_t)ch[k] - n) * W + w];
+		}
+	}
+	for (size_t s = 0; s < nsets; s++) {
+		if (!(sets[s * W] & 1)) continue;
+		for (size_t w = 0; w < W; w++) sets[s * W + w] = ~sets[s * W + w];
+		if (n % 64) sets[s * W + W - 1] &= ((uint64_t)1 << (n % 64)) - 1;
+	}
+	set_words = W;
+	qsort(sets, nsets, W * sizeof *sets, cmp_sets);
+	return sets;
+}
+
+/* the inner branches of the tree `before` that the tree `after` lacks */
+static size_t changed_branches(const andi_hip_nj_join *before, const andi_hip_nj_join *after, size_t n) {
+	const size_t W = (n + 63) / 64, nsets = n - 3;
+	uint64_t *x = sorted_sets(before, n), *y = sorted_sets(after, n);
+	size_t changed = 0;
+	for (size_t s = 0; s < nsets; s++) changed += !bsearch(x + s * W, y, nsets, W * sizeof *y, cmp_sets);
+	free(x), free(y);
+	return changed;
+}
+
+/* The records J of the K-th matrix D (1 = the point estimate) refined in place.  A tree that cannot be refined stays as it
+ * was joined, with a soft warning; one whose search ends at the cap of 10 n interchanges is kept as it stands, with one. */
+static void refine_joined(andi_hip_ctx *ctx, andi_hip_nj_join *J, size_t n, const double *D, unsigned long k, const char **names,
+						  int truncate) {
+	if (!refopt.on || n < 3) return;
+	const int report = k == 1 && refopt.rf && !refopt.reported;
+	const size_t cap = 10 * n;
+	andi_hip_nj_join *out = xmalloc((n - 2) * sizeof *out);
+	andi_hip_refine_move *log = report ? xmalloc(cap * sizeof *log) : NULL;
+	andi_hip_refine_result r;
+	if (andi_hip_refine(ctx, J, n, D, ANDI_REFINE_BNNI, refopt.tol, cap, out, &r, log)) {
+		soft_warnx("The tree of matrix %lu is written unrefined: %s", k, andi_hip_last_error(ctx));
+	} else {
+		if (!r.converged)
+			soft_warnx("The tree of matrix %lu is written as it stood after %zu interchanges: the refinement (--refine) did not converge.", k, cap);
+		if (report) {
+			FILE *f = refopt.rf;
+			const int w = truncate ? 10 : -1; /* (as the matrix prints a name) */
+			refopt.reported = 1;
+			fputs("#method\tmoves\tconverged\tlength_before\tlength_after\tchanged\n", f);
+			fprintf(f, "bnni\t%llu\t%d\t%.8g\t%.8g\t%zu\n", (unsigned long long)r.moves, (int)r.converged, r.length_before, r.length_after,
+					changed_branches(J, out, n));
+			fputs("#move\tgain\tfirst\tsecond\n", f);
+			for (size_t m = 0; m < r.moves; m++)
+				fprintf(f, "%zu\t%.8g\t%.*s\t%.*s\n", m + 1, log[m].gain, w, names[log[m].first], w, names[log[m].second]);
+			if (ferror(f)) err(1, "%s", refopt.report_path);
+		}
+		memcpy(J, out, (n - 2) * sizeof *out);
+	}
+	free(out), free(log);
+}
+
 /* --tree: the tree (neighbor-joining, or --tree-method's) of the K-th printed matrix (1 = the point estimate) as one Newick
  * line, from the averaged distances whatever -vv asks the matrix to print */
 typedef struct {
@@ -813,7 +907,12 @@ static void fit_report(tree_out *t, const andi_hip_model *M, const genome *g, co
 		soft_warnx("No fit report: a tree of two sequences has one branch and nothing to fit.");
 		ok = 0;
 	}
-	if (ok && (join_one(t->ctx, D, n, t->method, J) || andi_hip_fit(t->ctx, J, n, D, ANDI_FIT_OLS, len, &r, ss, ss + n))) {
+	if (ok && join_one(t->ctx, D, n, t->method, J)) {
+		soft_warnx("No fit report: %s", andi_hip_last_error(t->ctx));
+		ok = 0;
+	}
+	if (ok) refine_joined(t->ctx, J, n, D, 1, names, truncate);
+	if (ok && andi_hip_fit(t->ctx, J, n, D, ANDI_FIT_OLS, len, &r, ss, ss + n)) {
 		soft_warnx("No fit report: %s", andi_hip_last_error(t->ctx));
 		ok = 0;
 	}
@@ -869,6 +968,7 @@ static void write_tree(tree_out *t, const andi_hip_model *M, const genome *g, co
 		free(D), free(J);
 		return;
 	}
+	refine_joined(t->ctx, J, n, D, (unsigned long)k, names, truncate);
 	put_newick(t->o, &(newick_src){.J = J, .ctx = t->ctx, .point = k == 1, .D = D}, names, n, truncate);
 	free(D), free(J);
 }
@@ -960,6 +1060,7 @@ static void support_begin(support_state *s, const tree_file *o, const boot_run *
 		if (rf) soft_warnx("No rogue table: %s", andi_hip_last_error(r->ctx));
 		s->point_ok = s->trans_ok = s->rogue_ok = 0;
 	}
+	if (s->point_ok || s->trans_ok || s->rogue_ok) refine_joined(r->ctx, s->J, n, D, 1, r->names, r->truncate);
 	if (lengths_ols && !trees_only && (s->point_ok || s->trans_ok)) { /* (the chunks' matrices take D's place) */
 		if (!(s->Dpoint = malloc(n * n * sizeof *D))) err(errno, "Could not allocate enough memory for the support values.");
 		memcpy(s->Dpoint, D, n * n * sizeof *D);
@@ -1003,7 +1104,8 @@ static void support_chunk(support_state *s, unsigned long start, size_t count, c
 			if (skip[k])
 				soft_warnx("No tree for matrix %lu: the distance of '%s' and '%s'%s", first + (unsigned long)k + 2,
 						   g[s->bad[k] / (int64_t)n].name, g[s->bad[k] % (int64_t)n].name, NOT_FINITE);
-			else if (s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec, .ctx = ctx, .D = s->r.trees_only ? NULL : s->D + k * n * n}, s->r.names, n, s->r.truncate);
+			else if (!s->r.trees_only) refine_joined(ctx, R + k * nrec, n, s->D + k * n * n, first + (unsigned long)k + 2, s->r.names, s->r.truncate);
+			if (!skip[k] && s->o[OUT_TREE].f) put_newick(&s->o[OUT_TREE], &(newick_src){.J = R + k * nrec, .ctx = ctx, .D = s->r.trees_only ? NULL : s->D + k * n * n}, s->r.names, n, s->r.truncate);
 			s->counted += !skip[k];
 		}
 		/* (whatever fails below, the replicates' lines of --tree are still written) */
@@ -1456,6 +1558,9 @@ int main(int argc, char *argv[]) {
 												 {"root-report", required_argument, NULL, 0},
 												 {"lengths", required_argument, NULL, 0},
 												 {"fit", required_argument, NULL, 0},
+												 {"refine", required_argument, NULL, 0},
+												 {"refine-tol", required_argument, NULL, 0},
+												 {"refine-report", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
 												 {"dendrogram", required_argument, NULL, 0},
 												 {"clusters", required_argument, NULL, 0},
@@ -1520,6 +1625,13 @@ int main(int argc, char *argv[]) {
 					else errx(1, "Expected one of 'joined' or 'ols' for --lengths, but '%s' was given.", optarg);
 				}
 				if (!strcmp(o, "fit")) fitopt.path = optarg;
+				if (!strcmp(o, "refine")) {
+					if (!strcasecmp(optarg, "none")) refopt.on = 0;
+					else if (!strcasecmp(optarg, "bnni")) refopt.on = 1;
+					else errx(1, "Expected one of 'none' or 'bnni' for --refine, but '%s' was given.", optarg);
+				}
+				if (!strcmp(o, "refine-tol")) refopt.tol_arg = optarg;
+				if (!strcmp(o, "refine-report")) refopt.report_path = optarg;
 				if (!strcmp(o, "rogues")) rogues.path = optarg;
 				if (!strcmp(o, "rogue-cutoff")) rogues.cutoff_arg = optarg;
 				if (!strcmp(o, "dendrogram")) clus.dendro_path = optarg;
@@ -1660,6 +1772,16 @@ int main(int argc, char *argv[]) {
 	if (lengths_ols && trees_only)
 		errx(1, "Branch lengths (--lengths=ols) are not refit together with --trees-only: the bootstrap matrices stay on the GPU.");
 	if (fitopt.path && rect) errx(1, "A fit report (--fit) is" WITH_REFERENCE);
+	if (refopt.on && trees_only)
+		errx(1, "Trees (--refine=bnni) are not refined together with --trees-only: the bootstrap matrices stay on the GPU.");
+	if (refopt.report_path && !refopt.on) errx(1, "A refinement report (--refine-report) needs --refine=bnni.");
+	if (refopt.tol_arg) {
+		errno = 0;
+		char *end;
+		refopt.tol = strtod(refopt.tol_arg, &end);
+		if (errno || end == refopt.tol_arg || *end || !(refopt.tol >= 0.0))
+			errx(1, "Expected a number that is not negative for --refine-tol, but '%s' was given.", refopt.tol_arg);
+	}
 	if (clus.clusters_path && !clus.have_threshold) errx(1, "Clusters (--clusters) need a threshold: give --threshold=T.");
 	if (clus.have_threshold && !clus.clusters_path) errx(1, "A threshold (--threshold) needs somewhere to go: give --clusters=FILE.");
 	if (place.path && !rect) errx(1, "Placement (--place) needs references to place on: give --reference=FILE or --reference-list=FILE.");
@@ -1687,6 +1809,7 @@ int main(int argc, char *argv[]) {
 	if (cmpl.report_path && !(cmpl.rf = fopen(cmpl.report_path, "w"))) err(1, "%s", cmpl.report_path);
 	if (dlt.path && !(dlt.f = fopen(dlt.path, "w"))) err(1, "%s", dlt.path);
 	if (fitopt.path && !(fitopt.f = fopen(fitopt.path, "w"))) err(1, "%s", fitopt.path);
+	if (refopt.report_path && !(refopt.rf = fopen(refopt.report_path, "w"))) err(1, "%s", refopt.report_path);
 	if (rootopt.report_path) {
 		if (!(rootopt.rf = fopen(rootopt.report_path, "w"))) err(1, "%s", rootopt.report_path);
 		fputs("#method\tedge\tdistal\tlength\tscore\tambiguity\tpairs\n", rootopt.rf);
@@ -1808,6 +1931,7 @@ int main(int argc, char *argv[]) {
 	if (cmpl.rf && fclose(cmpl.rf)) err(1, "%s", cmpl.report_path);
 	if (dlt.f && fclose(dlt.f)) err(1, "%s", dlt.path);
 	if (fitopt.f && fclose(fitopt.f)) err(1, "%s", fitopt.path);
+	if (refopt.rf && fclose(refopt.rf)) err(1, "%s", refopt.report_path);
 	if (rootopt.rf && fclose(rootopt.rf)) err(1, "%s", rootopt.report_path);
 	free(M);
 	free(in);

@@ -141,6 +141,7 @@ SYMBOLS = {
                                                    C.POINTER(C.c_char_p), _P, C.c_size_t]),
     "andi_hip_fit": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P, _P, _P, _P]),
     "andi_hip_relength": (C.c_int, [_P, C.c_size_t, _P, _P]),
+    "andi_hip_refine": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_double, C.c_size_t, _P, _P, _P]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
                                             C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
@@ -1283,6 +1284,37 @@ def relength(J, length):
     if load().andi_hip_relength(J.ctypes.data, n, length.ctypes.data, out.ctypes.data):
         raise ValueError("andi_hip_relength: the records are not those of andi_hip_nj")
     return out
+
+
+# andi_hip_refine_result and andi_hip_refine_move: the sums of the balanced lengths before and after the search, the moves
+# made and whether it converged; a move's gain and the least leaves of the two subtrees it swapped
+REFINE = np.dtype([("length_before", "<f8"), ("length_after", "<f8"), ("moves", "<u8"), ("converged", "<i4"), ("pad", "<i4")])
+REFINE_MOVE = np.dtype([("gain", "<f8"), ("first", "<i4"), ("second", "<i4")])
+REFINE_METHODS = ("bnni",)
+
+
+def refine(ctx: Context, J, D, method="bnni", tol=0.0, max_moves=None, log=False):
+    """The tree J (n - 2 records of nj, tree or parse_newick) refined against the (n, n) matrix D by balanced
+    nearest-neighbor interchanges on the device (andi_hip_refine): (records, result) -- the refined tree's records with
+    its balanced lengths and a record of dtype REFINE --, and with log=True also the moves made, an array of dtype
+    REFINE_MOVE.  A move is made only if it shortens the tree by more than tol; max_moves=None allows 10 n."""
+    if str(method).lower() not in REFINE_METHODS:
+        raise ValueError("method must be one of %s" % sorted(REFINE_METHODS))
+    m = REFINE_METHODS.index(str(method).lower())
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.shape != (n, n):
+        raise ValueError("D must be (n, n) for the n - 2 records of J")
+    cap = 10 * n if max_moves is None else int(max_moves)
+    if cap < 0:
+        raise ValueError("max_moves must not be negative")
+    out = np.zeros(len(J), NJ_JOIN)
+    res = np.zeros(1, REFINE)
+    moves = np.zeros(max(cap, 1), REFINE_MOVE) if log else None
+    ctx._check(load().andi_hip_refine(ctx._h, J.ctypes.data, n, D.ctypes.data, m, float(tol), cap, out.ctypes.data,
+                                      res.ctypes.data, moves.ctypes.data if log else None), "refine")
+    return (out, res[0], moves[:int(res[0]["moves"])].copy()) if log else (out, res[0])
 
 
 def nj_support(ctx: Context, J, reps, skip=None):

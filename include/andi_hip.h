@@ -31,7 +31,8 @@
  * distances estimated from quartets, in front of those trees: andi_hip_complete and andi_hip_complete_batch (additions only);
  * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only); and the root of
  * a tree without an outgroup: andi_hip_root and andi_hip_format_newick_rooted (additions only); and a tree's branch
- * lengths refit to its matrix by least squares: andi_hip_fit and andi_hip_relength (additions only).
+ * lengths refit to its matrix by least squares: andi_hip_fit and andi_hip_relength (additions only); and a tree refined
+ * by balanced nearest-neighbor interchanges, with its balanced lengths: andi_hip_refine (an addition only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -925,6 +926,74 @@ int andi_hip_fit(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, cons
  * the 2n - 3 lengths by edge (andi_hip_fit's); everything else is copied, and out may be J itself.  Returns 1, and writes
  * nothing, on a NULL pointer, n < 3 or records that are not andi_hip_nj's (andi_hip_place's rule).  No GPU is touched. */
 int andi_hip_relength(const andi_hip_nj_join *J, size_t n, const double *len, andi_hip_nj_join *out);
+
+/* A tree refined by balanced nearest-neighbor interchanges (BNNI: FastME's topology search, Desper and Gascuel 2002), and
+ * its balanced (BME) branch lengths.  Neighbor-joining is one greedy pass over the balanced minimum evolution criterion and
+ * never revisits a join; BNNI swaps subtrees across inner branches until no swap shortens the tree under Pauplin's length,
+ * the sum over i < j of 2^(1 - hops(i, j)) D[i][j], and is consistent from any start tree (Bordewich et al. 2009).
+ * tree: the n - 2 records of andi_hip_nj / andi_hip_tree / andi_hip_parse_newick for n leaves (validated on the host by
+ * andi_hip_place's rule; their lengths are not read); D: as in andi_hip_fit -- the upper triangle is read and mirrored, the
+ * diagonal ignored; method: ANDI_REFINE_BNNI; tol >= 0: a move is made only if it shortens the tree by more than tol;
+ * max_moves: the moves made at most; out: n - 2 records, the refined tree with its balanced lengths (out may be tree
+ * itself); res: one record; log: NULL, or max_moves entries, of which the first res->moves are written.  3 <= n <= 65535.
+ * Bad arguments (a NULL ctx, tree, D, out or res, n out of range, a method other than 0, a tol that is negative or a NaN),
+ * records that are not andi_hip_nj's and a D[i][j], i < j, that is not finite (the message names the first in row-major
+ * order) fail with 1 before any HIP call, through the context's error, and write nothing.  Synchronous, on the context's
+ * stream; the host looks at one record of 32 bytes a round.  The records pass andi_hip_place's validation: the formatters,
+ * andi_hip_root, andi_hip_fit, andi_hip_nj_support, _transfer, _splits and andi_hip_place take them unchanged.
+ *
+ * The result is bit-exact to this contract (tests/bme_model.py restates it); every operation is an IEEE double operation
+ * rounded on its own (no a*b+c contracted into an FMA):
+ *  - the tree is rooted at the centre C = 2n - 3, the final record's node; node n + s is pair record s's; the children of
+ *    a node keep slots, at first the record's order (a, b, and c for C).  Node ids stay fixed during the search: a move
+ *    only re-hangs subtrees.  lev(x) is the number of edges from C to x;
+ *  - A(v, c), the balanced average distance between leaf c and the subtree on the far side of edge v (v to parent(v)) from
+ *    c, for every non-centre node v and every leaf c -- andi_hip_place's table shape, (2n - 3) x n.  c not below v: for a
+ *    leaf v, A(v, c) = D[v][c]; for an inner v with children a and b, A(v, c) = (A(a, c) + A(b, c)) * 0.5.  c below v (a
+ *    leaf is below itself): with q = parent(v) != C and s the sibling of v, A(v, c) = (A(s, c) + A(q, c)) * 0.5; with
+ *    parent(v) = C, A(v, c) = (A(s1, c) + A(s2, c)) * 0.5 over the other two children of C;
+ *  - S(x, r) = the sum of w(x, c) * A(r, c) over the leaves c below x, w(x, c) = 2^-(lev(c) - lev(x)), exact, and 0 once
+ *    the exponent passes 1022 (w is never subnormal).  The sum is taken as 64 partial sums: p_l takes the c with
+ *    c mod 64 = l in ascending order, p_l = p_l + w * A starting from +0.0; the total is the sequential sum of p_0 ... p_63
+ *    in ascending l, from +0.0 (what a wavefront that reads runs of 512 bytes of a table row produces);
+ *  - around an inner non-centre edge v with children a and b in slot order and q = parent(v): if q != C, s is v's sibling
+ *    and sums "against u" read row q; if q = C, s and u are C's other two children in slot order and sums against u read
+ *    row u.  The six averages: d_ab = S(a, b), d_as = S(a, s), d_bs = S(b, s), d_au = S(a, row of u), d_bu = S(b, row of u),
+ *    d_su = S(s, row of u);
+ *  - the gains: alternative 0 swaps b with s, g0 = ((d_ab + d_su) - (d_as + d_bu)) * 0.25; alternative 1 swaps a with s,
+ *    g1 = ((d_ab + d_su) - (d_bs + d_au)) * 0.25;
+ *  - a round takes the greatest gain over all (v, alternative), ties to the smaller v, then to alternative 0, a NaN below
+ *    every number.  If it is > tol and fewer than max_moves moves were made, the move is made -- the incoming subtree s
+ *    takes the outgoing one's slot in v, the outgoing one takes s's slot in q -- and the next round evaluates the new tree
+ *    from nothing.  If it is not > tol the search stops with converged = 1; if it is, but max_moves moves were made, with
+ *    converged = 0.  A log entry is the move's gain and the least leaves of the outgoing (first) and the incoming (second)
+ *    subtree, which name them whatever the numbering;
+ *  - the balanced lengths, from the same sums, on the first round's tree (length_before) and on the final tree (the
+ *    output, length_after): of a leaf edge v, ((S(v, s) + S(v, row of u)) - d_su) * 0.5 with s and u as for an inner edge;
+ *    of an inner edge, ((d_as + d_au) + (d_bs + d_bu)) * 0.25 - (d_ab + d_su) * 0.5.  Negative lengths are kept.  length_*
+ *    is the sequential sum of the lengths over v ascending, from +0.0; it is Pauplin's length of the tree up to rounding.
+ *    n = 3 has no inner edge: 0 moves, and the three balanced lengths;
+ *  - the output numbering (on the host, O(n)): the centre stays the final record; children are visited in order of their
+ *    least leaf; inner nodes get ids n, n + 1, ... in post-order; a pair record has the smaller id as a, the final record
+ *    x < y < z; the lengths are the balanced ones of the final tree.
+ * tol should lie above the gains' rounding noise, about n * 2^-53 times the largest distance: with a smaller one a search
+ * may go on making moves that mean nothing until max_moves ends it.
+ * On the device: the table (8 (2n - 3) n bytes; when it does not fit the call fails through the context's error, which
+ * names the bytes), the matrix (8 n^2), the leaf sets.  Work a round: the table once, read about twice. */
+enum { ANDI_REFINE_BNNI = 0 };
+typedef struct {
+	double length_before, length_after; /* the sum of the balanced lengths: of the tree given, of the refined one */
+	uint64_t moves;                     /* interchanges made */
+	int32_t converged;                  /* 1: no interchange gains more than tol; 0: max_moves ended the search */
+	int32_t pad;
+} andi_hip_refine_result; /* 32 bytes */
+typedef struct {
+	double gain;           /* what the move shortened the tree by */
+	int32_t first, second; /* the least leaf of the subtree that left the edge's lower node, of the one that took its place */
+} andi_hip_refine_move; /* 16 bytes */
+int andi_hip_refine(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, int method, double tol,
+					size_t max_moves, andi_hip_nj_join *out, andi_hip_refine_result *res,
+					andi_hip_refine_move *log /* NULL or max_moves */);
 
 /* ------------------------------------------------------------------ */
 /* The k-mer sketch screen: which references are worth an exact run    */
