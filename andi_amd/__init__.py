@@ -15,6 +15,6 @@ from .lib import (AndiHipError, Context, bootstrap, bootstrap_nj, bootstrap_rang
                   PLACEMENT, distances_rect, jplace, parse_newick, place,
                   ROOT, newick_rooted, root,
                   FIT, fit, relength,
-                  REFINE, REFINE_MOVE, refine,
+                  REFINE, REFINE_MOVE, refine, SPR_MOVE, refine_spr,
                   Sketches, screen, screen_select, sketch, sketch_shared,
                   scan_rows, subject_prepare, suffix_array)

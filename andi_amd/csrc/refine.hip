@@ -86,12 +86,17 @@ __device__ inline int32_t row_of(const int32_t *par, const int32_t *kid, uint32_
 
 // One wavefront.  order: the E = 2n - 3 non-centre nodes breadth-first; lev: E + 1 entries; lstart: E + 2 entries --
 // lstart[0] the deepest level, lstart[l] where level l >= 1 begins in order (a level is one run of it), E behind the last.
-__global__ __launch_bounds__(64) void k_order(const int32_t *__restrict__ kid, uint32_t n, int32_t *order, int32_t *lev,
-											  int32_t *lstart) {
+// SLOTS = false: the children are kid's.  SLOTS = true (the SPR search): src holds three neighbour slots per inner node,
+// src[3 (q - n) + s]; the children of a node are its neighbours but its parent, in slot order, and par and kid are written.
+// Returns the deepest level.
+template <bool SLOTS>
+__device__ inline int32_t order_from_centre(const int32_t *__restrict__ src, uint32_t n, int32_t *par, int32_t *kid, int32_t *order,
+											 int32_t *lev, int32_t *lstart) {
 	const uint32_t E = 2 * n - 3, C = E, lane = threadIdx.x;
 	if (lane < 3) {
-		const int32_t x = kid[2 * (size_t)(C - n) + lane];
+		const int32_t x = src[(SLOTS ? 3 : 2) * (size_t)(C - n) + lane];
 		order[lane] = x, lev[x] = 1;
+		if (SLOTS) par[x] = (int32_t)C, kid[2 * (size_t)(C - n) + lane] = x;
 	}
 	if (lane == 0) lev[C] = 0;
 	__syncthreads();
@@ -107,18 +112,31 @@ __global__ __launch_bounds__(64) void k_order(const int32_t *__restrict__ kid, u
 		}
 		if (inner) {
 			const uint32_t at = tail + 2 * (uint32_t)__popcll(m & ((1ull << lane) - 1));
-			const int32_t a = kid[2 * (size_t)(x - (int32_t)n)], b = kid[2 * (size_t)(x - (int32_t)n) + 1], l = lev[x] + 1;
-			if (at + 1 < E) order[at] = a, order[at + 1] = b, lev[a] = l, lev[b] = l; // (a tree's nodes are queued once each: it fits)
+			int32_t a, b;
+			if (SLOTS) {
+				const int32_t *s = src + 3 * (size_t)(x - (int32_t)n);
+				const int32_t p = par[x];
+				a = s[0] == p ? s[1] : s[0], b = s[2] == p ? s[1] : s[2];
+			} else a = src[2 * (size_t)(x - (int32_t)n)], b = src[2 * (size_t)(x - (int32_t)n) + 1];
+			const int32_t l = lev[x] + 1;
+			if (at + 1 < E) { // (a tree's nodes are queued once each: it fits)
+				order[at] = a, order[at + 1] = b, lev[a] = l, lev[b] = l;
+				if (SLOTS) par[a] = x, par[b] = x, kid[2 * (size_t)(x - (int32_t)n)] = a, kid[2 * (size_t)(x - (int32_t)n) + 1] = b;
+			}
 		}
 		head += tail - head < 64 ? tail - head : 64;
 		tail += 2 * (uint32_t)__popcll(m);
 		if (tail > E) tail = E;
 		__syncthreads();
 	}
-	if (lane == 0) {
-		const int32_t deepest = lev[order[E - 1]];
-		lstart[0] = deepest, lstart[deepest + 1] = (int32_t)E;
-	}
+	const int32_t deepest = lev[order[E - 1]];
+	if (lane == 0) lstart[0] = deepest, lstart[deepest + 1] = (int32_t)E;
+	return deepest;
+}
+
+__global__ __launch_bounds__(64) void k_order(const int32_t *__restrict__ kid, uint32_t n, int32_t *order, int32_t *lev,
+											  int32_t *lstart) {
+	order_from_centre<false>(kid, n, nullptr, nullptr, order, lev, lstart);
 }
 
 constexpr int LT = 1024; // k_rsets, k_table: the threads of a block that works level by level
@@ -396,6 +414,33 @@ double length_sum(const double *len, size_t E) {
 	return s;
 }
 
+// What both searches check on the host before any HIP call: the records are andi_hip_nj's and D is finite above the
+// diagonal (the message names the first in row-major order).  par: 2n - 3, kid: 2 (n - 3) + 3 -- the tree rooted at C.
+bool tree_input_ok(andi_hip_ctx *ctx, const char *who, const andi_hip_nj_join *tree, size_t n, const double *D, int32_t *par,
+				   int32_t *kid) {
+	const size_t C = 2 * n - 3, nsets = n - 3;
+	std::vector<uint8_t> seen(2 * n);
+	std::vector<int2> pairs(nsets ? nsets : 1);
+	if (!records_ok(tree, n, seen.data(), pairs.data())) {
+		ctx->err = std::string(who) + ": the tree's records are not those of andi_hip_nj";
+		return false;
+	}
+	for (size_t i = 0; i < n; ++i)
+		for (size_t j = i + 1; j < n; ++j)
+			if (!std::isfinite(D[i * n + j])) {
+				char msg[160];
+				snprintf(msg, sizeof msg, "%s: D[%zu][%zu] is not finite (%g)", who, i, j, D[i * n + j]);
+				ctx->err = msg;
+				return false;
+			}
+	for (size_t s = 0; s + 2 < n; ++s) {
+		const bool last = s + 3 == n;
+		const int32_t ch[3] = {tree[s].a, tree[s].b, tree[s].c};
+		for (int k = 0; k < (last ? 3 : 2); ++k) par[ch[k]] = (int32_t)(last ? C : n + s), kid[2 * s + k] = ch[k];
+	}
+	return true;
+}
+
 } // namespace
 
 int andi_hip_refine(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, int method, double tol,
@@ -406,27 +451,9 @@ int andi_hip_refine(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, c
 					   "tol >= 0)";
 		return 1;
 	}
-	const size_t E = 2 * n - 3, C = E, nsets = n - 3, W = (n + 63) / 64, nkid = 2 * nsets + 3;
-	std::vector<uint8_t> seen(2 * n);
-	std::vector<int2> pairs(nsets ? nsets : 1);
-	if (!records_ok(tree, n, seen.data(), pairs.data())) {
-		ctx->err = "andi_hip_refine: the tree's records are not those of andi_hip_nj";
-		return 1;
-	}
-	for (size_t i = 0; i < n; ++i)
-		for (size_t j = i + 1; j < n; ++j)
-			if (!std::isfinite(D[i * n + j])) {
-				char msg[160];
-				snprintf(msg, sizeof msg, "andi_hip_refine: D[%zu][%zu] is not finite (%g)", i, j, D[i * n + j]);
-				ctx->err = msg;
-				return 1;
-			}
+	const size_t E = 2 * n - 3, nsets = n - 3, W = (n + 63) / 64, nkid = 2 * nsets + 3;
 	std::vector<int32_t> par(E), kid(nkid);
-	for (size_t s = 0; s + 2 < n; ++s) {
-		const bool last = s + 3 == n;
-		const int32_t ch[3] = {tree[s].a, tree[s].b, tree[s].c};
-		for (int k = 0; k < (last ? 3 : 2); ++k) par[ch[k]] = (int32_t)(last ? C : n + s), kid[2 * s + k] = ch[k];
-	}
+	if (!tree_input_ok(ctx, "andi_hip_refine", tree, n, D, par.data(), kid.data())) return 1;
 
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const uint32_t N = (uint32_t)n, Ed = (uint32_t)E, Wd = (uint32_t)W, nb = (N + 63) / 64;
@@ -495,5 +522,395 @@ int andi_hip_refine(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, c
 	r.moves = moves.size(), r.converged = converged;
 	*res = r;
 	if (log && !moves.empty()) memcpy(log, moves.data(), moves.size() * sizeof(andi_hip_refine_move));
+	return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Balanced subtree pruning and regrafting (andi_hip_refine_spr): the same rounds with a wider set of moves.  The tree is
+// kept as three neighbour slots per inner node (nb), which a move rewires; every round orients it from C again:
+//   k_orient   k_order on the slots: it also writes par and kid (the children of a node are its non-parent neighbours in
+//              slot order), so k_rsets, k_table, k_sums and k_blen above run on the tree unchanged;
+//   k_pre      one block, level by level: the nodes below every node and its preorder number, so that "y lies below x"
+//              is two comparisons of wavefront-uniform against per-lane values;
+//   k_leafrows B[x][.] of the leaves x: A transposed through LDS tiles, both sides in runs of 512 bytes;
+//   k_pairs    k_table with an edge y where the leaf c was: block = 64 columns y x 16 wavefronts, the far sides below x the
+//              deepest level first, then one wavefront down the path from C to y;
+//   k_walk     thread = (pruned edge u, which side is pruned, which of v0's other two neighbours the path leaves by): the
+//              other side depth-first, pending nodes with their R on a stack in global memory (entry d of thread t at
+//              d * threads + t), the best candidate kept;
+//   k_pick     one block: the greatest of the threads' bests by the contract's order (k_choose's pattern);
+//   k_rehang   one wavefront: the least leaves of X and Z for the log, and the move in the slots.
+// The host reads one record of 56 bytes a round; it carries the next tree's depth, which sizes the stacks.
+static_assert(sizeof(andi_hip_spr_move) == 24, "andi_hip_spr_move: the gain, two leaves, the hops, pad");
+
+namespace {
+
+struct SprRec {
+	double gain;
+	int32_t x, v0, q, vk, w, hops, first, second, stop, depth;
+	int32_t over, pad; // over: a walk's stack was too short (never, while the host sizes it from depth); the call fails
+};
+
+struct SprBest { // a thread's best candidate: the target edge f (-1: none), its ends and its hops
+	int32_t f, vk, w, k;
+};
+
+// One wavefront: k_order on the neighbour slots; the tree's depth goes into the round's record.
+__global__ __launch_bounds__(64) void k_orient(const int32_t *__restrict__ nb, uint32_t n, int32_t *par, int32_t *kid,
+											   int32_t *order, int32_t *lev, int32_t *lstart, SprRec *rec) {
+	const int32_t deepest = order_from_centre<true>(nb, n, par, kid, order, lev, lstart);
+	if (threadIdx.x == 0) rec->depth = deepest;
+}
+
+// One block: sz[x], the nodes of the subtree of x, the deepest level first; then tin[x], x's preorder number among the
+// non-centre nodes, the first level first.  y lies below x, or is x: tin[y] - tin[x] < sz[x], unsigned.
+__global__ __launch_bounds__(LT) void k_pre(const int32_t *__restrict__ order, const int32_t *__restrict__ lstart,
+											const int32_t *__restrict__ kid, uint32_t n, int32_t *sz, int32_t *tin) {
+	const int32_t deepest = lstart[0];
+	for (int32_t l = deepest; l >= 1; --l) {
+		const uint32_t end = (uint32_t)lstart[l + 1];
+		for (uint32_t i = (uint32_t)lstart[l] + threadIdx.x; i < end; i += LT) {
+			const int32_t x = order[i];
+			sz[x] = x < (int32_t)n ? 1 : 1 + sz[kid[2 * (size_t)(x - (int32_t)n)]] + sz[kid[2 * (size_t)(x - (int32_t)n) + 1]];
+		}
+		__syncthreads();
+	}
+	if (threadIdx.x == 0) {
+		const int32_t *kc = kid + 2 * (size_t)(n - 3);
+		tin[kc[0]] = 0, tin[kc[1]] = sz[kc[0]], tin[kc[2]] = sz[kc[0]] + sz[kc[1]];
+	}
+	__syncthreads();
+	for (int32_t l = 1; l <= deepest; ++l) {
+		const uint32_t end = (uint32_t)lstart[l + 1];
+		for (uint32_t i = (uint32_t)lstart[l] + threadIdx.x; i < end; i += LT) {
+			const int32_t x = order[i];
+			if (x < (int32_t)n) continue;
+			const int32_t a = kid[2 * (size_t)(x - (int32_t)n)], b = kid[2 * (size_t)(x - (int32_t)n) + 1];
+			tin[a] = tin[x] + 1, tin[b] = tin[x] + 1 + sz[a];
+		}
+		__syncthreads();
+	}
+}
+
+// Block = a tile of 64 leaves x by 64 edges y, four wavefronts: B[x][y] = A[y][x].
+__global__ __launch_bounds__(256) void k_leafrows(const double *__restrict__ A, uint32_t n, double *__restrict__ B) {
+	__shared__ double tile[64][65];
+	const uint32_t E = 2 * n - 3, y0 = blockIdx.x * 64, x0 = blockIdx.y * 64, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	for (uint32_t r = wave; r < 64; r += 4)
+		if (y0 + r < E && x0 + lane < n) tile[r][lane] = A[(size_t)(y0 + r) * n + x0 + lane];
+	__syncthreads();
+	for (uint32_t r = wave; r < 64; r += 4)
+		if (x0 + r < n && y0 + lane < E) B[(size_t)(x0 + r) * E + y0 + lane] = tile[lane][r];
+}
+
+// Block = 64 edges y (the lanes) x 16 wavefronts: B[x * E + y] for the inner nodes x; the leaves' rows are k_leafrows'.
+__global__ __launch_bounds__(LT) void k_pairs(const int32_t *__restrict__ kid, const int32_t *__restrict__ order,
+											  const int32_t *__restrict__ lstart, const int32_t *__restrict__ sz,
+											  const int32_t *__restrict__ tin, uint32_t n, double *B) {
+	const uint32_t E = 2 * n - 3, C = E, y = blockIdx.x * 64 + (threadIdx.x & 63), wave = threadIdx.x >> 6, NW = LT / 64;
+	const bool live = y < E;
+	const uint32_t ty = live ? (uint32_t)tin[y] : 0;
+	for (int32_t l = lstart[0]; l >= 1; --l) { // the far side below x: the deepest level first
+		const uint32_t end = (uint32_t)lstart[l + 1];
+		for (uint32_t i = (uint32_t)lstart[l] + wave; i < end; i += NW) {
+			const int32_t x = order[i];
+			if (!live || x < (int32_t)n || ty - (uint32_t)tin[x] < (uint32_t)sz[x]) continue;
+			const int32_t a = kid[2 * (size_t)(x - (int32_t)n)], b = kid[2 * (size_t)(x - (int32_t)n) + 1];
+			B[(size_t)x * E + y] = (B[(size_t)a * E + y] + B[(size_t)b * E + y]) * 0.5;
+		}
+		__syncthreads();
+	}
+	if (wave != 0 || !live) return;
+	// the far side above v, down the path from the centre to y, by one wavefront
+	const int32_t *kc = kid + 2 * (size_t)(C - n);
+	int32_t v = kc[0];
+	if (!(ty - (uint32_t)tin[v] < (uint32_t)sz[v])) v = ty - (uint32_t)tin[kc[1]] < (uint32_t)sz[kc[1]] ? kc[1] : kc[2];
+	int32_t o0, o1;
+	others_of(kid, n, C, v, o0, o1);
+	double up = (B[(size_t)o0 * E + y] + B[(size_t)o1 * E + y]) * 0.5;
+	B[(size_t)v * E + y] = up;
+	for (uint32_t step = 0; v != (int32_t)y && v >= (int32_t)n && step < E; ++step) { // (a path has fewer than E nodes)
+		const int32_t a = kid[2 * (size_t)(v - (int32_t)n)], b = kid[2 * (size_t)(v - (int32_t)n) + 1];
+		const bool in_a = ty - (uint32_t)tin[a] < (uint32_t)sz[a];
+		const int32_t x = in_a ? a : b, s = in_a ? b : a;
+		up = (B[(size_t)s * E + y] + up) * 0.5;
+		B[(size_t)x * E + y] = up;
+		v = x;
+	}
+}
+
+// the two neighbours of inner node v but `from`, kids before the parent, in slot order
+__device__ inline void beyond(const int32_t *par, const int32_t *kid, uint32_t n, int32_t v, int32_t from, int32_t &o0, int32_t &o1) {
+	const int32_t *k = kid + 2 * (size_t)(v - (int32_t)n);
+	if ((uint32_t)v == 2 * n - 3) {
+		o0 = k[0] == from ? k[1] : k[0], o1 = k[2] == from ? k[1] : k[2];
+		return;
+	}
+	const int32_t p = par[v];
+	o0 = k[0] == from ? k[1] : k[0], o1 = p == from ? k[1] : p;
+}
+
+// the edge between the adjacent nodes a and b: its lower node
+__device__ inline int32_t edge_of(const int32_t *par, uint32_t n, int32_t a, int32_t b) {
+	return (uint32_t)b != 2 * n - 3 && par[b] == a ? b : a;
+}
+
+// candidate t = 4 u + 2 side + way: the pruned node x, its neighbour v0, and v0's other two: q where the path leaves, p.
+// false: no such candidate (the upper side of a leaf edge).
+__device__ inline bool pruned_of(const int32_t *par, const int32_t *kid, uint32_t n, uint32_t t, int32_t &x, int32_t &v0, int32_t &p,
+								 int32_t &q) {
+	const int32_t u = (int32_t)(t >> 2);
+	const bool up = t & 2, second = t & 1;
+	if (up && u < (int32_t)n) return false;
+	x = up ? par[u] : u, v0 = up ? u : par[u];
+	int32_t o0, o1;
+	beyond(par, kid, n, v0, x, o0, o1);
+	q = second ? o1 : o0, p = second ? o0 : o1;
+	return true;
+}
+
+// candidate (g, i) comes before (G, I), as before() above, on the wider index of the SPR candidates
+__device__ inline bool before64(double g, int64_t i, double G, int64_t I) {
+	if (I < 0) return true;
+	if (i < 0) return false;
+	const bool gn = __builtin_isnan(g), Gn = __builtin_isnan(G);
+	if (gn || Gn) return gn == Gn ? i < I : Gn;
+	return g > G || (g == G && i < I);
+}
+
+// Thread t: the best target edge of candidate t.  SR, SN: the stacks, cap entries a thread.
+__global__ __launch_bounds__(64) void k_walk(const double *__restrict__ B, const int32_t *__restrict__ par,
+											 const int32_t *__restrict__ kid, uint32_t n, uint32_t cap, double *SR, int4 *SN,
+											 double *__restrict__ bg, SprBest *__restrict__ bb, SprRec *rec) {
+	const uint32_t E = 2 * n - 3, NT = 4 * E, t = blockIdx.x * 64 + threadIdx.x;
+	if (t >= NT) return;
+	double G = 0.0;
+	SprBest best = {-1, -1, -1, 0};
+	int32_t x, v0, p, q;
+	if (pruned_of(par, kid, n, t, x, v0, p, q) && q >= (int32_t)n && cap > 0) {
+		const int32_t ep = edge_of(par, n, v0, p), e1 = edge_of(par, n, v0, q);
+		const double *Bx = B + (size_t)(t >> 2) * E, *By = B + (size_t)ep * E;
+		const double dXY0 = Bx[ep], dXW = Bx[e1], dYW = By[e1];
+		uint32_t sp = 1;
+		SR[t] = 0.0, SN[t] = make_int4(q, v0, 0, 0);
+		while (sp > 0) {
+			--sp;
+			const int4 fr = SN[(size_t)sp * NT + t];
+			const double Rp = SR[(size_t)sp * NT + t];
+			const int32_t v = fr.x, k = fr.z + 1;
+			int32_t o[2];
+			beyond(par, kid, n, v, fr.y, o[0], o[1]);
+			const double h = k > 1022 ? 0.0 : __longlong_as_double((long long)(1023 - k) << 52);
+			for (int j = 0; j < 2; ++j) {
+				const int32_t w = o[j], f = edge_of(par, n, v, w);
+				const double R = 0.5 * Rp + Bx[edge_of(par, n, v, o[1 - j])];
+				const double dXZ = Bx[f], dYZ = By[f], Bff = B[(size_t)f * E + f];
+				const double t1 = (0.5 * (1.0 - h)) * (dXY0 - dXZ), t2 = 0.5 * dXW - (0.5 * h) * dXZ;
+				const double t3 = 0.5 * dYW - (0.5 * h) * dYZ, t4 = 0.5 * Bff - (0.25 * h) * (dYZ + dXZ);
+				const double g = (((t1 + t2) - t3) + t4) - 0.25 * R;
+				if (before64(g, f, G, best.f)) G = g, best = {f, v, w, k};
+				if (w < (int32_t)n) continue;
+				if (sp < cap) { // (pending entries: one per node of the path and one more; cap holds them)
+					SR[(size_t)sp * NT + t] = R, SN[(size_t)sp * NT + t] = make_int4(w, v, k, 0);
+					++sp;
+				} else rec->over = 1;
+			}
+		}
+	}
+	bg[t] = G, bb[t] = best;
+}
+
+// One block: the greatest of the 4 E bests, index (2 u + side) E + f, and whether the search goes on.
+__global__ __launch_bounds__(CT) void k_pick(const double *__restrict__ bg, const SprBest *__restrict__ bb,
+											 const int32_t *__restrict__ par, const int32_t *__restrict__ kid, uint32_t n, double tol,
+											 int can_move, SprRec *__restrict__ rec) {
+	__shared__ double sg[CT];
+	__shared__ int64_t si[CT];
+	__shared__ uint32_t st[CT];
+	const uint32_t E = 2 * n - 3;
+	double G = 0.0;
+	int64_t I = -1;
+	uint32_t Tb = 0;
+	for (uint32_t t = threadIdx.x; t < 4 * E; t += CT) {
+		const int32_t f = bb[t].f;
+		const int64_t i = f < 0 ? -1 : (int64_t)(t >> 1) * E + f;
+		if (before64(bg[t], i, G, I)) G = bg[t], I = i, Tb = t;
+	}
+	sg[threadIdx.x] = G, si[threadIdx.x] = I, st[threadIdx.x] = Tb;
+	__syncthreads();
+	for (uint32_t h = CT / 2; h > 0; h >>= 1) {
+		if (threadIdx.x < h && before64(sg[threadIdx.x + h], si[threadIdx.x + h], sg[threadIdx.x], si[threadIdx.x]))
+			sg[threadIdx.x] = sg[threadIdx.x + h], si[threadIdx.x] = si[threadIdx.x + h], st[threadIdx.x] = st[threadIdx.x + h];
+		__syncthreads();
+	}
+	if (threadIdx.x != 0) return;
+	G = sg[0], I = si[0], Tb = st[0];
+	rec->gain = I < 0 ? 0.0 : G;
+	rec->x = -1, rec->v0 = rec->q = rec->vk = rec->w = -1, rec->hops = 0, rec->first = rec->second = -1;
+	if (I >= 0) {
+		int32_t x, v0, p, q;
+		pruned_of(par, kid, n, Tb, x, v0, p, q);
+		rec->x = x, rec->v0 = v0, rec->q = q, rec->vk = bb[Tb].vk, rec->w = bb[Tb].w, rec->hops = bb[Tb].k;
+	}
+	rec->stop = (I < 0 || !(G > tol)) ? 1 : can_move ? 0 : 2;
+}
+
+// the least leaf that is not below x, by one wavefront
+__device__ inline int32_t least_outside(const uint64_t *sets, uint32_t n, uint32_t W, int32_t x, uint32_t lane) {
+	if (x < (int32_t)n) return x == 0 ? 1 : 0;
+	uint32_t m = ~0u;
+	const uint64_t *set = sets + (size_t)(x - (int32_t)n) * W;
+	for (uint32_t w = lane; w < W; w += 64) {
+		const uint64_t word = ~set[w] & (w + 1 == W && (n & 63) ? (1ull << (n & 63)) - 1 : ~0ull);
+		if (word && m == ~0u) m = w * 64 + (uint32_t)__builtin_ctzll(word);
+	}
+	for (int s = 32; s > 0; s >>= 1) {
+		const uint32_t o = __shfl_xor(m, s);
+		m = o < m ? o : m;
+	}
+	return (int32_t)m;
+}
+
+// the slot of inner node i that holds t
+__device__ inline int32_t *slot_of(int32_t *nb, uint32_t n, int32_t i, int32_t t) {
+	int32_t *s = nb + 3 * (size_t)(i - (int32_t)n);
+	return s[0] == t ? s : s[1] == t ? s + 1 : s + 2;
+}
+
+// One wavefront: the least leaves of X and Z into the record; if the search goes on, the move in the slots.
+__global__ __launch_bounds__(64) void k_rehang(SprRec *rec, int32_t *nb, const int32_t *__restrict__ par,
+											   const uint64_t *__restrict__ sets, uint32_t n, uint32_t W) {
+	const int32_t x = rec->x, v0 = rec->v0, q = rec->q, vk = rec->vk, w = rec->w, stop = rec->stop;
+	if (x < 0) return;
+	const uint32_t C = 2 * n - 3, lane = threadIdx.x;
+	const bool x_below = (uint32_t)x != C && par[x] == v0, w_below = (uint32_t)w != C && par[w] == vk;
+	const int32_t first = x_below ? least_leaf(sets, n, W, x, lane) : least_outside(sets, n, W, v0, lane);
+	const int32_t second = w_below ? least_leaf(sets, n, W, w, lane) : least_outside(sets, n, W, vk, lane);
+	if (lane != 0) return;
+	rec->first = first, rec->second = second;
+	if (stop) return;
+	int32_t *s0 = nb + 3 * (size_t)(v0 - (int32_t)n);
+	const int32_t p = s0[0] != x && s0[0] != q ? s0[0] : s0[1] != x && s0[1] != q ? s0[1] : s0[2];
+	int32_t *in_p = p >= (int32_t)n ? slot_of(nb, n, p, v0) : nullptr, *in_q = q >= (int32_t)n ? slot_of(nb, n, q, v0) : nullptr;
+	int32_t *of_p = slot_of(nb, n, v0, p), *of_q = slot_of(nb, n, v0, q), *in_k = slot_of(nb, n, vk, w);
+	int32_t *in_w = w >= (int32_t)n ? slot_of(nb, n, w, vk) : nullptr;
+	if (in_p) *in_p = q;
+	if (in_q) *in_q = p;
+	*of_p = vk, *of_q = w, *in_k = v0;
+	if (in_w) *in_w = v0;
+}
+
+} // namespace
+
+int andi_hip_refine_spr(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, double tol, size_t max_moves,
+						andi_hip_nj_join *out, andi_hip_refine_result *res, andi_hip_spr_move *log) {
+	if (!ctx || !tree || !D || !out || !res || n < 3 || n > 65535 || !(tol >= 0)) {
+		if (ctx) ctx->err = "andi_hip_refine_spr: bad arguments (ctx, tree, D, out and res must be given, 3 <= n <= 65535, tol >= 0)";
+		return 1;
+	}
+	const size_t E = 2 * n - 3, C = E, nsets = n - 3, W = (n + 63) / 64, nkid = 2 * nsets + 3, NT = 4 * E;
+	std::vector<int32_t> par(E), kid(nkid), slots(3 * (n - 2));
+	if (!tree_input_ok(ctx, "andi_hip_refine_spr", tree, n, D, par.data(), kid.data())) return 1;
+	for (size_t i = n; i <= C; ++i) {
+		int32_t *s = slots.data() + 3 * (i - n);
+		s[0] = kid[2 * (i - n)], s[1] = kid[2 * (i - n) + 1], s[2] = i == C ? kid[2 * (i - n) + 2] : par[i];
+	}
+
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const uint32_t N = (uint32_t)n, Ed = (uint32_t)E, Wd = (uint32_t)W, nb = (N + 63) / 64, eb = (Ed + 63) / 64;
+	hipStream_t st = ctx->stream;
+	DevScope dev(st), stacks(st);
+	double *A = nullptr, *B = nullptr, *dD = nullptr, *T = nullptr, *dlen = nullptr, *bg = nullptr, *SR = nullptr;
+	int32_t *dnb = nullptr, *dpar = nullptr, *dkid = nullptr, *order = nullptr, *lev = nullptr, *lstart = nullptr, *sz = nullptr, *tin = nullptr;
+	uint64_t *sets = nullptr;
+	SprBest *bb = nullptr;
+	int4 *SN = nullptr;
+	SprRec *drec = nullptr;
+	dev.alloc(&B, E * E), dev.alloc(&A, E * n);
+	if (dev.err != hipSuccess) {
+		char msg[240];
+		snprintf(msg, sizeof msg, "andi_hip_refine_spr: the tables of averages need %zu + %zu bytes of device memory: %s",
+				 E * E * sizeof(double), E * n * sizeof(double), hipGetErrorString(dev.err));
+		(void)hipGetLastError();
+		ctx->err = msg;
+		return 1;
+	}
+	dev.alloc(&dD, n * n), dev.alloc(&T, 4 * E), dev.alloc(&dlen, 2 * E), dev.alloc(&dpar, E + 1), dev.alloc(&dkid, nkid);
+	dev.alloc(&dnb, slots.size()), dev.alloc(&order, E), dev.alloc(&lev, E + 1), dev.alloc(&lstart, E + 2), dev.alloc(&sz, E);
+	dev.alloc(&tin, E), dev.alloc(&sets, nsets ? nsets * W : 1), dev.alloc(&bg, NT), dev.alloc(&bb, NT), dev.alloc(&drec, 1);
+	hipError_t e = dev.err;
+	if (e == hipSuccess) e = hipMemcpyAsync(dD, D, n * n * sizeof(double), hipMemcpyHostToDevice, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(dnb, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+	SprRec rec;
+	if (e == hipSuccess) e = hipMemsetAsync(drec, 0, sizeof rec, st);
+	if (e == hipSuccess) {
+		k_mirror<<<N, 256, 0, st>>>(dD, N);
+		k_orient<<<1, 64, 0, st>>>(dnb, N, dpar, dkid, order, lev, lstart, drec);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(&rec, drec, sizeof rec, hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	std::vector<andi_hip_spr_move> moves; // (the caller's arrays are written on success only)
+	int converged = 0;
+	size_t cap = 0;
+	while (e == hipSuccess) {
+		const size_t need = 2 * (size_t)rec.depth + 2; // a path has at most 2 depth edges
+		if (need > cap) {
+			stacks.release();
+			cap = need;
+			stacks.alloc(&SR, cap * NT), stacks.alloc(&SN, cap * NT);
+			if (stacks.err != hipSuccess) {
+				char msg[240];
+				snprintf(msg, sizeof msg, "andi_hip_refine_spr: the walk's stacks need %zu bytes of device memory (depth %d): %s",
+						 cap * NT * (sizeof(double) + sizeof(int4)), rec.depth, hipGetErrorString(stacks.err));
+				(void)hipGetLastError();
+				ctx->err = msg;
+				return 1;
+			}
+		}
+		if (nsets) k_rsets<<<1, LT, 0, st>>>(order, lstart, dkid, N, Wd, sets);
+		k_pre<<<1, LT, 0, st>>>(order, lstart, dkid, N, sz, tin);
+		k_table<<<nb, LT, 0, st>>>(dD, dkid, order, lstart, sets, N, Wd, A);
+		k_sums<<<Ed, 256, 0, st>>>(A, dpar, dkid, sets, lev, N, Wd, T);
+		if (moves.empty()) k_blen<<<eb, 64, 0, st>>>(T, dpar, dkid, N, dlen);
+		k_leafrows<<<dim3(eb, nb), 256, 0, st>>>(A, N, B);
+		k_pairs<<<eb, LT, 0, st>>>(dkid, order, lstart, sz, tin, N, B);
+		k_walk<<<(uint32_t)(NT + 63) / 64, 64, 0, st>>>(B, dpar, dkid, N, (uint32_t)cap, SR, SN, bg, bb, drec);
+		k_pick<<<1, CT, 0, st>>>(bg, bb, dpar, dkid, N, tol, moves.size() < max_moves ? 1 : 0, drec);
+		k_rehang<<<1, 64, 0, st>>>(drec, dnb, dpar, sets, N, Wd);
+		k_orient<<<1, 64, 0, st>>>(dnb, N, dpar, dkid, order, lev, lstart, drec); // (a stop leaves the slots: the same tree again)
+		e = hipGetLastError();
+		if (e == hipSuccess) e = hipMemcpyAsync(&rec, drec, sizeof rec, hipMemcpyDeviceToHost, st);
+		if (e == hipSuccess) e = hipStreamSynchronize(st);
+		if (e != hipSuccess) break;
+		if (rec.over) {
+			ctx->err = "andi_hip_refine_spr: a walk's stack was too short for the tree's depth (a bug: the result is not used)";
+			return 1;
+		}
+		if (rec.stop) {
+			converged = rec.stop == 1;
+			break;
+		}
+		andi_hip_spr_move m;
+		m.gain = rec.gain, m.first = rec.first, m.second = rec.second, m.hops = rec.hops, m.pad = 0;
+		moves.push_back(m);
+	}
+	std::vector<double> len(2 * E);
+	if (e == hipSuccess) {
+		k_blen<<<eb, 64, 0, st>>>(T, dpar, dkid, N, dlen + E);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipMemcpyAsync(len.data(), dlen, 2 * E * sizeof(double), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipMemcpyAsync(kid.data(), dkid, nkid * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+	if (e == hipSuccess) e = hipStreamSynchronize(st);
+	if (e != hipSuccess) return fail(ctx, "andi_hip_refine_spr", e);
+
+	number_records(kid.data(), len.data() + E, n, out);
+	andi_hip_refine_result r;
+	memset(&r, 0, sizeof r);
+	r.length_before = length_sum(len.data(), E), r.length_after = length_sum(len.data() + E, E);
+	r.moves = moves.size(), r.converged = converged;
+	*res = r;
+	if (log && !moves.empty()) memcpy(log, moves.data(), moves.size() * sizeof(andi_hip_spr_move));
 	return 0;
 }

@@ -442,6 +442,9 @@ static void usage(int status) {
 		"                       interchanges on the GPU until none shortens the tree (as FastME's BNNI); the tree then carries\n"
 		"                       its balanced (BME) lengths, which --lengths, --root and --fit start from; not together with\n"
 		"                       --trees-only\n"
+		"      --refine-moves=MOVES  With --refine=bnni: the moves of the search, 'nni' (the default), interchanges across one\n"
+		"                       branch, or 'spr', balanced subtree pruning and regrafting: a round re-hangs one subtree on any\n"
+		"                       other branch (as FastME's SPR), which leaves the local optima of interchanges\n"
 		"      --refine-tol=X   With --refine: an interchange is made only if it shortens the tree by more than X, in the units\n"
 		"                       of the printed matrix; default: 1e-9\n"
 		"      --refine-report=FILE  With --refine: write the refinement of the first matrix's tree to FILE, tab-separated: the\n"
@@ -694,9 +697,9 @@ static int join_bootstrap(andi_hip_ctx *ctx, const andi_hip_model *M, size_t n, 
 /* --refine=bnni: every joined tree is refined against the matrix it was joined from (andi_hip_refine) right after the join,
  * so every file of trees sees the refined records, with their balanced lengths.  --refine-report: the point estimate's. */
 typedef struct {
-	int on, reported;
+	int on, reported, spr;
 	double tol;
-	const char *tol_arg, *report_path;
+	const char *tol_arg, *report_path, *moves_arg;
 	FILE *rf;
 } refine_opts;
 static refine_opts refopt = {.tol = 1e-9};
@@ -743,16 +746,19 @@ static size_t changed_branches(const andi_hip_nj_join *before, const andi_hip_nj
 }
 
 /* The records J of the K-th matrix D (1 = the point estimate) refined in place.  A tree that cannot be refined stays as it
- * was joined, with a soft warning; one whose search ends at the cap of 10 n interchanges is kept as it stands, with one. */
+ * was joined, with a soft warning; one whose search ends at the cap of 10 n interchanges is kept as it stands, with one.
+ * --refine-moves=spr: the same through andi_hip_refine_spr, whose log has the hops of every move beside. */
 static void refine_joined(andi_hip_ctx *ctx, andi_hip_nj_join *J, size_t n, const double *D, unsigned long k, const char **names,
 						  int truncate) {
 	if (!refopt.on || n < 3) return;
 	const int report = k == 1 && refopt.rf && !refopt.reported;
 	const size_t cap = 10 * n;
 	andi_hip_nj_join *out = xmalloc((n - 2) * sizeof *out);
-	andi_hip_refine_move *log = report ? xmalloc(cap * sizeof *log) : NULL;
+	andi_hip_refine_move *log = report && !refopt.spr ? xmalloc(cap * sizeof *log) : NULL;
+	andi_hip_spr_move *slog = report && refopt.spr ? xmalloc(cap * sizeof *slog) : NULL;
 	andi_hip_refine_result r;
-	if (andi_hip_refine(ctx, J, n, D, ANDI_REFINE_BNNI, refopt.tol, cap, out, &r, log)) {
+	if (refopt.spr ? andi_hip_refine_spr(ctx, J, n, D, refopt.tol, cap, out, &r, slog)
+				   : andi_hip_refine(ctx, J, n, D, ANDI_REFINE_BNNI, refopt.tol, cap, out, &r, log)) {
 		soft_warnx("The tree of matrix %lu is written unrefined: %s", k, andi_hip_last_error(ctx));
 	} else {
 		if (!r.converged)
@@ -762,16 +768,19 @@ static void refine_joined(andi_hip_ctx *ctx, andi_hip_nj_join *J, size_t n, cons
 			const int w = truncate ? 10 : -1; /* (as the matrix prints a name) */
 			refopt.reported = 1;
 			fputs("#method\tmoves\tconverged\tlength_before\tlength_after\tchanged\n", f);
-			fprintf(f, "bnni\t%llu\t%d\t%.8g\t%.8g\t%zu\n", (unsigned long long)r.moves, (int)r.converged, r.length_before, r.length_after,
-					changed_branches(J, out, n));
-			fputs("#move\tgain\tfirst\tsecond\n", f);
+			fprintf(f, "%s\t%llu\t%d\t%.8g\t%.8g\t%zu\n", refopt.spr ? "bspr" : "bnni", (unsigned long long)r.moves, (int)r.converged,
+					r.length_before, r.length_after, changed_branches(J, out, n));
+			fputs(refopt.spr ? "#move\tgain\tfirst\tsecond\thops\n" : "#move\tgain\tfirst\tsecond\n", f);
 			for (size_t m = 0; m < r.moves; m++)
-				fprintf(f, "%zu\t%.8g\t%.*s\t%.*s\n", m + 1, log[m].gain, w, names[log[m].first], w, names[log[m].second]);
+				if (refopt.spr)
+					fprintf(f, "%zu\t%.8g\t%.*s\t%.*s\t%d\n", m + 1, slog[m].gain, w, names[slog[m].first], w, names[slog[m].second],
+							(int)slog[m].hops);
+				else fprintf(f, "%zu\t%.8g\t%.*s\t%.*s\n", m + 1, log[m].gain, w, names[log[m].first], w, names[log[m].second]);
 			if (ferror(f)) err(1, "%s", refopt.report_path);
 		}
 		memcpy(J, out, (n - 2) * sizeof *out);
 	}
-	free(out), free(log);
+	free(out), free(log), free(slog);
 }
 
 /* --tree: the tree (neighbor-joining, or --tree-method's) of the K-th printed matrix (1 = the point estimate) as one Newick
@@ -1559,6 +1568,7 @@ int main(int argc, char *argv[]) {
 												 {"lengths", required_argument, NULL, 0},
 												 {"fit", required_argument, NULL, 0},
 												 {"refine", required_argument, NULL, 0},
+												 {"refine-moves", required_argument, NULL, 0},
 												 {"refine-tol", required_argument, NULL, 0},
 												 {"refine-report", required_argument, NULL, 0},
 												 {"linkage", required_argument, NULL, 0},
@@ -1629,6 +1639,12 @@ int main(int argc, char *argv[]) {
 					if (!strcasecmp(optarg, "none")) refopt.on = 0;
 					else if (!strcasecmp(optarg, "bnni")) refopt.on = 1;
 					else errx(1, "Expected one of 'none' or 'bnni' for --refine, but '%s' was given.", optarg);
+				}
+				if (!strcmp(o, "refine-moves")) {
+					refopt.moves_arg = optarg;
+					if (!strcasecmp(optarg, "nni")) refopt.spr = 0;
+					else if (!strcasecmp(optarg, "spr")) refopt.spr = 1;
+					else errx(1, "Expected one of 'nni' or 'spr' for --refine-moves, but '%s' was given.", optarg);
 				}
 				if (!strcmp(o, "refine-tol")) refopt.tol_arg = optarg;
 				if (!strcmp(o, "refine-report")) refopt.report_path = optarg;
@@ -1775,6 +1791,7 @@ int main(int argc, char *argv[]) {
 	if (refopt.on && trees_only)
 		errx(1, "Trees (--refine=bnni) are not refined together with --trees-only: the bootstrap matrices stay on the GPU.");
 	if (refopt.report_path && !refopt.on) errx(1, "A refinement report (--refine-report) needs --refine=bnni.");
+	if (refopt.moves_arg && !refopt.on) errx(1, "The moves of the refinement (--refine-moves) need --refine=bnni.");
 	if (refopt.tol_arg) {
 		errno = 0;
 		char *end;

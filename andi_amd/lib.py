@@ -142,6 +142,7 @@ SYMBOLS = {
     "andi_hip_fit": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, _P, _P, _P, _P]),
     "andi_hip_relength": (C.c_int, [_P, C.c_size_t, _P, _P]),
     "andi_hip_refine": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_int, C.c_double, C.c_size_t, _P, _P, _P]),
+    "andi_hip_refine_spr": (C.c_int, [_P, _P, C.c_size_t, _P, C.c_double, C.c_size_t, _P, _P, _P]),
     "andi_hip_parse_newick": (C.c_int, [C.c_char_p, C.POINTER(C.c_char_p), C.c_size_t, C.c_int, _P, C.c_char_p, C.c_size_t]),
     "andi_hip_format_jplace": (C.c_size_t, [_P, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t,
                                             C.POINTER(C.c_char_p), C.c_int, _P, C.c_size_t]),
@@ -1314,6 +1315,29 @@ def refine(ctx: Context, J, D, method="bnni", tol=0.0, max_moves=None, log=False
     moves = np.zeros(max(cap, 1), REFINE_MOVE) if log else None
     ctx._check(load().andi_hip_refine(ctx._h, J.ctypes.data, n, D.ctypes.data, m, float(tol), cap, out.ctypes.data,
                                       res.ctypes.data, moves.ctypes.data if log else None), "refine")
+    return (out, res[0], moves[:int(res[0]["moves"])].copy()) if log else (out, res[0])
+
+
+# andi_hip_spr_move: a move's gain, the least leaves of the pruned side and of the side beyond the target edge, the hops
+SPR_MOVE = np.dtype([("gain", "<f8"), ("first", "<i4"), ("second", "<i4"), ("hops", "<i4"), ("pad", "<i4")])
+
+
+def refine_spr(ctx: Context, J, D, tol=0.0, max_moves=None, log=False):
+    """refine() with balanced subtree pruning and regrafting as the move (andi_hip_refine_spr): a round re-hangs one
+    subtree on any other branch.  The same arguments and results; the log's entries are of dtype SPR_MOVE."""
+    J = np.ascontiguousarray(J, dtype=NJ_JOIN)
+    n = len(J) + 2
+    D = np.ascontiguousarray(D, dtype=np.float64)
+    if D.shape != (n, n):
+        raise ValueError("D must be (n, n) for the n - 2 records of J")
+    cap = 10 * n if max_moves is None else int(max_moves)
+    if cap < 0:
+        raise ValueError("max_moves must not be negative")
+    out = np.zeros(len(J), NJ_JOIN)
+    res = np.zeros(1, REFINE)
+    moves = np.zeros(max(cap, 1), SPR_MOVE) if log else None
+    ctx._check(load().andi_hip_refine_spr(ctx._h, J.ctypes.data, n, D.ctypes.data, float(tol), cap, out.ctypes.data,
+                                          res.ctypes.data, moves.ctypes.data if log else None), "refine_spr")
     return (out, res[0], moves[:int(res[0]["moves"])].copy()) if log else (out, res[0])
 
 

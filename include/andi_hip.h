@@ -32,7 +32,8 @@
  * and the tree-likeness score of every genome from all quartets: andi_hip_delta_scores (an addition only); and the root of
  * a tree without an outgroup: andi_hip_root and andi_hip_format_newick_rooted (additions only); and a tree's branch
  * lengths refit to its matrix by least squares: andi_hip_fit and andi_hip_relength (additions only); and a tree refined
- * by balanced nearest-neighbor interchanges, with its balanced lengths: andi_hip_refine (an addition only).
+ * by balanced nearest-neighbor interchanges, with its balanced lengths: andi_hip_refine, and by balanced subtree pruning
+ * and regrafting: andi_hip_refine_spr (additions only).
  */
 #ifndef ANDI_HIP_H
 #define ANDI_HIP_H
@@ -994,6 +995,54 @@ typedef struct {
 int andi_hip_refine(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, int method, double tol,
 					size_t max_moves, andi_hip_nj_join *out, andi_hip_refine_result *res,
 					andi_hip_refine_move *log /* NULL or max_moves */);
+
+/* The same search with FastME's wider move, balanced subtree pruning and regrafting (SPR): a round prunes one subtree and
+ * re-hangs it on any other branch, so it leaves the local optima of interchanges and comes back from a far start in few
+ * rounds.  Arguments, validation (messages begin "andi_hip_refine_spr:"), error path, result record, output numbering and
+ * the balanced lengths are andi_hip_refine's; there is no method argument.  log: NULL, or max_moves entries of 24 bytes.
+ *
+ * The move.  The tree is unrooted.  Prune the side X of an edge (x, v0), x the node on X's side; the inner node v0 has two
+ * other neighbours p and q.  Y0 is the side of (p, v0) away from v0.  A path v0, v1 = q, ..., vk (k >= 1) of inner nodes
+ * ends in a target edge f = (vk, w); Z is the side of f beyond w, Y_i the side of v_i's third edge, W1 the side of (v0, v1)
+ * beyond v1.  After the move p and q are adjacent and v0 sits on f with the neighbours x, vk and w.  k = 1 is an
+ * interchange.  The candidates of a round: every side of every edge as X (the upper side only of an inner edge), with
+ * every edge on the other side that is not adjacent to v0 as f.
+ *
+ * Bit-exact to this contract (tests/spr_model.py restates it), every operation rounded on its own:
+ *  - the tree, A, S and the lengths are andi_hip_refine's, on the tree rooted at C.  An edge goes by its lower node;
+ *  - B(e, f) for all edges e, f, a (2n - 3)^2 table: the balanced average between the side of e away from f and the side
+ *    of f away from e; B(e, e) between the two sides of e.  It is A's recursion with the edge f where the leaf c was, "f
+ *    lies below e or is e" where "c lies below v" was: f not below e: for a leaf e, B(e, f) = A(f, e); for an inner e with
+ *    children a and b, B(e, f) = (B(a, f) + B(b, f)) * 0.5.  f below e or e: with q = parent(e) != C and s the sibling,
+ *    B(e, f) = (B(s, f) + B(q, f)) * 0.5; with parent(e) = C, (B(s1, f) + B(s2, f)) * 0.5 over C's other two children in
+ *    slot order.  B is symmetric only up to rounding; the terms below name the entry they read;
+ *  - with ex, ep, e1, ey_i the edges of X, Y0, W1 and Y_i (ex = (x, v0), ep = (p, v0), e1 = (v0, v1)):
+ *    R_0 = +0.0, R_i = 0.5 * R_(i-1) + B(ex, ey_i); h = 2^-k, exact, and +0.0 once k > 1022;
+ *      t1 = (0.5 * (1.0 - h)) * (B(ex, ep) - B(ex, f))      t2 = 0.5 * B(ex, e1) - (0.5 * h) * B(ex, f)
+ *      t3 = 0.5 * B(ep, e1) - (0.5 * h) * B(ep, f)          t4 = 0.5 * B(f, f) - (0.25 * h) * (B(ep, f) + B(ex, f))
+ *      gain = (((t1 + t2) - t3) + t4) - 0.25 * R_k
+ *    which is Pauplin's length of the tree minus that of the tree after the move, up to rounding;
+ *  - a round takes the greatest gain, a NaN below every number; ties go to the smaller edge ex, then to its lower side as
+ *    X before its upper side, then to the smaller edge f;
+ *  - the tree after a move.  Every inner node keeps three neighbour slots: at first a, b and the parent for a pair
+ *    record's node, a, b, c for C.  In p the slot that held v0 takes q, in q it takes p; in v0 the slot of p takes vk and
+ *    the slot of q takes w; in vk the slot of w takes v0, in w the slot of vk takes v0 (a leaf has no slots).  The next
+ *    round roots the tree at C again: the children of a node are its neighbours but its parent, in slot order, and
+ *    everything above is evaluated on that tree from nothing.  Node ids stay fixed;
+ *  - the stop rule is andi_hip_refine's: a gain that is not > tol ends the search with converged = 1, max_moves with
+ *    converged = 0.  A log entry: the gain, the least leaf of X (first), the least leaf of Z (second), and k (hops).
+ * On the device: B (8 (2n - 3)^2 bytes: 304 MB at 3085 leaves) beside andi_hip_refine's buffers, and the walk's stacks,
+ * 96 (2n - 3) (2 depth + 2) bytes for a tree `depth` edges deep from C; when either does not fit, the call fails through
+ * the context's error, which names the bytes.  The host looks at one record of 56 bytes a round. */
+typedef struct {
+	double gain;           /* what the move shortened the tree by */
+	int32_t first, second; /* the least leaf of the pruned side X, of the side Z beyond the target edge */
+	int32_t hops;          /* k: the inner nodes from v0 to the target edge, 1 for an interchange */
+	int32_t pad;
+} andi_hip_spr_move; /* 24 bytes */
+int andi_hip_refine_spr(andi_hip_ctx *ctx, const andi_hip_nj_join *tree, size_t n, const double *D, double tol,
+						size_t max_moves, andi_hip_nj_join *out, andi_hip_refine_result *res,
+						andi_hip_spr_move *log /* NULL or max_moves */);
 
 /* ------------------------------------------------------------------ */
 /* The k-mer sketch screen: which references are worth an exact run    */
